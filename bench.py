@@ -18,9 +18,20 @@ Two frame transports (--frame):
                   the tiles to rank 0 (RCCL over xGMI) and the device band
                   assembly (pt_assemble_bands_device); then rank 0's PCIe copy
                   of the frame to pinned host memory.
-The other transport is measured after the headline one with the same steps
-and reported under `frame_modes`, with per-leg times (max / min band kernel
-over ranks; device: gather, assembly, D2H on rank 0's stream).
+With --full the other transport is measured after the headline one with the
+same steps and reported under `frame_modes`, with per-leg times (max / min
+band kernel over ranks; device: gather, assembly, D2H on rank 0's stream).
+
+A plain run (no --full) sets up, warms up, times --steps steps and prints the
+line: metric, value, unit, ms_per_step, the ranks' GPUs and the headline
+transport's legs.  Everything measured or checked after the timed steps —
+`roofline` (a counting launch), `cpu_baseline` and `linf_vs_cpu_ref` (the
+oracle), the other frame transport — runs with --full only and is null /
+"skipped" in a plain line.  --dump-outputs DIR writes the frame of the last
+timed step, as rank 0 read it from host memory, to DIR/frame.npy (float32,
+(H, W, 3); k4's 201-MB frame as a fixed sample of its pixels, dump_outputs).
+The scene, the seed and the launch are fixed by the arguments, so two runs
+with the same arguments dump the same frame.
 
 Workloads (--config, BASELINE.json configs):
   k2 (default)  Cornell 512x512, 64 spp, 4 bounces (configs[1], the config the
@@ -39,7 +50,7 @@ Launched by torch.distributed.run (RANK / WORLD_SIZE in the environment), or,
 for `python bench.py --gpus N`, by this script itself: the parent spawns N
 fresh rank processes (it never touches the GPU) and exits with their status.
 
-Printed on rank 0: one JSON line with the driver's fields plus
+Printed on rank 0: one JSON line with the driver's fields plus (--full)
   roofline     : the dominant kernel's achieved rate against its roof.
                  k2/k4: k_render, FP32 VALU: reference-semantics ray-triangle
                  tests (exact, from a counting launch) x 47 FLOP (SURVEY.md
@@ -104,7 +115,7 @@ QNODE_B, UNITC_B, SHADOWQ_B, SHADOW_RES_B = 64, 64, 48, 8
 CLOSESTQ_B, CLOSEST_RES_B = 52, 16
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None)
@@ -118,10 +129,20 @@ def parse():
     ap.add_argument("--no-check", action="store_true", help="skip L-inf vs the CPU oracle")
     ap.add_argument("--no-secondary", action="store_true",
                     help="do not measure the other frame transport after the headline one")
-    a = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the roofline, the parity check and the CPU baseline on "
+                         "the oracle, and the other frame transport (each of which --no-* drops again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step, as read from host memory, to "
+                         "DIR/frame.npy (float32)")
+    a = ap.parse_args(argv)
     c = CONFIGS[a.config]
     a.steps = c["steps"] if a.steps is None else a.steps
     a.warmup = c["warmup"] if a.warmup is None else a.warmup
+    if not a.full:
+        # a plain run ends with its headline: everything measured or checked
+        # after the timed steps belongs to --full
+        a.no_cpu_baseline = a.no_check = a.no_secondary = True
     if a.scaling == "weak" and a.config != "k2":
         ap.error("--scaling weak is defined for k2 only")
     return a
@@ -449,6 +470,33 @@ def run_device_frame(ctx, steps, warmup):
     return elapsed, legs, (host.numpy().copy() if rank == 0 else None)
 
 
+DUMP_MAX_BYTES = 64_000_000
+DUMP_SAMPLE_PIXELS = 1 << 22   # 48 MiB of f32 RGB
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, fb):
+    """--dump-outputs: the frame the timed path left in host memory at its
+    last step, (H, W, 3) float32, as out_dir/frame.npy.  A frame above
+    DUMP_MAX_BYTES (k4) is written as a fixed sample of its pixels, (n, 3) in
+    ascending order of the flat pixel index row * W + column — the same
+    pixels on every run.  Returns the record for the result line."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    fb = np.ascontiguousarray(fb, dtype=np.float32)
+    rec = {"frame": {"file": "frame.npy", "dtype": "float32", "frame_shape": list(fb.shape)}}
+    if fb.nbytes > DUMP_MAX_BYTES:
+        n_pix = fb.shape[0] * fb.shape[1]
+        idx = np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).choice(n_pix, DUMP_SAMPLE_PIXELS,
+                                                                     replace=False))
+        fb = fb.reshape(n_pix, 3)[idx]
+        rec["frame"]["sample"] = (f"{DUMP_SAMPLE_PIXELS} of {n_pix} pixels, numpy RandomState("
+                                  f"{DUMP_SAMPLE_SEED}).choice without replacement, sorted")
+    rec["frame"]["shape"] = list(fb.shape)
+    np.save(os.path.join(out_dir, "frame.npy"), fb)
+    return rec
+
+
 def main():
     args = parse()
     from pathtracerpython_amd.launch import init_gloo, pg_timeout, rank_env, spawn_ranks, under_launcher
@@ -481,7 +529,6 @@ def main():
         # it down; the device-frame leg makes its own RCCL group for its gather
         init_gloo()
 
-    from oracle.oracle import host_threads
     from pathtracerpython_amd import scene_reader
     from pathtracerpython_amd.distributed import HostFrame, band_rows_of
     from pathtracerpython_amd.render import Renderer
@@ -597,11 +644,15 @@ def main():
     # CPU baseline) — before the secondary transport runs at all
     result = None
     if rank == 0:
-        from oracle import oracle
-        if args.config == "k5":
-            roofline = k5_roofline(r, p, k_ms)
-        else:
-            roofline = k_render_roofline(r, p, k_ms, W, rows, SPP, args.config)
+        dumped = dump_outputs(args.dump_outputs, fb) if args.dump_outputs else None
+        roofline = None
+        if args.full:
+            from oracle import oracle
+            from oracle.oracle import host_threads
+            if args.config == "k5":
+                roofline = k5_roofline(r, p, k_ms)
+            else:
+                roofline = k_render_roofline(r, p, k_ms, W, rows, SPP, args.config)
         linf = checked = over = None
         cpu = None
         want_cpu = not args.no_cpu_baseline and world == 1
@@ -682,12 +733,16 @@ def main():
             "linf_vs_cpu_ref": linf, "linf_checked": checked, "pixels_over": over,
             "roofline": roofline,
             "cpu_baseline": cpu,
+            "full": args.full,
+            "dumped_outputs": dumped,
         }
 
     # 3. the other transport, after the headline line is complete: bounded and
     # non-fatal (a failure or a hang is recorded under frame_modes, the
     # headline line is printed regardless)
-    if args.no_secondary:
+    if not args.full:
+        run = {"skipped": "measured with --full"}
+    elif args.no_secondary:
         run = {"skipped": "--no-secondary"}
     elif other_name == "host" and hf is None:
         run = {"skipped": f"host frame unavailable: {hf_err}"}

@@ -7,7 +7,9 @@ set -o pipefail
 mkdir -p gpurun_out/r06_final
 PARTS=k5 bash scripts/refresh_profiles.sh r06 > gpurun_out/r06_final/refresh_k5.log 2>&1
 rc=$?; tail -2 gpurun_out/r06_final/refresh_k5.log; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python3 bench.py --config k4 > gpurun_out/refresh_r06/profiles/r06_bench_k4.json 2> gpurun_out/r06_final/bench_k4.err
+# (the staging folders made above; --full: the line with its roofline, parity and CPU baseline)
+STAGE=$(ls -d "$PWD"/*/refresh_r06) && FINAL=$(ls -d "$PWD"/*/r06_final) || exit 1
+timeout -k 10 300 python3 bench.py --full --config k4 > "$STAGE/profiles/r06_bench_k4.json" 2> "$FINAL/bench_k4.err"
 rc=$?; cat gpurun_out/refresh_r06/profiles/r06_bench_k4.json; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 600 python3 -u scripts/run_configs.py 2>&1 | grep -v amdgpu.ids > gpurun_out/refresh_r06/profiles/r06_configs.jsonl
 rc=$?; cat gpurun_out/refresh_r06/profiles/r06_configs.jsonl; exit $rc

@@ -51,16 +51,16 @@ cd "$R"
 cp "$P/traffic_k2.json" "$R/profiles/traffic_k2.json"
 # 3-4. K2 bench: rocprof stats of the bench command, then the line itself
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_k2" -o k2 \
-    -- python3 "$R/bench.py" --steps 50 --no-cpu-baseline --no-check > "$OUT/trace_k2.log" 2>&1
+    -- python3 "$R/bench.py" --full --steps 50 --no-cpu-baseline --no-check > "$OUT/trace_k2.log" 2>&1
 cp "$OUT/trace_k2/k2_kernel_stats.csv" "$P/${TAG}_k2_kernel_stats.csv"
-timeout -k 10 400 python3 "$R/bench.py" > "$P/${TAG}_bench_k2.json" 2> "$OUT/bench_k2.err"
+timeout -k 10 400 python3 "$R/bench.py" --full > "$P/${TAG}_bench_k2.json" 2> "$OUT/bench_k2.err"
 cat "$P/${TAG}_bench_k2.json"
 fi
 if [[ " $PARTS " == *" k5 "* ]]; then
 cd "$R"
 # 5. K5
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_k5" -o k5 \
-    -- python3 "$R/bench.py" --config k5 --steps 1 --warmup 0 --no-cpu-baseline --no-check \
+    -- python3 "$R/bench.py" --full --config k5 --steps 1 --warmup 0 --no-cpu-baseline --no-check \
     > "$OUT/trace_k5.log" 2>&1
 cp "$OUT/trace_k5/k5_kernel_stats.csv" "$P/${TAG}_k5_kernel_stats.csv"
 cd /tmp
@@ -80,6 +80,6 @@ python3 "$R/scripts/stamp_traffic.py" "$P/${TAG}_pmc_k5_traffic.json" "$P/traffi
     "$P/${TAG}_pmc_k5_closest_traffic.json"
 cd "$R"
 cp "$P/traffic_k5.json" "$R/profiles/traffic_k5.json"
-timeout -k 10 400 python3 "$R/bench.py" --config k5 > "$P/${TAG}_bench_k5.json" 2> "$OUT/bench_k5.err"
+timeout -k 10 400 python3 "$R/bench.py" --full --config k5 > "$P/${TAG}_bench_k5.json" 2> "$OUT/bench_k5.err"
 cat "$P/${TAG}_bench_k5.json"
 fi

@@ -86,3 +86,38 @@ def test_duplicate_devices():
     rk = [{"rank": r, "pci_bus_id": "0000:%02x:00" % b} for r, b in enumerate((0x05, 0x15, 0x05, 0x25, 0x15))]
     assert bench.duplicate_devices(rk) == ["0000:05:00", "0000:15:00"]
     assert bench.duplicate_devices(rk[:2]) == [] and bench.duplicate_devices(rk[:1]) == []
+
+
+def test_plain_run_leaves_the_extras_to_full():
+    """Without --full nothing runs after the timed steps (no oracle, no other
+    transport); with it the --no-* switches still drop one leg each."""
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert a.no_check and a.no_cpu_baseline and a.no_secondary
+    a = bench.parse(["--full", "--no-check", "--dump-outputs", "d"])
+    assert a.full and a.no_check and not a.no_cpu_baseline and not a.no_secondary
+    assert a.dump_outputs == "d" and a.steps == bench.CONFIGS["k2"]["steps"]
+
+
+def test_dump_outputs(tmp_path):
+    """--dump-outputs: a frame is written whole as float32; one above the size
+    cap as the same sample of its pixels every time, in pixel order."""
+    import numpy as np
+    import bench
+    rs = np.random.RandomState(3)
+    fb = rs.rand(37, 19, 3).astype(np.float32)
+    rec = bench.dump_outputs(str(tmp_path / "a"), fb)
+    got = np.load(tmp_path / "a" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, fb)
+    assert rec["frame"]["shape"] == [37, 19, 3] and "sample" not in rec["frame"]
+    H, W = 2400, 2400   # 69 MB of f32 RGB: above the cap
+    big = np.arange(H * W, dtype=np.float32)[:, None].repeat(3, axis=1).reshape(H, W, 3)
+    assert big.nbytes > bench.DUMP_MAX_BYTES
+    rec = bench.dump_outputs(str(tmp_path / "b"), big)
+    s1 = np.load(tmp_path / "b" / "frame.npy")
+    assert s1.dtype == np.float32 and s1.shape == (bench.DUMP_SAMPLE_PIXELS, 3)
+    assert s1.nbytes <= bench.DUMP_MAX_BYTES and rec["frame"]["frame_shape"] == [H, W, 3]
+    assert (np.diff(s1[:, 0]) > 0).all()   # distinct pixels (the value is the pixel's index), ascending
+    bench.dump_outputs(str(tmp_path / "c"), big)
+    assert np.array_equal(np.load(tmp_path / "c" / "frame.npy"), s1)

@@ -692,7 +692,7 @@ def test_bench_host_frame_path_two_ranks(tmp_path):
     from conftest import ROOT
     env = dict(os.environ, PT_BENCH_REHEARSE="1")
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6",
-                          "--warmup", "2", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
+                          "--warmup", "2", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
                          timeout=240)
     assert res.returncode == 0, res.stderr[-3000:]
     line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
@@ -734,11 +734,40 @@ def test_bench_line_names_its_gpu():
     import sys
     from conftest import ROOT
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
-                          "--no-cpu-baseline", "--no-check"], capture_output=True, text=True, timeout=240)
+                          "--full", "--no-cpu-baseline", "--no-check"], capture_output=True, text=True, timeout=240)
     assert res.returncode == 0, res.stderr[-3000:]
     line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
     assert len(line["ranks"]) == 1 and line["ranks"][0]["rank"] == 0 and line["ranks_share_a_gpu"] is None
     assert line["frame_modes"]["device"]["rccl_world"] == 1
+
+
+def test_bench_plain_run_dumps_its_frame(R, tmp_path):
+    """A plain run (no --full): the line has the headline fields and nothing
+    measured after the timed steps, --steps is the number of timed steps, and
+    --dump-outputs writes the frame the timed path left in host memory — the
+    K2 render, bit for bit."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3",
+                          "--warmup", "1", "--dump-outputs", str(tmp_path / "out")],
+                         capture_output=True, text=True, timeout=240)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, res.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["full"] is False
+    assert line["unit"] == "Mpath-samples/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f32+f64" and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(512 * 512 * 64 / (line["ms_per_step"] * 1e-3) / 1e6, rel=1e-3)
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["linf_vs_cpu_ref"] is None
+    assert "skipped" in line["frame_modes"]["device"]
+    assert line["frame_modes"]["host"]["legs_ms"]["band_kernel_max"] > 0
+    assert os.listdir(tmp_path / "out") == ["frame.npy"]
+    fb = np.load(tmp_path / "out" / "frame.npy")
+    assert fb.dtype == np.float32 and line["dumped_outputs"]["frame"]["shape"] == [512, 512, 3]
+    assert np.array_equal(fb, R.render(512, 512, 64, 4, 9))
 
 
 @pytest.mark.parametrize("inject", ["raise:1", "hang:1"])
@@ -754,7 +783,7 @@ def test_bench_headline_survives_a_failing_secondary_leg(inject):
     env = dict(os.environ, PT_BENCH_REHEARSE="1", PT_BENCH_INJECT_DEVICE_LEG=inject,
                PT_BENCH_LEG_TIMEOUT_S="10")
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4",
-                          "--warmup", "1", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
+                          "--warmup", "1", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
                          timeout=240)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
