@@ -6,7 +6,11 @@ tracks the float64 reference to rounding; the default f32 framebuffer is
 checked at <= 1e-6 (f32 output rounding).  BASELINE.json's bar is 1e-4.
 At the full bench sizes the oracle checks pixel subsets, and size-independent
 properties (hybrid == forced-f64 bitwise, band/sample-split consistency,
-determinism) cover the whole image."""
+determinism) cover the whole image.  The filter's device path at its
+thresholds (rays within 1e-9 .. 1e-3 of an edge, of |n.d| = 1e-5, of sqd = 1e-5
+and of the shadow range, which a random frame almost never holds) is run by
+the grazing scenes of tests/grazing.py in tests/test_gpu_grazing.py, which
+fail when the shadow fold loses its del or qhi term."""
 import os
 
 import numpy as np
