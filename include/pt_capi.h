@@ -204,6 +204,80 @@ int pt_render_multi(pt_scene* const* scenes, int32_t n, const pt_render_params* 
 /* Kernel time (ms) of the last pt_render_device launch on this handle. */
 int pt_last_kernel_ms(pt_scene* scene, float* ms);
 
+/* Adaptive sampling to a noise target (v7, additive; build extension — the
+ * reference spends -r samples on every pixel, main.py:186-271).  A pt_accum is
+ * a device-resident accumulator of one (width, height) frame of `scene`.  Per
+ * pixel e = (height-1-iy)*width + ix (image orientation) it holds
+ *     S[e][3]  f64  sum of the pixel's sample colours,
+ *     Q[e][3]  f64  per-channel sum of their squares (one sample colour is
+ *                   what the reference adds to pixel_color_list per
+ *                   rays_counter, main.py:269-271: a whole path),
+ *     n[e]     u32  samples taken — always the sample indices 0..n-1,
+ *     err[e]   f64  the error estimate of the last pt_accum_select,
+ * and the active list of that select: u32 values of e, ascending, unique.
+ * Error estimate (f64 throughout, in this order), for n >= 2 and channel c:
+ *     m_c = S_c / n
+ *     v_c = max(0, Q_c - S_c*S_c / n) / (n - 1)
+ *     err = sqrt((v_r + v_g + v_b) / n) / (|m_r| + |m_g| + |m_b| + floor)
+ * and err = +inf for n < 2.  A pixel is active iff
+ *     n < min_spp || (err > tol && n < max_spp),
+ * and a render pass adds k = min(step_spp, (n < min_spp ? min_spp : max_spp) - n)
+ * samples, the indices n .. n+k-1, to each listed pixel.  The keyed RNG makes
+ * sample s of a pixel the same draw whichever pass renders it, so a pixel that
+ * stopped at n samples holds what a uniform render of n samples gives it
+ * (to the sum order: ~1e-15 relative).  tol = 0 takes every pixel of non-zero
+ * variance to max_spp; min_spp == max_spp is a uniform render that also
+ * yields Q.  Requires 2 <= min_spp <= max_spp, step_spp >= 1, tol >= 0,
+ * floor > 0 (PT_EINVAL otherwise).                                         */
+typedef struct pt_adapt_params {
+    double tol;              /* stop at err <= tol                            */
+    double floor;            /* added to the mean's magnitude (dark pixels)   */
+    int32_t min_spp;         /* every pixel gets at least this many samples   */
+    int32_t max_spp;         /* the per-pixel budget                          */
+    int32_t step_spp;        /* samples a pass adds per listed pixel          */
+    int32_t reserved;        /* 0 */
+} pt_adapt_params;
+
+typedef struct pt_accum pt_accum;
+
+/* An empty accumulator (n = 0 everywhere) on the scene's device.  It uses the
+ * scene handle's launch ordering and shares its rule: one call at a time per
+ * scene handle, accumulator calls included; launches are ordered after the
+ * handle's previous launch whatever stream either was issued on.  Destroy it
+ * before the scene. */
+int pt_accum_create(pt_scene* scene, int32_t width, int32_t height, pt_accum** out);
+void pt_accum_destroy(pt_accum* acc);
+/* n = 0, S = Q = 0, err = +inf, empty list.  Asynchronous on `stream`. */
+int pt_accum_reset(pt_accum* acc, void* stream);
+/* err of every pixel and the active list (an ordered stream compaction: a
+ * count per block, a scan, a scatter).  The list's length stays in device
+ * memory; this call reads it back — the only host synchronisation of a pass —
+ * into *n_active, with the samples the pass will add in *pass_samples
+ * (either may be NULL). */
+int pt_accum_select(pt_accum* acc, const pt_adapt_params* a, void* stream,
+                    uint32_t* n_active, uint64_t* pass_samples);
+/* One pass over the active list of the last pt_accum_select made with the
+ * same `a` (when there is none since the last change of the accumulator, the
+ * select runs first): k more samples for each listed pixel.  p describes the
+ * whole frame: width and height the accumulator's, spp = a->max_spp,
+ * row_begin 0, row_end height, row_step 1, row_phase 0, sample_begin 0,
+ * out_row_stride 0, lanes_per_pixel 0, flags within PT_FLAG_RR |
+ * PT_FLAG_FORCE_F64; anything else is PT_EINVAL.  Scenes with a BVH run
+ * through the same single kernel.  Asynchronous on `stream` (after the
+ * select's read); pt_last_kernel_ms() gives the pass's kernel time. */
+int pt_accum_render(pt_accum* acc, const pt_render_params* p, const pt_adapt_params* a,
+                    void* stream);
+/* S / n (0 where n = 0) into a framebuffer of pt_render_device's layout for
+ * the whole frame: height*width*3 float32, or float64 with PT_FLAG_OUT_F64 in
+ * flags (no other flag).  Asynchronous on `stream`. */
+int pt_accum_resolve_device(pt_accum* acc, uint32_t flags, void* out_rgb_dev, void* stream);
+/* Synchronous copy-out after the handle's last launch; NULL pointers are
+ * skipped.  S, Q: [height*width][3] f64; n: [height*width] u32; err:
+ * [height*width] f64; list: up to list_cap entries of the last select's list,
+ * *list_len its length (list needs list_len). */
+int pt_accum_read(pt_accum* acc, double* S, double* Q, uint32_t* n, double* err,
+                  uint32_t* list, uint32_t list_cap, uint32_t* list_len);
+
 /* Batched replacement of intersect_objects (main.py:83-122).
  * rays: [n][6] f64 (origin, direction — direction need not be normalised).
  * out_tri [n]: closest triangle index or -1 (None); out_p [n][3]: hit point.

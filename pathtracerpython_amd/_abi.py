@@ -47,6 +47,19 @@ class PtRenderParams(C.Structure):
     ]
 
 
+class PtAdaptParams(C.Structure):
+    """pt_adapt_params (include/pt_capi.h): the stop rule of an adaptive run."""
+    _fields_ = [("tol", C.c_double), ("floor", C.c_double), ("min_spp", C.c_int32),
+                ("max_spp", C.c_int32), ("step_spp", C.c_int32), ("reserved", C.c_int32)]
+
+
+def make_adapt(tol, max_spp, min_spp=8, step_spp=8, floor=0.01):
+    a = PtAdaptParams()
+    a.tol, a.floor = float(tol), float(floor)
+    a.min_spp, a.max_spp, a.step_spp = int(min_spp), int(max_spp), int(step_spp)
+    return a
+
+
 class PtMesh(C.Structure):
     """pt_mesh (include/pt_capi.h): a mesh read by pt_obj_load."""
     _fields_ = [("n_vert", C.c_int64), ("n_tri", C.c_int64), ("n_skip", C.c_int64),

@@ -7,7 +7,7 @@ raise `NativeError` — loudly, never silently.
 import ctypes as C
 import os
 
-from ._abi import PtMesh, PtRenderParams, PtSceneDesc, PtStats  # noqa: F401 (PtMesh re-exported)
+from ._abi import PtAdaptParams, PtMesh, PtRenderParams, PtSceneDesc, PtStats  # noqa: F401 (PtMesh re-exported)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PT_HIP_LIB", os.path.join(HERE, "_lib", "libpt_hip.so"))
@@ -50,6 +50,16 @@ def _bind(lib):
         "pt_wait_flags": ([vp, C.c_int32, C.c_int32, C.c_uint64, C.c_double], C.c_int),
         "pt_obj_load": ([C.c_char_p, C.POINTER(C.POINTER(PtMesh))], C.c_int),
         "pt_mesh_free": ([C.POINTER(PtMesh)], None),
+        # adaptive sampling (v7, additive)
+        "pt_accum_create": ([vp, C.c_int32, C.c_int32, C.POINTER(vp)], C.c_int),
+        "pt_accum_destroy": ([vp], None),
+        "pt_accum_reset": ([vp, vp], C.c_int),
+        "pt_accum_select": ([vp, C.POINTER(PtAdaptParams), vp, C.POINTER(C.c_uint32),
+                             C.POINTER(C.c_uint64)], C.c_int),
+        "pt_accum_render": ([vp, C.POINTER(PtRenderParams), C.POINTER(PtAdaptParams), vp], C.c_int),
+        "pt_accum_resolve_device": ([vp, C.c_uint32, vp, vp], C.c_int),
+        "pt_accum_read": ([vp, dp, dp, C.POINTER(C.c_uint32), dp, C.POINTER(C.c_uint32), C.c_uint32,
+                           C.POINTER(C.c_uint32)], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -63,7 +73,9 @@ EXPORTS = ("pt_api_version", "pt_last_error", "pt_build_id", "pt_test_fault_inje
            "pt_scene_create_on", "pt_render_multi", "pt_scene_destroy", "pt_band_rows",
            "pt_render_device", "pt_render", "pt_last_kernel_ms", "pt_intersect_objects", "pt_compute_color",
            "pt_image_u8_device", "pt_image_u8", "pt_assemble_bands_device", "pt_host_map",
-           "pt_host_unmap", "pt_signal", "pt_wait_flags", "pt_obj_load", "pt_mesh_free")
+           "pt_host_unmap", "pt_signal", "pt_wait_flags", "pt_obj_load", "pt_mesh_free",
+           "pt_accum_create", "pt_accum_destroy", "pt_accum_reset", "pt_accum_select",
+           "pt_accum_render", "pt_accum_resolve_device", "pt_accum_read")
 
 
 def lib():

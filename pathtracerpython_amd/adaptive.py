@@ -1,0 +1,188 @@
+"""Adaptive sampling: render until every pixel's noise estimate is below a
+target, within a per-pixel sample budget (build extension).
+
+The reference spends `-r` samples on every pixel (main.py:186-271).  Here a
+device-resident accumulator (`pt_accum`, include/pt_capi.h) keeps, per pixel,
+the sum S of its sample colours, the per-channel sum of their squares Q and
+the sample count n.  A run is a loop of passes: a select evaluates
+
+    m_c = S_c / n
+    v_c = max(0, Q_c - S_c*S_c / n) / (n - 1)
+    err = sqrt((v_r + v_g + v_b) / n) / (|m_r| + |m_g| + |m_b| + floor)
+
+(err = +inf below two samples), lists the pixels with
+n < min_spp or (err > tol and n < max_spp), and a render pass adds
+k = min(step_spp, (min_spp if n < min_spp else max_spp) - n) samples — the
+sample indices n .. n+k-1 — to each listed pixel.  The run ends when the list
+is empty.  The keyed RNG makes sample s of a pixel the same draw whichever
+pass renders it, so a pixel that stopped at n samples holds what a uniform
+render of n samples gives it (to ~1e-15 relative: the sum order).  The
+list's length is the one value the host reads per pass.
+"""
+import ctypes as C
+import weakref
+
+import numpy as np
+
+from . import _native
+from ._abi import PT_FLAG_FORCE_F64, PT_FLAG_OUT_F64, PT_FLAG_RR, make_adapt, make_params
+
+
+class AdaptiveResult:
+    """fb (H, W, 3) f64 mean colours; counts (H, W) u32 samples per pixel;
+    err (H, W) f64 the last error estimates; passes [(n_active,
+    samples_added)]; samples the total."""
+
+    def __init__(self, fb, counts, err, passes):
+        self.fb, self.counts, self.err = fb, counts, err
+        self.passes = list(passes)
+        self.samples = int(sum(s for _, s in self.passes))
+
+    def __repr__(self):
+        H, W = self.counts.shape
+        return (f"AdaptiveResult({W}x{H}, {len(self.passes)} passes, {self.samples} samples, "
+                f"{self.samples / max(1, W * H):.2f} spp mean)")
+
+
+def check_rule(tol, max_spp, min_spp=8, step_spp=8, floor=0.01):
+    """The argument checks of pt_adapt_params, before any device work."""
+    if not (isinstance(min_spp, (int, np.integer)) and isinstance(max_spp, (int, np.integer))
+            and isinstance(step_spp, (int, np.integer))):
+        raise ValueError("min_spp, max_spp and step_spp must be integers")
+    if not 2 <= min_spp <= max_spp:
+        raise ValueError("need 2 <= min_spp <= max_spp")
+    if step_spp < 1:
+        raise ValueError("step_spp must be >= 1")
+    if not tol >= 0:
+        raise ValueError("tol must be >= 0")
+    if not floor > 0:
+        raise ValueError("floor must be > 0")
+
+
+def pass_samples(n, min_spp, max_spp, step_spp):
+    """k of the rule above for a pixel with n samples (0: at its goal)."""
+    goal = min_spp if n < min_spp else max_spp
+    return max(0, min(step_spp, goal - n))
+
+
+class Accumulator:
+    """A `pt_accum` of one (width, height) frame of a Renderer's scene."""
+
+    def __init__(self, renderer, width, height):
+        self._lib = renderer._lib
+        self.renderer = renderer
+        self.width, self.height = int(width), int(height)
+        h = C.c_void_p()
+        _native.check(self._lib.pt_accum_create(renderer._h, self.width, self.height, C.byref(h)),
+                      "pt_accum_create")
+        self._h = h
+        # the accumulator must go before its scene: Renderer.close() closes
+        # the accumulators still open on it first
+        if not hasattr(renderer, "_accums"):
+            renderer._accums = weakref.WeakSet()
+        renderer._accums.add(self)
+
+    def reset(self, stream=None):
+        _native.check(self._lib.pt_accum_reset(self._h, C.c_void_p(stream or 0)), "pt_accum_reset")
+
+    def select(self, adapt, stream=None):
+        """(n_active, samples the pass will add)."""
+        n, k = C.c_uint32(0), C.c_uint64(0)
+        _native.check(self._lib.pt_accum_select(self._h, C.byref(adapt), C.c_void_p(stream or 0),
+                                                C.byref(n), C.byref(k)), "pt_accum_select")
+        return n.value, k.value
+
+    def render(self, params, adapt, stream=None):
+        _native.check(self._lib.pt_accum_render(self._h, C.byref(params), C.byref(adapt),
+                                                C.c_void_p(stream or 0)), "pt_accum_render")
+
+    def resolve_device(self, out_ptr, f64=True, stream=None):
+        _native.check(self._lib.pt_accum_resolve_device(self._h, PT_FLAG_OUT_F64 if f64 else 0,
+                                                        C.c_void_p(out_ptr), C.c_void_p(stream or 0)),
+                      "pt_accum_resolve_device")
+
+    def read(self, S=False, Q=False, n=False, err=False, active=False):
+        """The requested arrays as a dict: S, Q (H, W, 3) f64; n (H, W) u32;
+        err (H, W) f64; list (the last select's active list, u32)."""
+        H, W = self.height, self.width
+        out = {}
+        if S:
+            out["S"] = np.zeros((H, W, 3), dtype=np.float64)
+        if Q:
+            out["Q"] = np.zeros((H, W, 3), dtype=np.float64)
+        if n:
+            out["n"] = np.zeros((H, W), dtype=np.uint32)
+        if err:
+            out["err"] = np.zeros((H, W), dtype=np.float64)
+        lst = np.zeros(H * W, dtype=np.uint32) if active else None
+        ln = C.c_uint32(0)
+
+        def ptr(k, t):
+            return out[k].ctypes.data_as(C.POINTER(t)) if k in out else None
+        _native.check(self._lib.pt_accum_read(
+            self._h, ptr("S", C.c_double), ptr("Q", C.c_double), ptr("n", C.c_uint32),
+            ptr("err", C.c_double),
+            lst.ctypes.data_as(C.POINTER(C.c_uint32)) if active else None,
+            H * W if active else 0, C.byref(ln) if active else None), "pt_accum_read")
+        if active:
+            out["list"] = lst[:ln.value].copy()
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.pt_accum_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def run_passes(acc, params, adapt, on_pass=None, max_passes=None):
+    """The pass loop on an accumulator (anything with select / render): select,
+    stop on an empty list, render.  Returns [(n_active, samples_added)]."""
+    passes = []
+    # every pass adds at least one sample to each listed pixel, so a run has at
+    # most max_spp passes (+1 for the closing select): a longer one is a bug
+    limit = int(adapt.max_spp) + 1 if max_passes is None else int(max_passes)
+    while True:
+        n_active, k = acc.select(adapt)
+        if n_active == 0:
+            return passes
+        if len(passes) >= limit:
+            raise RuntimeError(f"adaptive run did not end within {limit} passes")
+        acc.render(params, adapt)
+        passes.append((int(n_active), int(k)))
+        if on_pass is not None:
+            on_pass(len(passes), int(n_active), int(k))
+
+
+def render_adaptive(renderer, width=None, height=None, max_spp=64, bounces=1, seed=None, rr=False,
+                    rr_depth=3, tol=0.05, min_spp=8, step_spp=8, floor=0.01, force_f64=False,
+                    on_pass=None):
+    """Render until err <= tol everywhere or a pixel has max_spp samples.
+
+    renderer: a render.Renderer.  on_pass(i, n_active, samples_added) after
+    each pass.  Returns an AdaptiveResult."""
+    check_rule(tol, max_spp, min_spp, step_spp, floor)
+    width = int(renderer.scene.width if width is None else width)
+    height = int(renderer.scene.height if height is None else height)
+    seed = renderer.scene.seed if seed is None else seed
+    seed = 0 if seed is None else int(seed)
+    flags = (PT_FLAG_RR if rr else 0) | (PT_FLAG_FORCE_F64 if force_f64 else 0)
+    params = make_params(width, height, max_spp, bounces, seed, flags, rr_depth)
+    adapt = make_adapt(tol, max_spp, min_spp, step_spp, floor)
+    with Accumulator(renderer, width, height) as acc:
+        passes = run_passes(acc, params, adapt, on_pass)
+        d = acc.read(S=True, n=True, err=True)
+    n = d["n"]
+    fb = np.where(n[..., None] > 0, d["S"] / np.maximum(n, 1)[..., None], 0.0)
+    return AdaptiveResult(fb, n, d["err"], passes)

@@ -416,6 +416,211 @@ __global__ __launch_bounds__(256) void k_wf_final(SceneK S, RenderK R, const WfP
     store_pixel(R, j, acc, out, R.split);
 }
 
+// ------------------------------------ adaptive sampling (pt_accum) --
+// Per-pixel moments S, Q and counts n on the device (include/pt_capi.h,
+// pt_accum; the rule and the lane code: pt_path.h MomentSched, moment_err).
+// A pass renders a LIST of pixels: k_accum_select_* build it (err, the active
+// predicate, an ordered compaction), k_render_list adds k samples to each
+// listed pixel, k_accum_resolve writes S / n as a framebuffer.
+struct ListK {
+    int32_t W, H, bounces, rr_depth;   // rr_depth -1: off
+    uint64_t seed;
+    uint32_t split, split_log2;
+    uint32_t n_list, npix;
+    uint64_t lanes;   // work-items of the launch (a multiple of 64): the moment home's stride
+    AdaptK A;
+};
+// The lane's home of S and Q across the bounce loop: 0 the lane's registers
+// (MomentRegs), 1 a device buffer [6][lanes], touched only when a path ends
+// (MomentMem).  Both stay at 128 VGPRs / 64 B scratch; the registers are 5%
+// faster on the K2 frame, the buffer stays as a tuning build.
+#ifndef PT_MOMENT_HOME
+#define PT_MOMENT_HOME 0
+#endif
+#ifndef PT_LIST_WAVES
+#define PT_LIST_WAVES PT_RENDER_WAVES
+#endif
+// A work-item is (list entry, sample slice): `split` adjacent lanes share the
+// entry's pixel e and stride the k samples its pass adds, from sample n[e] on.
+// The pixel's lanes reduce S and Q in store_pixel's xor order and lane 0 adds
+// them to the accumulator with plain loads and stores (the list is unique).
+template <bool FORCE64, bool BVH>
+__global__ __launch_bounds__(kRenderBlock, PT_LIST_WAVES) void k_render_list(
+    SceneK S, ListK R, const uint32_t* __restrict__ list, double* __restrict__ accS,
+    double* __restrict__ accQ, uint32_t* __restrict__ accN, double* __restrict__ home) {
+    __shared__ double spill[kSpillSlots][kRenderBlock];
+    const Spill sp{&spill[0][threadIdx.x], (int)kRenderBlock};
+    const uint32_t tid = blockIdx.x * kRenderBlock + threadIdx.x;
+    const uint32_t entry = tid >> R.split_log2, c = tid & (R.split - 1u);
+    // (entries that are no pixel of the frame are skipped, never dereferenced)
+    const uint32_t e = entry < R.n_list ? list[entry] : 0xffffffffu;
+    const bool valid = e < R.npix;   // the same for all lanes of an entry
+#if PT_MOMENT_HOME
+    MomentMem M{home + tid, (size_t)R.lanes};
+#else
+    MomentRegs M;
+    (void)home;
+#endif
+    uint32_t k = 0;
+    if (valid) {
+        M.clear();
+        const uint32_t n0 = accN[e];
+        k = adapt_k(n0, R.A);
+        const int32_t row = (int32_t)(e / (uint32_t)R.W);
+        const int32_t ix = (int32_t)e - row * R.W, iy = R.H - 1 - row;
+        const D3 eye = ld3(S.eye);
+        const double x = linspace_at(S.ortho[0], S.ortho[2], R.W, ix);
+        const double y = linspace_at(S.ortho[1], S.ortho[3], R.H, iy);
+        const D3 d0 = d3(x - eye.x, y - eye.y, 0.0 - eye.z);
+        LaneJob J;
+        J.seed = R.seed;
+        J.pixel = (uint32_t)ix * (uint32_t)R.H + (uint32_t)iy;
+        J.sample0 = (int32_t)(n0 + c);
+        J.sample_stride = (int32_t)R.split;
+        J.n_samples = c < k ? (int32_t)((k - c + R.split - 1u) >> R.split_log2) : 0;
+        J.bounces = R.bounces;
+        J.rr_depth = R.rr_depth;
+        Counters cnt = {};
+        D3 P0 = d3(0, 0, 0);
+        int tri0 = -1;
+        // the primary hit once per lane and pass (k, like valid, is the same
+        // in every lane of the entry: the whole group takes one branch)
+        if (PT_PRIMARY_SHARED && !FORCE64 && !BVH && R.split >= PT_PRIMARY_SHARED) {
+            if (R.bounces > 0 && k > 0) tri0 = primary_shared(S, eye, d0, c, R.split, sp, &P0);
+        } else if (J.n_samples > 0 && R.bounces > 0) {
+            tri0 = closest<FORCE64, false, BVH>(S, eye, d0, -1, sp, &P0, &cnt, true);
+        }
+        render_lane_moments<FORCE64, false, BVH>(S, J, d0, tri0, P0, sp, &cnt, M);
+    }
+    D3 s = valid ? M.sum() : d3(0, 0, 0), q = valid ? M.sumsq() : d3(0, 0, 0);
+    for (uint32_t m = 1; m < R.split; m <<= 1) {
+        s.x += __shfl_xor(s.x, (int)m); s.y += __shfl_xor(s.y, (int)m); s.z += __shfl_xor(s.z, (int)m);
+        q.x += __shfl_xor(q.x, (int)m); q.y += __shfl_xor(q.y, (int)m); q.z += __shfl_xor(q.z, (int)m);
+    }
+    if (valid && c == 0 && k > 0) {
+        double* ps = accS + (size_t)e * 3;
+        double* pq = accQ + (size_t)e * 3;
+        ps[0] += s.x; ps[1] += s.y; ps[2] += s.z;
+        pq[0] += q.x; pq[1] += q.y; pq[2] += q.z;
+        accN[e] += k;
+    }
+}
+
+// What a select leaves in device memory for the host's one read per pass:
+// the list's length, ~(the smallest k of a listed pixel) (0: empty list) and
+// the samples the pass will add.
+struct AccumMeta {
+    uint32_t count, nkmin;
+    unsigned long long ksum;
+};
+constexpr uint32_t kSelBlock = 256;
+__device__ __forceinline__ uint32_t sel_pixel(uint32_t npix, bool* in) {
+    const uint64_t e = (uint64_t)blockIdx.x * kSelBlock + threadIdx.x;
+    *in = e < (uint64_t)npix;
+    return (uint32_t)e;
+}
+// 1. err of every pixel, the active pixels of each block counted
+__global__ __launch_bounds__(kSelBlock) void k_accum_select_count(
+    const double* __restrict__ accS, const double* __restrict__ accQ, const uint32_t* __restrict__ accN,
+    uint32_t npix, AdaptK A, double* __restrict__ err, uint32_t* __restrict__ bcount,
+    AccumMeta* __restrict__ meta) {
+    __shared__ uint32_t wc[kSelBlock / 64];
+    bool in;
+    const uint32_t e = sel_pixel(npix, &in);
+    bool act = false;
+    uint32_t k = 0;
+    if (in) {
+        const uint32_t n = accN[e];
+        const double er = moment_err(accS + (size_t)e * 3, accQ + (size_t)e * 3, n, A.floor);
+        err[e] = er;
+        act = adapt_active(n, er, A);
+        k = act ? adapt_k(n, A) : 0u;
+    }
+    const unsigned long long b = __ballot(act);
+    uint32_t ks = k, nk = act ? ~k : 0u;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        ks += __shfl_xor(ks, m);
+        nk = max(nk, (uint32_t)__shfl_xor(nk, m));
+    }
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    if (lane == 0) {
+        wc[w] = (uint32_t)__popcll(b);
+        if (b) {
+            atomicAdd(&meta->ksum, (unsigned long long)ks);
+            atomicMax(&meta->nkmin, nk);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+        for (uint32_t i = 0; i < kSelBlock / 64; ++i) t += wc[i];
+        bcount[blockIdx.x] = t;
+    }
+}
+// 2. one block of 1024: the block counts become their exclusive prefix sums,
+// the total is the list's length
+__global__ __launch_bounds__(1024) void k_accum_select_scan(uint32_t* __restrict__ bcount, uint32_t nb,
+                                                            AccumMeta* __restrict__ meta) {
+    __shared__ uint32_t wsum[16];
+    const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < nb; base += 1024u) {   // (block-uniform trip count)
+        const uint32_t i = base + t;
+        const uint32_t v = i < nb ? bcount[i] : 0u;
+        const uint32_t incl = wave_incl_scan(v);
+        if (lane == 63) wsum[w] = incl;
+        __syncthreads();
+        uint32_t x = carry + incl - v, total = 0;
+        for (uint32_t j = 0; j < 16; ++j) {
+            if (j < w) x += wsum[j];
+            total += wsum[j];
+        }
+        if (i < nb) bcount[i] = x;
+        carry += total;
+        __syncthreads();
+    }
+    if (t == 0) meta->count = carry;
+}
+// 3. the active pixels of each block, in order, from the block's offset on
+__global__ __launch_bounds__(kSelBlock) void k_accum_select_scatter(
+    const double* __restrict__ err, const uint32_t* __restrict__ accN, uint32_t npix, AdaptK A,
+    const uint32_t* __restrict__ boff, uint32_t* __restrict__ list) {
+    __shared__ uint32_t wc[kSelBlock / 64];
+    bool in;
+    const uint32_t e = sel_pixel(npix, &in);
+    const bool act = in && adapt_active(accN[e], err[e], A);
+    const unsigned long long b = __ballot(act);
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    if (lane == 0) wc[w] = (uint32_t)__popcll(b);
+    __syncthreads();
+    uint32_t off = boff[blockIdx.x] + (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+    for (uint32_t i = 0; i < w; ++i) off += wc[i];
+    if (act) list[off] = e;   // off < the list's length <= npix
+}
+__global__ __launch_bounds__(256) void k_accum_reset(double* __restrict__ err, uint32_t npix) {
+    const uint64_t e = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (e < (uint64_t)npix) err[e] = (double)INFINITY;
+}
+// S / n (0 where n = 0) as a framebuffer of k_render's layout (the whole frame)
+__global__ __launch_bounds__(256) void k_accum_resolve(const double* __restrict__ accS,
+                                                       const uint32_t* __restrict__ accN, uint32_t npix,
+                                                       int32_t out_f64, void* __restrict__ out) {
+    const uint64_t e = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (e >= (uint64_t)npix) return;
+    const uint32_t n = accN[e];
+    const double dn = (double)n;
+    const double* s = accS + e * 3;
+    const double r = n ? s[0] / dn : 0.0, g = n ? s[1] / dn : 0.0, b = n ? s[2] / dn : 0.0;
+    if (out_f64) {
+        double* o = (double*)out + e * 3;
+        o[0] = r; o[1] = g; o[2] = b;
+    } else {
+        float* o = (float*)out + e * 3;
+        o[0] = (float)r; o[1] = (float)g; o[2] = (float)b;
+    }
+}
+
 // the origins the filter's bounds cover: within the surface frame's box
 // (xs), within the box with the eye (xa); outside both -> forced f64
 __device__ __forceinline__ bool in_box(F3 o, float x) {
@@ -1165,6 +1370,259 @@ int pt_render(pt_scene* s, const pt_render_params* p, void* out_host, pt_stats* 
         HIPCHK(hipMemcpy2DAsync(out_host, (size_t)p->out_row_stride * elem, s->out_dev, row_bytes,
                                 row_bytes, (size_t)rows, hipMemcpyDeviceToHost, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
+    return PT_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------ pt_accum (adaptive) --
+struct pt_accum {
+    pt_scene* scene = nullptr;
+    int32_t W = 0, H = 0;
+    uint32_t npix = 0, nblocks = 0;   // nblocks: k_accum_select_*'s grid
+    double *S = nullptr, *Q = nullptr, *err = nullptr;
+    uint32_t *n = nullptr, *list = nullptr, *bcount = nullptr;
+    AccumMeta* meta = nullptr;
+    double* home = nullptr;           // k_render_list's moment home, grown on demand
+    uint64_t home_lanes = 0;
+    hipStream_t stream = nullptr;     // the synchronous reads
+    // the last select's result, while the accumulator is unchanged since
+    bool list_valid = false;
+    AccumMeta list_meta{};
+    pt_adapt_params list_params{};
+};
+
+static int check_adapt(const pt_adapt_params* a, AdaptK* A) {
+    if (!a) return fail(PT_EINVAL, "null adapt params");
+    if (a->min_spp < 2 || a->max_spp < a->min_spp) return fail(PT_EINVAL, "need 2 <= min_spp <= max_spp");
+    if (a->step_spp < 1) return fail(PT_EINVAL, "step_spp must be >= 1");
+    if (!(a->tol >= 0.0)) return fail(PT_EINVAL, "tol must be >= 0");
+    if (!(a->floor > 0.0)) return fail(PT_EINVAL, "floor must be > 0");
+    A->tol = a->tol; A->floor = a->floor;
+    A->min_spp = (uint32_t)a->min_spp; A->max_spp = (uint32_t)a->max_spp;
+    A->step_spp = (uint32_t)a->step_spp;
+    return PT_OK;
+}
+static bool same_adapt(const pt_adapt_params& x, const pt_adapt_params& y) {
+    return x.tol == y.tol && x.floor == y.floor && x.min_spp == y.min_spp && x.max_spp == y.max_spp &&
+           x.step_spp == y.step_spp;
+}
+// accumulator launches are ordered on the scene handle as pt_render_device's
+static int accum_begin(pt_accum* a, hipStream_t st) {
+    pt_scene* s = a->scene;
+    if (s->timed) HIPCHK(hipStreamWaitEvent(st, s->ev1, 0));
+    HIPCHK(hipEventRecord(s->ev0, st));
+    return PT_OK;
+}
+static int accum_end(pt_accum* a, hipStream_t st) {
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(a->scene->ev1, st));
+    a->scene->timed = true;
+    return PT_OK;
+}
+
+extern "C" {
+
+void pt_accum_destroy(pt_accum* a) {
+    if (!a) return;
+    {
+        DeviceGuard g(a->scene->device);
+        if (a->stream) (void)hipStreamSynchronize(a->stream);
+        void* bufs[] = {a->S, a->Q, a->err, a->n, a->list, a->bcount, a->meta, a->home};
+        for (void* b : bufs)
+            if (b) (void)hipFree(b);
+        if (a->stream) (void)hipStreamDestroy(a->stream);
+    }
+    delete a;
+}
+
+int pt_accum_reset(pt_accum* a, void* stream) {
+    if (!a) return fail(PT_EINVAL, "null accumulator");
+    DeviceGuard g(a->scene->device);
+    hipStream_t st = (hipStream_t)stream;
+    int rc = accum_begin(a, st);
+    if (rc) return rc;
+    a->list_valid = false;
+    a->list_meta = AccumMeta{};
+    HIPCHK(hipMemsetAsync(a->S, 0, (size_t)a->npix * 3 * sizeof(double), st));
+    HIPCHK(hipMemsetAsync(a->Q, 0, (size_t)a->npix * 3 * sizeof(double), st));
+    HIPCHK(hipMemsetAsync(a->n, 0, (size_t)a->npix * sizeof(uint32_t), st));
+    HIPCHK(hipMemsetAsync(a->meta, 0, sizeof(AccumMeta), st));
+    hipLaunchKernelGGL(k_accum_reset, dim3((a->npix + 255u) / 256u), dim3(256), 0, st, a->err, a->npix);
+    return accum_end(a, st);
+}
+
+int pt_accum_create(pt_scene* s, int32_t width, int32_t height, pt_accum** out) {
+    if (!out) return fail(PT_EINVAL, "null output handle");
+    *out = nullptr;
+    if (!s) return fail(PT_EINVAL, "null scene");
+    if (width <= 0 || height <= 0) return fail(PT_EINVAL, "width/height must be > 0");
+    if ((int64_t)width * height >= (int64_t)1 << 32) return fail(PT_EINVAL, "image too large for 32-bit pixel keys");
+    DeviceGuard g(s->device);
+    pt_accum* a = new pt_accum();
+    a->scene = s;
+    a->W = width; a->H = height;
+    a->npix = (uint32_t)((int64_t)width * height);
+    a->nblocks = (uint32_t)(((uint64_t)a->npix + kSelBlock - 1) / kSelBlock);
+    const size_t np = a->npix;
+    const bool ok = hipMalloc((void**)&a->S, np * 3 * sizeof(double)) == hipSuccess &&
+                    hipMalloc((void**)&a->Q, np * 3 * sizeof(double)) == hipSuccess &&
+                    hipMalloc((void**)&a->err, np * sizeof(double)) == hipSuccess &&
+                    hipMalloc((void**)&a->n, np * sizeof(uint32_t)) == hipSuccess &&
+                    hipMalloc((void**)&a->list, np * sizeof(uint32_t)) == hipSuccess &&
+                    hipMalloc((void**)&a->bcount, (size_t)a->nblocks * sizeof(uint32_t)) == hipSuccess &&
+                    hipMalloc((void**)&a->meta, sizeof(AccumMeta)) == hipSuccess;
+    if (!ok) { pt_accum_destroy(a); return fail(PT_ENOMEM, "hipMalloc accumulator"); }
+    if (hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking) != hipSuccess) {
+        pt_accum_destroy(a);
+        return fail(PT_EHIP, "stream creation");
+    }
+    int rc = pt_accum_reset(a, a->stream);
+    if (rc) { pt_accum_destroy(a); return rc; }
+    *out = a;
+    return PT_OK;
+}
+
+int pt_accum_select(pt_accum* a, const pt_adapt_params* ap, void* stream, uint32_t* n_active,
+                    uint64_t* pass_samples) {
+    if (!a) return fail(PT_EINVAL, "null accumulator");
+    AdaptK A;
+    int rc = check_adapt(ap, &A);
+    if (rc) return rc;
+    DeviceGuard g(a->scene->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (!(a->list_valid && same_adapt(a->list_params, *ap))) {
+        rc = accum_begin(a, st);
+        if (rc) return rc;
+        a->list_valid = false;
+        HIPCHK(hipMemsetAsync(a->meta, 0, sizeof(AccumMeta), st));
+        const dim3 grid(a->nblocks), block(kSelBlock);
+        hipLaunchKernelGGL(k_accum_select_count, grid, block, 0, st, a->S, a->Q, a->n, a->npix, A, a->err,
+                           a->bcount, a->meta);
+        hipLaunchKernelGGL(k_accum_select_scan, dim3(1), dim3(1024), 0, st, a->bcount, a->nblocks, a->meta);
+        hipLaunchKernelGGL(k_accum_select_scatter, grid, block, 0, st, a->err, a->n, a->npix, A, a->bcount,
+                           a->list);
+        rc = accum_end(a, st);
+        if (rc) return rc;
+        // the pass's one host synchronisation: the list's length (with the
+        // smallest k and the pass's samples, 16 bytes)
+        HIPCHK(hipMemcpyAsync(&a->list_meta, a->meta, sizeof(AccumMeta), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (a->list_meta.count > a->npix) return fail(PT_EHIP, "select: list longer than the frame");
+        a->list_params = *ap;
+        a->list_valid = true;
+    }
+    if (n_active) *n_active = a->list_meta.count;
+    if (pass_samples) *pass_samples = a->list_meta.ksum;
+    return PT_OK;
+}
+
+int pt_accum_render(pt_accum* a, const pt_render_params* p, const pt_adapt_params* ap, void* stream) {
+    int rc = validate(p);
+    if (rc) return rc;
+    if (!a) return fail(PT_EINVAL, "null accumulator");
+    AdaptK A;
+    rc = check_adapt(ap, &A);
+    if (rc) return rc;
+    if (p->width != a->W || p->height != a->H)
+        return fail(PT_EINVAL, "width/height are not the accumulator's");
+    if (p->row_begin != 0 || p->row_end != p->height || p->row_step != 1 || p->row_phase != 0 ||
+        p->sample_begin != 0 || p->out_row_stride != 0 || p->lanes_per_pixel != 0)
+        return fail(PT_EINVAL, "an accumulator pass renders the whole frame: row_begin 0, row_end height, "
+                               "row_step 1, sample_begin 0, out_row_stride 0, lanes_per_pixel 0");
+    if (p->flags & ~(uint32_t)(PT_FLAG_RR | PT_FLAG_FORCE_F64))
+        return fail(PT_EINVAL, "unsupported flag bits: an accumulator pass takes PT_FLAG_RR and PT_FLAG_FORCE_F64 only");
+    if (p->spp != ap->max_spp) return fail(PT_EINVAL, "spp must be the budget max_spp");
+    pt_scene* s = a->scene;
+    DeviceGuard g(s->device);
+    hipStream_t st = (hipStream_t)stream;
+    rc = pt_accum_select(a, ap, stream, nullptr, nullptr);
+    if (rc) return rc;
+    const AccumMeta m = a->list_meta;
+    if (m.count == 0) return PT_OK;
+    const uint32_t kmin = ~m.nkmin;
+    if (kmin == 0 || kmin > A.step_spp) return fail(PT_EHIP, "select: bad pass size");
+    const bool bvh = s->dev.n_bnode > 0;
+    ListK R;
+    R.W = a->W; R.H = a->H; R.bounces = p->bounces;
+    R.rr_depth = (p->flags & PT_FLAG_RR) ? std::max(0, p->rr_depth) : -1;
+    R.seed = p->seed;
+    // lanes per pixel: choose_split's rule for a launch of the list's pixels
+    // whose pixels take at least kmin samples
+    R.split = choose_split((uint64_t)a->npix, (uint64_t)m.count, (int32_t)std::min(kmin, 64u), bvh,
+                           min_lanes_of(s->n_cu));
+    R.split_log2 = 0;
+    while ((1u << R.split_log2) < R.split) ++R.split_log2;
+    R.n_list = m.count;
+    R.npix = a->npix;
+    R.A = A;
+    const uint64_t threads = (uint64_t)m.count << R.split_log2;
+    const uint64_t blocks = (threads + kRenderBlock - 1) / kRenderBlock;
+    R.lanes = blocks * kRenderBlock;
+    if (R.lanes >= ((uint64_t)1 << 32)) return fail(PT_EINVAL, "launch needs 2^32 or more work-items (32-bit lane index)");
+#if PT_MOMENT_HOME
+    if (R.lanes > a->home_lanes) {   // (the previous pass may still read the old one: ordered by the free)
+        if (a->home) HIPCHK(hipFree(a->home));
+        a->home = nullptr;
+        a->home_lanes = 0;
+        if (hipMalloc((void**)&a->home, (size_t)R.lanes * 6 * sizeof(double)) != hipSuccess)
+            return fail(PT_ENOMEM, "hipMalloc moment home");
+        a->home_lanes = R.lanes;
+    }
+#endif
+    rc = accum_begin(a, st);
+    if (rc) return rc;
+    a->list_valid = false;   // the pass changes n, S, Q
+    const dim3 grid((unsigned)blocks), block(kRenderBlock);
+    const bool f64 = (p->flags & PT_FLAG_FORCE_F64) != 0;
+    if (f64) {
+        hipLaunchKernelGGL((k_render_list<true, true>), grid, block, 0, st, s->dev, R, a->list, a->S, a->Q, a->n, a->home);
+    } else if (bvh) {
+        hipLaunchKernelGGL((k_render_list<false, true>), grid, block, 0, st, s->dev, R, a->list, a->S, a->Q, a->n, a->home);
+    } else {
+        hipLaunchKernelGGL((k_render_list<false, false>), grid, block, 0, st, s->dev, R, a->list, a->S, a->Q, a->n, a->home);
+    }
+    return accum_end(a, st);
+}
+
+int pt_accum_resolve_device(pt_accum* a, uint32_t flags, void* out_dev, void* stream) {
+    if (!a) return fail(PT_EINVAL, "null accumulator");
+    if (!out_dev) return fail(PT_EINVAL, "null output");
+    if (flags & ~(uint32_t)PT_FLAG_OUT_F64) return fail(PT_EINVAL, "resolve takes PT_FLAG_OUT_F64 only");
+    DeviceGuard g(a->scene->device);
+    hipStream_t st = (hipStream_t)stream;
+    int rc = accum_begin(a, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_accum_resolve, dim3((a->npix + 255u) / 256u), dim3(256), 0, st, a->S, a->n, a->npix,
+                       (flags & PT_FLAG_OUT_F64) ? 1 : 0, out_dev);
+    return accum_end(a, st);
+}
+
+int pt_accum_read(pt_accum* a, double* S, double* Q, uint32_t* n, double* err, uint32_t* list,
+                  uint32_t list_cap, uint32_t* list_len) {
+    if (!a) return fail(PT_EINVAL, "null accumulator");
+    if (list && !list_len) return fail(PT_EINVAL, "list needs list_len");
+    pt_scene* s = a->scene;
+    DeviceGuard g(s->device);
+    hipStream_t st = a->stream;
+    if (s->timed) HIPCHK(hipStreamWaitEvent(st, s->ev1, 0));
+    const size_t np = a->npix;
+    if (S) HIPCHK(hipMemcpyAsync(S, a->S, np * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (Q) HIPCHK(hipMemcpyAsync(Q, a->Q, np * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (n) HIPCHK(hipMemcpyAsync(n, a->n, np * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (err) HIPCHK(hipMemcpyAsync(err, a->err, np * sizeof(double), hipMemcpyDeviceToHost, st));
+    AccumMeta m{};
+    if (list_len) HIPCHK(hipMemcpyAsync(&m, a->meta, sizeof(m), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (list_len) {
+        if (m.count > a->npix) return fail(PT_EHIP, "read: list longer than the frame");
+        *list_len = m.count;
+        const uint32_t take = std::min(m.count, list_cap);
+        if (list && take) {
+            HIPCHK(hipMemcpyAsync(list, a->list, (size_t)take * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+        }
+    }
     return PT_OK;
 }
 

@@ -2098,4 +2098,114 @@ PT_HD D3 render_lane(const SceneK& S, const LaneJob& J, D3 d0, int tri0, D3 P0,
     return acc;
 }
 
+// ------------------------------------------------- per-pixel moments --
+// Adaptive sampling (build extension): besides the sum S of a
+// pixel's sample colours the accumulator keeps the per-channel sum of their
+// squares Q.  One sample colour is what the reference adds to
+// pixel_color_list per rays_counter (main.py:269-271): a whole path.
+//
+// The lane's moment home.  MomentRegs: six f64 in the lane's registers.
+// MomentMem: six f64 in memory, element i at base[i * stride] (the device
+// home [6][lanes]: a wave's 64 lanes touch one 512-B run per element, and
+// only when a path ends).
+struct MomentRegs {
+    D3 s, q;
+    PT_HD void clear() { s = d3(0, 0, 0); q = d3(0, 0, 0); }
+    PT_HD void add(D3 c) {
+        s = s + c;
+        q = d3(q.x + c.x * c.x, q.y + c.y * c.y, q.z + c.z * c.z);
+    }
+    PT_HD D3 sum() const { return s; }
+    PT_HD D3 sumsq() const { return q; }
+};
+struct MomentMem {
+    double* base;
+    size_t stride;
+    PT_HD void clear() {
+        for (int i = 0; i < 6; ++i) base[i * stride] = 0.0;
+    }
+    PT_HD void add(D3 c) {
+        base[0] += c.x; base[stride] += c.y; base[2 * stride] += c.z;
+        base[3 * stride] += c.x * c.x; base[4 * stride] += c.y * c.y; base[5 * stride] += c.z * c.z;
+    }
+    PT_HD D3 sum() const { return d3(base[0], base[stride], base[2 * stride]); }
+    PT_HD D3 sumsq() const { return d3(base[3 * stride], base[4 * stride], base[5 * stride]); }
+};
+
+// LaneSched's sample order plus the moments: when a path ends its colour
+// (render_loop's running acc, which then restarts at 0) goes to the home.
+template <class Home>
+struct MomentSched {
+    const LaneJob& J;
+    int tri0;
+    int si;
+    Home& home;
+    PT_HD uint32_t sample() const { return (uint32_t)(J.sample0 + si * J.sample_stride); }
+    PT_HD uint32_t pixel() const { return J.pixel; }
+    template <bool COUNT>
+    PT_HD bool advance(const SceneK& S, bool done, const Spill& sp, int* tri, D3* acc, Counters* cnt) {
+        if (!done) return true;
+        home.add(*acc);
+        *acc = d3(0, 0, 0);
+        if (++si >= J.n_samples) return false;
+        *tri = tri0;
+        sp.put3(kSpP, sp.get3(kSpP0));
+        sp.put3(kSpNd, d3(sp.get(kSpD0), sp.get(kSpD0 + 1), 0.0 - S.kd[kKdEye + 2]));
+        if (COUNT) {
+            bump<COUNT>(cnt, &Counters::closest_tests, (uint32_t)S.n_tri);
+            bump<COUNT>(cnt, &Counters::ray_bounces, 1);
+        }
+        return true;
+    }
+};
+
+// render_lane with the moments: the lane's J.n_samples sample colours are
+// added to `home` one by one (a primary ray that escapes or hits the light
+// gives constant samples; no bounces: samples of 0, main.py:192 never runs).
+template <bool FORCE64, bool COUNT, bool BVH, class Home>
+PT_HD void render_lane_moments(const SceneK& S, const LaneJob& J, D3 d0, int tri0, D3 P0,
+                               const Spill& sp, Counters* cnt, Home& home) {
+    if (J.n_samples <= 0) return;
+    if (J.bounces <= 0 || tri0 < 0 || tri0 >= S.n_obj_tri) {
+        const D3 v = (J.bounces <= 0 || tri0 < 0) ? d3(0, 0, 0) : ld3(S.kd + kKdLightRgb);
+        for (int i = 0; i < J.n_samples; ++i) home.add(v);
+        return;
+    }
+    sp.put(kSpD0, d0.x);
+    sp.put(kSpD0 + 1, d0.y);
+    sp.put3(kSpP0, P0);
+    sp.put3(kSpP, P0);
+    sp.put3(kSpNd, d0);   // incoming direction of bounce 0 (main.py:191)
+    D3 acc = d3(0, 0, 0);
+    MomentSched<Home> q{J, tri0, 0, home};
+    render_loop<FORCE64, COUNT, BVH>(S, J, tri0, sp, cnt, q, &acc);
+}
+
+// The stop rule of an adaptive run.  Every operation is f64, in this order
+// (the tests evaluate the same expressions in numpy and compare bits).
+struct AdaptK {
+    double tol, floor;
+    uint32_t min_spp, max_spp, step_spp;
+};
+// relative standard error of the pixel's mean; +inf below two samples
+PT_HD double moment_err(const double* S, const double* Q, uint32_t n, double floor) {
+    if (n < 2u) return (double)INFINITY;
+    const double dn = (double)n, d1 = (double)(n - 1u);
+    double v[3], m[3];
+    for (int c = 0; c < 3; ++c) {
+        m[c] = S[c] / dn;
+        v[c] = fmax(0.0, Q[c] - S[c] * S[c] / dn) / d1;
+    }
+    return sqrt((v[0] + v[1] + v[2]) / dn) / (fabs(m[0]) + fabs(m[1]) + fabs(m[2]) + floor);
+}
+PT_HD bool adapt_active(uint32_t n, double err, const AdaptK& A) {
+    return n < A.min_spp || (err > A.tol && n < A.max_spp);
+}
+// samples a pass adds to a listed pixel: indices n .. n + k - 1
+PT_HD uint32_t adapt_k(uint32_t n, const AdaptK& A) {
+    const uint32_t goal = n < A.min_spp ? A.min_spp : A.max_spp;
+    if (n >= goal) return 0u;
+    return A.step_spp < goal - n ? A.step_spp : goal - n;
+}
+
 }  // namespace pt

@@ -9,7 +9,9 @@ flags of this build: --seed (RNG key; default the SDL `seed`), --rr
 (Russian roulette), --size W H (override the SDL size), --devices N (N GPUs:
 one rank process per GPU, rows interleaved, one RCCL gather; launch.py),
 --chunk-spp K [--checkpoint F] (the samples in launches of K, resumable from
-F; progressive.py).  The
+F; progressive.py), --noise TOL [--min-spp N] [--step-spp K] [--save-aov P]
+(adaptive sampling to the noise target TOL with -r as the per-pixel budget;
+adaptive.py).  The
 reference's interactive 3-D viewer flags (--show-scene, --show-normals,
 --show-screen, --show-inter -> plot.py) are accepted and ignored with a
 notice: the pyqtgraph viewer is out of scope.
@@ -44,6 +46,15 @@ def setup(argv=None):
     parser.add_argument('--checkpoint', default=None,
                         help='with --chunk-spp: .npz written after every chunk; a rerun '
                              'resumes from it')
+    parser.add_argument('--noise', type=float, default=None, metavar='TOL',
+                        help='adaptive sampling: stop a pixel at this relative standard error; '
+                             '-r becomes the per-pixel sample budget (adaptive.py)')
+    parser.add_argument('--min-spp', type=int, default=8,
+                        help='with --noise: samples every pixel gets at least')
+    parser.add_argument('--step-spp', type=int, default=8,
+                        help='with --noise: samples a pass adds per active pixel')
+    parser.add_argument('--save-aov', default=None, metavar='PREFIX',
+                        help='with --noise: write PREFIX_counts.npy and PREFIX_err.npy')
     return parser.parse_args(argv)
 
 
@@ -99,6 +110,19 @@ def check_args(args):
         raise SystemExit('--checkpoint needs --chunk-spp')
     if args.chunk_spp and args.devices > 1:
         raise SystemExit('--chunk-spp runs on one device (--devices 1)')
+    if args.noise is None:
+        if args.save_aov:
+            raise SystemExit('--save-aov needs --noise')
+        return
+    if args.chunk_spp or args.checkpoint:
+        raise SystemExit('--noise does not combine with --chunk-spp / --checkpoint')
+    if args.devices > 1:
+        raise SystemExit('--noise runs on one device (--devices 1)')
+    from .adaptive import check_rule
+    try:
+        check_rule(args.noise, args.n_rays, min(args.min_spp, args.n_rays), args.step_spp)
+    except ValueError as e:
+        raise SystemExit(f'--noise: {e} (-r is max_spp)')
 
 
 def main(argv=None):
@@ -128,7 +152,21 @@ def main(argv=None):
         return finish(args, arr, fb)
     with Renderer(scene) as r:
         chunks = []
-        if args.chunk_spp:   # chunked, resumable (progressive.py)
+        if args.noise is not None:   # adaptive sampling (adaptive.py)
+            from .render import image_u8
+            res = r.render_adaptive(W, H, args.n_rays, args.n_bounces, args.seed, args.rr,
+                                    tol=args.noise, min_spp=min(args.min_spp, args.n_rays),
+                                    step_spp=args.step_spp)
+            fb = res.fb
+            arr = image_u8(fb) if W == H else None
+            uniform = W * H * args.n_rays
+            print(f'adaptive: {len(res.passes)} passes, {res.samples} samples, '
+                  f'{res.samples / uniform:.3f} of the uniform budget ({uniform})')
+            if args.save_aov:
+                np.save(args.save_aov + '_counts.npy', res.counts)
+                np.save(args.save_aov + '_err.npy', res.err)
+            chunks.append(res.samples)
+        elif args.chunk_spp:   # chunked, resumable (progressive.py)
             from .progressive import render_progressive
             from .render import image_u8
 
@@ -148,7 +186,8 @@ def main(argv=None):
             arr = None
         last = f'kernel {r.last_kernel_ms():.3f} ms' if chunks or not args.chunk_spp \
             else 'all samples from the checkpoint'
-        print(f'render: {W}x{H}, {args.n_rays} spp, {args.n_bounces} bounces, {last}')
+        spp = f'up to {args.n_rays}' if args.noise is not None else f'{args.n_rays}'
+        print(f'render: {W}x{H}, {spp} spp, {args.n_bounces} bounces, {last}')
     return finish(args, arr, fb)
 
 

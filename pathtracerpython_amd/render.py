@@ -118,6 +118,14 @@ class Renderer:
         img = img.cpu().numpy()
         return (img, fb.cpu().numpy()) if return_fb else img
 
+    def render_adaptive(self, width=None, height=None, max_spp=64, bounces=1, seed=None,
+                        rr=False, rr_depth=3, tol=0.05, **rule):
+        """Render to the noise target `tol` within max_spp samples per pixel
+        (adaptive.render_adaptive: fb, counts, err, passes, samples)."""
+        from .adaptive import render_adaptive
+        return render_adaptive(self, width, height, max_spp, bounces, seed, rr, rr_depth, tol,
+                               **rule)
+
     def last_kernel_ms(self):
         ms = C.c_float(0)
         _native.check(self._lib.pt_last_kernel_ms(self._h, C.byref(ms)), "pt_last_kernel_ms")
@@ -158,6 +166,8 @@ class Renderer:
         return out
 
     def close(self):
+        for acc in list(getattr(self, "_accums", ())):   # adaptive.Accumulator: before the scene
+            acc.close()
         if getattr(self, "_h", None):
             self._lib.pt_scene_destroy(self._h)
             self._h = None

@@ -1,0 +1,165 @@
+#!/usr/bin/env python3
+"""Measure the adaptive sampler (dev tool; prints one JSON document).
+
+    python3 scripts/bench_adaptive.py [--parts a,b] [--reps N] [--out FILE]
+
+The K2 shape: Cornell 512x512, 4 bounces, seed 9, budget 64 samples per pixel.
+  a  throughput of the list kernel: tol 0, min = max = 64 in one pass of 64 and
+     in 8 passes of 8, beside k_render (the uniform render of the same frame)
+     in interleaved rounds of one process; Mpath-samples/s from kernel time
+     (HIP events) and from wall time of the whole run, selects included
+  b  adaptive runs at tol 0.05 and 0.02 (min 8, step 8): samples, passes, wall
+     time of the whole run, RMSE against a 4096-spp uniform frame of another
+     seed, and beside it the RMSE of a uniform render of the same total sample
+     count; each also as a relative RMSE in the stop rule's normalisation
+Reads none of bench.py's artifacts.  Times are medians over --reps rounds
+after --warmup rounds, with min and max."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+W = H = 512
+BOUNCES, SEED, BUDGET = 4, 9, 64
+
+
+def stat(xs):
+    return {"median": statistics.median(xs), "min": min(xs), "max": max(xs), "n": len(xs)}
+
+
+def rel_rmse(x, ref, floor=0.01):
+    """RMS over pixels of |x - ref|_2 / (|r| + |g| + |b| + floor) of ref: the
+    error in the stop rule's own normalisation."""
+    e = np.sqrt(((x - ref) ** 2).sum(axis=-1)) / (np.abs(ref).sum(axis=-1) + floor)
+    return float(np.sqrt(np.mean(e ** 2)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parts", default="a,b")
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    from pathtracerpython_amd import _native, scene_reader
+    from pathtracerpython_amd._abi import make_adapt
+    from pathtracerpython_amd.adaptive import Accumulator, run_passes
+    from pathtracerpython_amd.render import Renderer
+    scene_reader.VERBOSE = False
+    sc = scene_reader.Scene(os.path.join(ROOT, "scenes", "cornell", "cornellroom.sdl"))
+    torch.cuda.set_device(0)
+    res = {"shape": {"width": W, "height": H, "bounces": BOUNCES, "seed": SEED, "budget": BUDGET},
+           "build_id": _native.build_id(), "device": torch.cuda.get_device_name(0),
+           "reps": args.reps, "warmup": args.warmup}
+    parts = args.parts.split(",")
+    npix = W * H
+    with Renderer(sc) as r, Accumulator(r, W, H) as acc:
+        p = r.params(W, H, BUDGET, BOUNCES, SEED)
+        fb = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
+
+        def uniform():
+            t0 = time.perf_counter()
+            r.render_device(p, fb.data_ptr(), 0)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3, r.last_kernel_ms()
+
+        def adaptive(adapt):
+            """(wall ms of reset + every select and pass, passes)"""
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            acc.reset()
+            passes = run_passes(acc, p, adapt)   # (kernel times: pass_kernel_ms, timed apart)
+            torch.cuda.synchronize()
+            wall = (time.perf_counter() - t0) * 1e3
+            return wall, passes
+
+        def pass_kernel_ms(adapt):
+            acc.reset()
+            out = []
+            while acc.select(adapt)[0]:
+                acc.render(p, adapt)
+                out.append(r.last_kernel_ms())
+            return out
+
+        if "a" in parts:
+            one = make_adapt(0.0, BUDGET, BUDGET, BUDGET)
+            eight = make_adapt(0.0, BUDGET, BUDGET, 8)
+            rows = {"k_render": [], "list_1x64": [], "list_8x8": []}
+            kern = {"k_render": [], "list_1x64": [], "list_8x8": []}
+            for i in range(args.warmup + args.reps):
+                w_u, k_u = uniform()
+                w_1, _ = adaptive(one)
+                k_1 = sum(pass_kernel_ms(one))
+                w_8, _ = adaptive(eight)
+                k_8 = sum(pass_kernel_ms(eight))
+                if i >= args.warmup:
+                    for name, w, k in (("k_render", w_u, k_u), ("list_1x64", w_1, k_1),
+                                       ("list_8x8", w_8, k_8)):
+                        rows[name].append(w)
+                        kern[name].append(k)
+            a = {}
+            for name in rows:
+                a[name] = {"wall_ms": stat(rows[name]), "kernel_ms": stat(kern[name]),
+                           "msamples_per_s_kernel": npix * BUDGET / statistics.median(kern[name]) / 1e3,
+                           "msamples_per_s_wall": npix * BUDGET / statistics.median(rows[name]) / 1e3}
+            for name in ("list_1x64", "list_8x8"):
+                a[name]["kernel_ratio_to_k_render"] = (a[name]["kernel_ms"]["median"] /
+                                                       a["k_render"]["kernel_ms"]["median"])
+                a[name]["wall_ratio_to_k_render"] = (a[name]["wall_ms"]["median"] /
+                                                     a["k_render"]["wall_ms"]["median"])
+            sel = []   # the three select kernels of one pass (HIP events), full frame active
+            for _ in range(args.warmup + args.reps):
+                acc.reset()
+                acc.select(one)
+                sel.append(r.last_kernel_ms())
+            a["select_kernel_ms"] = stat(sel[args.warmup:])
+            res["throughput"] = a
+        if "b" in parts:
+            # (another seed: the reference shares no sample with the frames it judges)
+            ref = r.render(W, H, spp=4096, bounces=BOUNCES, seed=SEED + 1, out_f64=True)
+            b = []
+            for tol in (0.05, 0.02):
+                adapt = make_adapt(tol, BUDGET, 8, 8, 0.01)
+                walls = []
+                for i in range(args.warmup + args.reps):
+                    w, passes = adaptive(adapt)
+                    if i >= args.warmup:
+                        walls.append(w)
+                d = acc.read(S=True, n=True)
+                mean = d["S"] / d["n"][..., None]
+                total = int(d["n"].sum())
+                spp_u = max(1, int(round(total / npix)))
+                uni = r.render(W, H, spp=spp_u, bounces=BOUNCES, seed=SEED, out_f64=True)
+                b.append({"tol": tol, "min_spp": 8, "step_spp": 8, "floor": 0.01,
+                          "samples": total, "fraction_of_uniform_budget": total / (npix * BUDGET),
+                          "passes": [list(x) for x in passes], "wall_ms": stat(walls),
+                          "pass_kernel_ms": pass_kernel_ms(adapt),
+                          "rmse_vs_4096spp": float(np.sqrt(np.mean((mean - ref) ** 2))),
+                          "rel_rmse_vs_4096spp": rel_rmse(mean, ref),
+                          "uniform_same_samples": {
+                              "spp": spp_u, "samples": spp_u * npix,
+                              "rmse_vs_4096spp": float(np.sqrt(np.mean((uni - ref) ** 2))),
+                              "rel_rmse_vs_4096spp": rel_rmse(uni, ref)},
+                          "uniform_budget_rmse_vs_4096spp": None})
+            full = r.render(W, H, spp=BUDGET, bounces=BOUNCES, seed=SEED, out_f64=True)
+            for x in b:
+                x["uniform_budget_rmse_vs_4096spp"] = float(np.sqrt(np.mean((full - ref) ** 2)))
+            res["adaptive"] = b
+    text = json.dumps(res, indent=1)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+    print(text)
+
+
+if __name__ == "__main__":
+    main()
