@@ -1,5 +1,6 @@
 """Shared helpers of the adaptive-sampling tests (tests/test_adaptive.py on the
-host, tests/test_gpu_adaptive.py on the GPU): the stop rule of
+host, tests/test_gpu_adaptive.py and tests/test_gpu_adaptive_wide.py on the
+GPU): the stop rule of
 include/pt_capi.h (pt_adapt_params) evaluated in numpy with the same f64
 operations in the same order, a simulation of a whole adaptive run on
 per-sample colours, and the oracle's per-sample frames."""
@@ -77,6 +78,27 @@ def oracle_samples(packed, width, height, bounces, seed, n_samples, flags=0, rr_
                              sample_begin=s)
         out[s] = from_list_order(c, width, height)
     return out
+
+
+def moments_upto(samples, n):
+    """S[e] = sum of samples[s][e] over s < n[e] and Q likewise with the
+    squares, for per-pixel counts n (...) <= len(samples): what an accumulator
+    holds once every pixel e has taken its first n[e] samples."""
+    samples = np.asarray(samples, dtype=np.float64)
+    n = np.asarray(n).astype(np.int64)
+    assert n.min() >= 0 and n.max() <= len(samples)
+    zero = np.zeros((1,) + samples.shape[1:])
+    idx = np.broadcast_to(n[None, ..., None], (1,) + samples.shape[1:])
+    S = np.take_along_axis(np.concatenate([zero, np.cumsum(samples, axis=0)]), idx, axis=0)[0]
+    Q = np.take_along_axis(np.concatenate([zero, np.cumsum(samples ** 2, axis=0)]), idx, axis=0)[0]
+    return S, Q
+
+
+def block_counts(active, block=256):
+    """Active pixels per select block: the counts k_accum_select_count leaves
+    for the scan (pixel e belongs to block e // block)."""
+    a = np.asarray(active).ravel().astype(np.int64)
+    return np.add.reduceat(a, np.arange(0, a.size, block))
 
 
 def histogram(n):
