@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <random>
 
 #include "../../pathtracerpython_amd/csrc/pt_path.h"
@@ -98,18 +99,67 @@ int hc_render(const pt_scene_desc* d, const pt_render_params* p, int force64,
 // leaf units; the same for the closest walks.
 // depth_hist (optional, int64[2][32]): node visits of the shadow / closest
 // walks by QNode depth (root = 0)
+// lds_entries: 0 runs the walks on per-lane local arrays (whose views never
+// leave their first part); n in 1 .. kBvhStack runs them on the split views
+// of the walk kernels (pt_hip.hip k_wf_shadow / k_wf_closest): entries below
+// n in one heap block of exactly n elements, entries n .. kBvhStack - 1 in
+// another of exactly kBvhStack - n, so an index outside either part is a heap
+// overrun (the sanitize build reports it).  The framebuffer must not depend
+// on it.  The GPU's split is n = 16 (PT_WALK_STACK_LDS).
+// peak (optional, int64[4]): the largest T.top after a node visit of the
+// shadow / closest walks, and their node visits that left T.top > 16.
+int hc_render_wavefront3(const pt_scene_desc* d, const pt_render_params* p, double* out,
+                         int32_t* steps_out, int64_t* walk_stats, int64_t* depth_hist,
+                         int32_t lds_entries, int64_t* peak);
 int hc_render_wavefront2(const pt_scene_desc* d, const pt_render_params* p, double* out,
-                         int32_t* steps_out, int64_t* walk_stats, int64_t* depth_hist);
+                         int32_t* steps_out, int64_t* walk_stats, int64_t* depth_hist) {
+    return hc_render_wavefront3(d, p, out, steps_out, walk_stats, depth_hist, 0, nullptr);
+}
 int hc_render_wavefront(const pt_scene_desc* d, const pt_render_params* p, double* out,
                         int32_t* steps_out, int64_t* walk_stats) {
     return hc_render_wavefront2(d, p, out, steps_out, walk_stats, nullptr);
 }
-int hc_render_wavefront2(const pt_scene_desc* d, const pt_render_params* p, double* out,
-                         int32_t* steps_out, int64_t* walk_stats, int64_t* depth_hist) {
+int hc_render_wavefront3(const pt_scene_desc* d, const pt_render_params* p, double* out,
+                         int32_t* steps_out, int64_t* walk_stats, int64_t* depth_hist,
+                         int32_t lds_entries, int64_t* peak) {
     int64_t ws[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t pk[4] = {0, 0, 0, 0};
+    if (lds_entries < 0 || lds_entries > kBvhStack) return -4;
+    // the split stacks' two parts (stale entries stay between walks, as in
+    // the kernels' shared and global memory)
+    const int nl = lds_entries, ng = kBvhStack - lds_entries;
+    std::unique_ptr<int[]> s_lds, s_glob, c_ref, c_gref;
+    std::unique_ptr<uint16_t[]> c_dist, c_gdist;
+    if (nl > 0) {
+        s_lds.reset(new int[nl]);
+        s_glob.reset(new int[ng]);
+        c_ref.reset(new int[nl]);
+        c_gref.reset(new int[ng]);
+        c_dist.reset(new uint16_t[nl]);
+        c_gdist.reset(new uint16_t[ng]);
+        std::fill_n(s_lds.get(), nl, kNoRef);
+        std::fill_n(s_glob.get(), ng, kNoRef);
+        std::fill_n(c_ref.get(), nl, kNoRef);
+        std::fill_n(c_gref.get(), ng, kNoRef);
+        // (distances start as +inf: an entry whose store was lost is dropped on
+        // its pop instead of passing every bound)
+        std::fill_n(c_dist.get(), nl, (uint16_t)0x7f80);
+        std::fill_n(c_gdist.get(), ng, (uint16_t)0x7f80);
+    }
+    // a walk visits a QNode or a leaf at most once and holds at most kBvhStack
+    // entries: anything else is a corrupted stack (-5 instead of a walk that
+    // never ends or leaves the tree)
     HostScene H;
     if (!prepare_scene(d, &H).empty()) return -1;
     bind_host(&H);
+    auto sane = [&](int ref, int top, int64_t work) {
+        return ref < (int)H.qnode.size() && top >= 0 && top <= kBvhStack &&
+               work <= 5 * (int64_t)H.qnode.size() + 1;
+    };
+    auto seen = [&](int kind, int top) {
+        pk[kind] = std::max<int64_t>(pk[kind], top);
+        if (top > 16) ++pk[2 + kind];
+    };
     std::vector<int> qdepth(H.qnode.size(), 0);
     if (depth_hist && H.k.qroot >= 0) {   // depth of every QNode (refs point deeper)
         std::vector<int> st{H.k.qroot};
@@ -179,11 +229,20 @@ int hc_render_wavefront2(const pt_scene_desc* d, const pt_render_params* p, doub
                 ++ws[0];
                 ShadowTrav1 T;
                 int buf[kBvhStackLocal];
-                const ShadowStack K{buf, 1};
+                const ShadowStack K = nl > 0 ? ShadowStack{s_lds.get(), 1, s_glob.get(), 1, nl}
+                                             : ShadowStack{buf, 1};
                 s1_init(T, H.k, o32, ogrp, r, H.k.qroot);
+                int64_t work = 0;
                 while (T.ref != kNoRef) {   // the walk, counted
-                    while (T.ref >= 0) { hist(0, T.ref); s1_qnode(T, K, H.k, r); ++ws[1]; }
+                    while (T.ref >= 0) {
+                        if (!sane(T.ref, T.top, ++work)) return -5;
+                        hist(0, T.ref);
+                        s1_qnode(T, K, H.k, r);
+                        ++ws[1];
+                        seen(0, T.top);
+                    }
                     if (T.ref != kNoRef) {
+                        if (!sane(-1, T.top, ++work)) return -5;
                         ++ws[2];
                         ws[3] += (~T.ref) & 7;
                         if (H.k.bunitc) s1_units<true, PT_WF_LRNG != 0>(T, H.k, &r, sp, T.ref);
@@ -197,14 +256,24 @@ int hc_render_wavefront2(const pt_scene_desc* d, const pt_render_params* p, doub
                 ClosestAcc ca = wf_get_acc(CQ[i]);
                 ClosestTrav T;
                 ClosestStackLocal L;
-                const ClosestStack K = L.view();
+                const ClosestStack K =
+                    nl > 0 ? ClosestStack{c_ref.get(), c_dist.get(), 1, c_gref.get(), c_gdist.get(), 1, nl}
+                           : L.view();
                 const WfClosestQ& q = CQ[i];
                 ctrav_init(T, H.k, F3{q.o[0], q.o[1], q.o[2]}, q.ogrp, F3{q.d[0], q.d[1], q.d[2]}, ca.b1,
                            H.k.qroot);
                 ++ws[4];
+                int64_t work = 0;
                 while (T.ref != kNoRef) {   // ctrav_step, counted
-                    while (T.ref >= 0) { hist(1, T.ref); ctrav_qnode(T, K, H.k, &ca); ++ws[5]; }
+                    while (T.ref >= 0) {
+                        if (!sane(T.ref, T.top, ++work)) return -5;
+                        hist(1, T.ref);
+                        ctrav_qnode(T, K, H.k, &ca);
+                        ++ws[5];
+                        seen(1, T.top);
+                    }
                     if (T.ref != kNoRef) {
+                        if (!sane(-1, T.top, ++work)) return -5;
                         ++ws[6];
                         ws[7] += (~T.ref) & 7;
                         if (H.k.bunitc) ctrav_leaf<false, true>(T, K, H.k, &ca, sp, nullptr);   // as k_wf_closest
@@ -223,6 +292,7 @@ int hc_render_wavefront2(const pt_scene_desc* d, const pt_render_params* p, doub
         }
     if (steps_out) *steps_out = busy;
     if (walk_stats) memcpy(walk_stats, ws, sizeof(ws));
+    if (peak) memcpy(peak, pk, sizeof(pk));
     return 0;
 }
 

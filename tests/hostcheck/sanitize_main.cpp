@@ -8,7 +8,9 @@
 //     random meshes of several sizes;
 //   * the kernel's per-lane code (pt_path.h, pt_wavefront.h) through the
 //     host-build entry points of pt_hostcheck.cpp: single-kernel and
-//     wavefront renders, the BVH reachability check and the filter self-test.
+//     wavefront renders, the BVH reachability check and the filter self-test;
+//     the wavefront walks on the walk kernels' split stacks (two exactly sized
+//     heap blocks) on a sliver mesh that fills them past the split.
 // Exit 0 = no sanitizer report (the sanitizers abort on the first one) and
 // every consistency check passed.  Usage: sanitize <scenes/cornell dir>
 #include "pt_hostcheck.cpp"
@@ -49,6 +51,31 @@ std::string random_obj(int n, uint64_t seed, double sigma) {
         const double c[3] = {ux(rng), ux(rng), uz(rng)};
         for (int v = 0; v < 3; ++v) {
             snprintf(buf, sizeof buf, "v %.17g %.17g %.17g\n", c[0] + N(rng), c[1] + N(rng), c[2] + N(rng));
+            s += buf;
+        }
+    }
+    for (int i = 0; i < n; ++i) {
+        snprintf(buf, sizeof buf, "f %d %d %d\n", 3 * i + 1, 3 * i + 2, 3 * i + 3);
+        s += buf;
+    }
+    return s;
+}
+
+// long thin triangles between two uniform points of the room, as OBJ text
+// (tests/deep_scenes.py sliver_scene: room-sized overlapping boxes, walks
+// that hold more than 16 stack entries)
+std::string sliver_obj(int n, uint64_t seed, double width) {
+    std::mt19937_64 rng(seed);
+    std::uniform_real_distribution<double> ux(-3.4, 3.4), uz(-32.0, -17.5);
+    std::normal_distribution<double> N(0.0, width);
+    std::string s = "# slivers\n";
+    char buf[128];
+    for (int i = 0; i < n; ++i) {
+        const double a[3] = {ux(rng), ux(rng), uz(rng)}, b[3] = {ux(rng), ux(rng), uz(rng)};
+        const double m[3] = {(a[0] + b[0]) / 2 + N(rng), (a[1] + b[1]) / 2 + N(rng), (a[2] + b[2]) / 2 + N(rng)};
+        const double* vs[3] = {a, b, m};
+        for (int v = 0; v < 3; ++v) {
+            snprintf(buf, sizeof buf, "v %.9f %.9f %.9f\n", vs[v][0], vs[v][1], vs[v][2]);
             s += buf;
         }
     }
@@ -214,6 +241,49 @@ int main(int argc, char** argv) {
         }
         printf("scene %d: %d tris, bnodes %d depth %d qnodes %d, %llu tests\n", si, S.d.n_tri,
                info[0], info[1], info[2], (unsigned long long)(cnt[0] + cnt[1]));
+    }
+    // 3. the walk kernels' split stacks (entries below nl in one heap block,
+    // the rest in another, each exactly sized: hc_render_wavefront3) on a
+    // sliver mesh, whose walks hold more than 16 entries: any index outside
+    // either part is a heap overrun
+    {
+        SceneBuild S;
+        int obj = 0;
+        for (int i = 0; i < 7; ++i) {
+            S.add(objs[i], obj++);
+            S.mat.insert(S.mat.end(), mats[i], mats[i] + 8);
+        }
+        const std::string t = sliver_obj(3000, 5, 1e-2);
+        MeshOut M;
+        CHECK(parse_obj_text(t.data(), t.size(), &M) == kIngestOk);
+        Obj sl;
+        sl.tri_v = M.tri_v; sl.tri_n = M.tri_n; sl.tri_area = M.tri_area;
+        S.add(sl, obj++);
+        const double m[8] = {.2, .5, .9, .3, .6, .4, 0, 3};
+        S.mat.insert(S.mat.end(), m, m + 8);
+        S.n_obj = obj;
+        const int n_obj_tri = (int)S.tri_area.size();
+        S.add(light, obj);
+        S.finish(n_obj_tri);
+        int32_t info[6] = {0, 0, 0, 0, 0, 0};
+        CHECK(hc_bvh_info(&S.d, info) == 0);
+        CHECK(info[2] > 0 && info[3] <= kBvhStack);
+        pt_render_params p{};
+        p.width = 24; p.height = 24; p.spp = 1; p.bounces = 4; p.seed = 9;
+        p.flags = 0; p.rr_depth = 2;
+        p.row_begin = 0; p.row_end = p.height; p.row_step = 1; p.row_phase = 0;
+        std::vector<double> a(p.width * p.height * 3), b(a.size());
+        int64_t pk0[4], pk[4];
+        CHECK(hc_render_wavefront3(&S.d, &p, a.data(), nullptr, nullptr, nullptr, 0, pk0) == 0);
+        printf("slivers: qstack %d, peak top %lld / %lld, visits above 16: %lld / %lld\n", info[3],
+               (long long)pk0[0], (long long)pk0[1], (long long)pk0[2], (long long)pk0[3]);
+        CHECK(pk0[0] >= 20 && pk0[1] >= 20 && pk0[2] >= 100 && pk0[3] >= 100);   // deep walks
+        const int splits[] = {16, 3, 1};
+        for (int nl : splits) {
+            CHECK(hc_render_wavefront3(&S.d, &p, b.data(), nullptr, nullptr, nullptr, nl, pk) == 0);
+            CHECK(a == b);   // split stacks == local stacks, bit for bit
+            CHECK(pk[0] == pk0[0] && pk[1] == pk0[1] && pk[2] == pk0[2] && pk[3] == pk0[3]);
+        }
     }
     printf("sanitize: OK\n");
     return 0;
