@@ -501,9 +501,6 @@ PT_HD float pt_canon(float x) {
 #ifndef PT_LIGHT_QUAD
 #define PT_LIGHT_QUAD 1
 #endif
-#ifndef PT_CADD_BF
-#define PT_CADD_BF 1
-#endif
 PT_HD void margin_unit(float cm, float nm, float M, float del, float* c, float* a) {
     *c = nan_min(cm, M - del);
     *a = fminf(fminf(nm, M + del), -*c);
@@ -521,15 +518,6 @@ PT_HD float fmax_q(float a, float b) {
     return r;
 #else
     return fmaxf(a, b);
-#endif
-}
-PT_HD float fmin_q(float a, float b) {   // fminf likewise (IEEE minNum of quiet NaNs or numbers)
-#if defined(__HIP_DEVICE_COMPILE__)
-    float r;
-    asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-#else
-    return fminf(a, b);
 #endif
 }
 // nan_min(nan_min(a, b), c) as one v_minimum3_f32 (the compiler emits each
@@ -715,11 +703,8 @@ PT_HD void fused_fallback(const SceneK& S, const UnitF& U, uint32_t amb, ShadowS
     }
 }
 
-// The next ray's closest-hit test against a uniform unit in the render
-// loop's unit form (quad_m): per-member verdicts as lane masks, the candidate
-// into ca, the ambiguous members as bits 6 / 7 of *amb.
-PT_HD void closest_unit_m(const UnitF& U, const OriginU& O, bool coplanar, F3 n32, ClosestAcc* ca,
-                          uint32_t* amb) {
+// the closest ray's plane part with its lean range
+PT_HD RayPlane closest_plane_m(const UnitF& U, const OriginU& O, F3 n32) {
     RayPlane p = ray_plane_e(U, O.h, n32, INFINITY, INFINITY, O.eh, O.eo);
 #if PT_CLOSEST_LEAN
     // the closest ray's range has no far end (hi_lo = hi_hi = inf): rcand's
@@ -731,6 +716,42 @@ PT_HD void closest_unit_m(const UnitF& U, const OriginU& O, bool coplanar, F3 n3
     p.rcand = (fabsf(p.q) > U.qhi) & (p.at - p.dt > kTzHi);
     p.rmiss = p.at + p.dt < kTzLo;
 #endif
+    return p;
+}
+// closest_add without a branch, for candidates that are never NaN (a = +inf:
+// no candidate; b is only read with a < a1, so it needs no +inf of its own).
+// With a1 <= a2 (closest_add keeps them ordered) the new second-lowest bound
+// is the median of (a, a1, a2): a1 when a < a1, a when a1 <= a <= a2, else a2
+// — one v_med3_f32 for closest_add's minimum and select.
+PT_HD float med3_q(float a, float b, float c) {   // b <= c, no NaN
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_fmed3f(a, b, c);
+#else
+    return a < b ? b : fminf(c, a);
+#endif
+}
+PT_HD void closest_add_bf(ClosestAcc* ca, int t, float a, float b) {
+    const bool lt = a < ca->a1;
+    ca->a2 = med3_q(a, ca->a1, ca->a2);
+    ca->a1 = lt ? a : ca->a1;
+    ca->b1 = lt ? b : ca->b1;
+    ca->i1 = lt ? t : ca->i1;
+}
+// The closest bits (6 / 7: the ambiguous members) of a unit, from the
+// per-member verdicts: the rare path of closest_unit_m's flag.
+PT_HD uint32_t closest_bits_m(const UnitF& U, const OriginU& O, bool coplanar, F3 n32) {
+    const RayPlane p = closest_plane_m(U, O, n32);
+    const QuadM m = quad_m(U, p, O, n32);
+    const Verdict v0 = verdict_m(m.m0, p), v1 = verdict_m(m.m1, p);
+    return ((v0.amb & !coplanar) ? 64u : 0u) | ((v1.amb & !coplanar) ? 128u : 0u);
+}
+// The next ray's closest-hit test against a uniform unit in the render
+// loop's unit form (quad_m): per-member verdicts as lane masks, the candidate
+// into ca.  Returns whether a member's verdict is ambiguous — a lane mask,
+// scalar work beside a VALU-bound loop; the bits themselves (five VALU per
+// unit to build and test) are left to the rare block (closest_bits_m).
+PT_HD bool closest_unit_m(const UnitF& U, const OriginU& O, bool coplanar, F3 n32, ClosestAcc* ca) {
+    const RayPlane p = closest_plane_m(U, O, n32);
     const QuadM m = quad_m(U, p, O, n32);
     const Verdict v0 = verdict_m(m.m0, p), v1 = verdict_m(m.m1, p);
     const bool c0 = v0.cand & !coplanar, a0 = v0.amb & !coplanar;
@@ -738,20 +759,8 @@ PT_HD void closest_unit_m(const UnitF& U, const OriginU& O, bool coplanar, F3 n3
     // both candidates of one unit cannot happen (a point certainly inside
     // one triangle is certainly outside its coplanar neighbour)
     const bool c = c0 | c1;
-#if PT_CADD_BF
-    // closest_add branch-free, the running minimum as an asm v_min_f32 (no
-    // canonicalising v_max x, x of its phi inputs; a and a2 are never NaN)
-    const float a = c ? p.at - p.dt : INFINITY, b = c ? p.at + p.dt : INFINITY;
-    const int tc = c0 ? U.t[0] : U.t[1];
-    const bool lt = a < ca->a1;
-    ca->a2 = lt ? ca->a1 : fmin_q(ca->a2, a);
-    ca->a1 = lt ? a : ca->a1;
-    ca->b1 = lt ? b : ca->b1;
-    ca->i1 = lt ? tc : ca->i1;
-#else
-    closest_add(ca, c0 ? U.t[0] : U.t[1], c ? p.at - p.dt : INFINITY, c ? p.at + p.dt : INFINITY);
-#endif
-    *amb |= (a0 ? 64u : 0u) | (a1 ? 128u : 0u);
+    closest_add_bf(ca, c0 ? U.t[0] : U.t[1], c ? p.at - p.dt : INFINITY, p.at + p.dt);
+    return a0 | a1;
 }
 
 // One plane unit against the 3 shadow rays and the next ray's closest hit,
@@ -778,6 +787,7 @@ PT_HD void fused_unit(const SceneK& S, const UnitF& U, const OriginU& O, bool co
     uint32_t amb = 0;   // bit 2k+i: shadow ray k / triangle i; bit 6+i: closest / triangle i
     const bool two = (U.count == 2);
     float amax = -1.0f;   // PT_AMB_MAX: >= 0 when some shadow test of the unit is ambiguous
+    bool camb = false;    // the unit form's closest test has an ambiguous member (closest_unit_m)
     if (MARGIN) {   // the render loop's uniform units (oc: occlusion margins)
         if (do_shadow) shadow_unit_m(S, U, O, coplanar, sh, oc, &amb, PT_QUAD ? &amax : nullptr);
     } else if (do_shadow) {   // (sh is only touched here and for shadow bits: null without shadows)
@@ -820,7 +830,7 @@ PT_HD void fused_unit(const SceneK& S, const UnitF& U, const OriginU& O, bool co
     }
     if (!FORCE64 && do_closest && (rays & 8u)) {
         if (MARGIN && PT_QUAD) {   // the render loop's unit form (quad_m)
-            closest_unit_m(U, O, coplanar, n32, ca, &amb);
+            camb = closest_unit_m(U, O, coplanar, n32, ca);
         } else {
             const RayPlane p = ray_plane(U, O.h, n32, INFINITY, INFINITY);
             bool c1 = false, a1 = false;
@@ -840,10 +850,15 @@ PT_HD void fused_unit(const SceneK& S, const UnitF& U, const OriginU& O, bool co
             amb |= (a0 ? 64u : 0u) | (a1 ? 128u : 0u);
         }
     }
-    if (PT_AMB_MAX && MARGIN && PT_QUAD && (PARTS & 1) && !(amax < 0.0f))   // rare: rebuild the bits
-        amb |= shadow_bits_m(S, U, O, coplanar, sh, oc);
-    amb &= ((PARTS & 1) ? 0x3fu : 0u) | ((PARTS & 2) ? 0xc0u : 0u);
-    if (amb) fused_fallback<FORCE64, COUNT, MARGIN, PARTS, LRNG>(S, U, amb, sh, ca, sp, cnt, oc);   // rare (FORCE64: every shadow test) — decide in f64
+    // one test per unit for "some test is ambiguous": the shadow rays' margin
+    // and the closest ray's flag; the rare block rebuilds the bits of each
+    const bool samb = PT_AMB_MAX && MARGIN && PT_QUAD && (PARTS & 1) && !(amax < 0.0f);
+    if (samb | camb | (amb != 0)) {
+        if (samb) amb |= shadow_bits_m(S, U, O, coplanar, sh, oc);
+        if (camb) amb |= closest_bits_m(U, O, coplanar, n32);
+        amb &= ((PARTS & 1) ? 0x3fu : 0u) | ((PARTS & 2) ? 0xc0u : 0u);
+        if (amb) fused_fallback<FORCE64, COUNT, MARGIN, PARTS, LRNG>(S, U, amb, sh, ca, sp, cnt, oc);   // rare (FORCE64: every shadow test) — decide in f64
+    }
 }
 
 template <bool COUNT>
@@ -2010,9 +2025,10 @@ PT_HD void render_loop(const SceneK& S, const LaneJob& J, int tri, const Spill& 
                 const UnitF U = S.unit[u];
 #if PT_LIGHT_QUAD && PT_QUAD && PT_MARGIN
                 if (!COUNT) {   // the render loop's unit form (one pair of forms for a quad)
-                    uint32_t amb = 0;
-                    closest_unit_m(U, origin_q(U, o32u), U.grp == ogrp, n32, &ca, &amb);
-                    if (amb) fused_fallback<FORCE64, COUNT, true, 2>(S, U, amb, &sh, &ca, sp, cnt, nullptr);   // rare
+                    const OriginU O = origin_q(U, o32u);
+                    if (closest_unit_m(U, O, U.grp == ogrp, n32, &ca))   // rare
+                        fused_fallback<FORCE64, COUNT, true, 2>(S, U, closest_bits_m(U, O, U.grp == ogrp, n32),
+                                                                &sh, &ca, sp, cnt, nullptr);
                     continue;
                 }
 #endif
