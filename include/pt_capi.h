@@ -262,11 +262,22 @@ int pt_accum_select(pt_accum* acc, const pt_adapt_params* a, void* stream,
  * whole frame: width and height the accumulator's, spp = a->max_spp,
  * row_begin 0, row_end height, row_step 1, row_phase 0, sample_begin 0,
  * out_row_stride 0, lanes_per_pixel 0, flags within PT_FLAG_RR |
- * PT_FLAG_FORCE_F64; anything else is PT_EINVAL.  Scenes with a BVH run
- * through the same single kernel.  Asynchronous on `stream` (after the
- * select's read); pt_last_kernel_ms() gives the pass's kernel time. */
+ * PT_FLAG_FORCE_F64 | PT_FLAG_MEGAKERNEL | PT_FLAG_WALK_COUNT |
+ * PT_FLAG_KERNEL_TIMES; anything else is PT_EINVAL.  Scenes with a BVH run
+ * the pass through the wavefront kernels (shade, sort and walk steps over the
+ * slots of the listed pixels) under pt_render_device's conditions, and
+ * through the single kernel with PT_FLAG_MEGAKERNEL or PT_FLAG_FORCE_F64;
+ * both use the same lanes per pixel, so S, Q and n are the same bit for bit.
+ * Asynchronous on `stream` (after the select's read); pt_last_kernel_ms()
+ * gives the pass's kernel time. */
 int pt_accum_render(pt_accum* acc, const pt_render_params* p, const pt_adapt_params* a,
                     void* stream);
+/* The same pass with stats (may be NULL): with PT_FLAG_WALK_COUNT /
+ * PT_FLAG_KERNEL_TIMES in p->flags a wavefront pass fills the walk counters /
+ * the per-kernel launch counts and times as pt_render_device does (and is
+ * then synchronous); a single-kernel pass leaves them 0.  (v7, additive) */
+int pt_accum_render_stats(pt_accum* acc, const pt_render_params* p, const pt_adapt_params* a,
+                          void* stream, pt_stats* stats);
 /* S / n (0 where n = 0) into a framebuffer of pt_render_device's layout for
  * the whole frame: height*width*3 float32, or float64 with PT_FLAG_OUT_F64 in
  * flags (no other flag).  Asynchronous on `stream`. */

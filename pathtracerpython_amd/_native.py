@@ -57,6 +57,8 @@ def _bind(lib):
         "pt_accum_select": ([vp, C.POINTER(PtAdaptParams), vp, C.POINTER(C.c_uint32),
                              C.POINTER(C.c_uint64)], C.c_int),
         "pt_accum_render": ([vp, C.POINTER(PtRenderParams), C.POINTER(PtAdaptParams), vp], C.c_int),
+        "pt_accum_render_stats": ([vp, C.POINTER(PtRenderParams), C.POINTER(PtAdaptParams), vp,
+                                   C.POINTER(PtStats)], C.c_int),
         "pt_accum_resolve_device": ([vp, C.c_uint32, vp, vp], C.c_int),
         "pt_accum_read": ([vp, dp, dp, C.POINTER(C.c_uint32), dp, C.POINTER(C.c_uint32), C.c_uint32,
                            C.POINTER(C.c_uint32)], C.c_int),
@@ -75,7 +77,7 @@ EXPORTS = ("pt_api_version", "pt_last_error", "pt_build_id", "pt_test_fault_inje
            "pt_image_u8_device", "pt_image_u8", "pt_assemble_bands_device", "pt_host_map",
            "pt_host_unmap", "pt_signal", "pt_wait_flags", "pt_obj_load", "pt_mesh_free",
            "pt_accum_create", "pt_accum_destroy", "pt_accum_reset", "pt_accum_select",
-           "pt_accum_render", "pt_accum_resolve_device", "pt_accum_read")
+           "pt_accum_render", "pt_accum_render_stats", "pt_accum_resolve_device", "pt_accum_read")
 
 
 def lib():

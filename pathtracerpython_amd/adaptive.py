@@ -25,7 +25,8 @@ import weakref
 import numpy as np
 
 from . import _native
-from ._abi import PT_FLAG_FORCE_F64, PT_FLAG_OUT_F64, PT_FLAG_RR, make_adapt, make_params
+from ._abi import (PT_FLAG_FORCE_F64, PT_FLAG_MEGAKERNEL, PT_FLAG_OUT_F64, PT_FLAG_RR, PtStats,
+                   make_adapt, make_params)
 
 
 class AdaptiveResult:
@@ -92,9 +93,22 @@ class Accumulator:
                                                 C.byref(n), C.byref(k)), "pt_accum_select")
         return n.value, k.value
 
-    def render(self, params, adapt, stream=None):
-        _native.check(self._lib.pt_accum_render(self._h, C.byref(params), C.byref(adapt),
-                                                C.c_void_p(stream or 0)), "pt_accum_render")
+    def render(self, params, adapt, stream=None, stats=False):
+        """One pass.  Scenes with a BVH take it through the wavefront kernels
+        (PT_FLAG_MEGAKERNEL in params.flags: through the single kernel, the
+        same S, Q, n bit for bit).  stats=True returns the pass's stats dict
+        (pt_accum_render_stats): with PT_FLAG_WALK_COUNT / PT_FLAG_KERNEL_TIMES
+        the walk counts / per-kernel launch counts and times of a wavefront
+        pass, zeros after a single-kernel one."""
+        if not stats:
+            _native.check(self._lib.pt_accum_render(self._h, C.byref(params), C.byref(adapt),
+                                                    C.c_void_p(stream or 0)), "pt_accum_render")
+            return None
+        st = PtStats()
+        _native.check(self._lib.pt_accum_render_stats(self._h, C.byref(params), C.byref(adapt),
+                                                      C.c_void_p(stream or 0), C.byref(st)),
+                      "pt_accum_render_stats")
+        return st.as_dict(all_fields=True)
 
     def resolve_device(self, out_ptr, f64=True, stream=None):
         _native.check(self._lib.pt_accum_resolve_device(self._h, PT_FLAG_OUT_F64 if f64 else 0,
@@ -167,17 +181,20 @@ def run_passes(acc, params, adapt, on_pass=None, max_passes=None):
 
 def render_adaptive(renderer, width=None, height=None, max_spp=64, bounces=1, seed=None, rr=False,
                     rr_depth=3, tol=0.05, min_spp=8, step_spp=8, floor=0.01, force_f64=False,
-                    on_pass=None):
+                    on_pass=None, megakernel=False):
     """Render until err <= tol everywhere or a pixel has max_spp samples.
 
     renderer: a render.Renderer.  on_pass(i, n_active, samples_added) after
-    each pass.  Returns an AdaptiveResult."""
+    each pass.  megakernel=True: scenes with a BVH take their passes through
+    the single kernel instead of the wavefront kernels (the same result, bit
+    for bit).  Returns an AdaptiveResult."""
     check_rule(tol, max_spp, min_spp, step_spp, floor)
     width = int(renderer.scene.width if width is None else width)
     height = int(renderer.scene.height if height is None else height)
     seed = renderer.scene.seed if seed is None else seed
     seed = 0 if seed is None else int(seed)
-    flags = (PT_FLAG_RR if rr else 0) | (PT_FLAG_FORCE_F64 if force_f64 else 0)
+    flags = (PT_FLAG_RR if rr else 0) | (PT_FLAG_FORCE_F64 if force_f64 else 0) | \
+        (PT_FLAG_MEGAKERNEL if megakernel else 0)
     params = make_params(width, height, max_spp, bounces, seed, flags, rr_depth)
     adapt = make_adapt(tol, max_spp, min_spp, step_spp, floor)
     with Accumulator(renderer, width, height) as acc:

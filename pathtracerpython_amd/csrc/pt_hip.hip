@@ -421,15 +421,8 @@ __global__ __launch_bounds__(256) void k_wf_final(SceneK S, RenderK R, const WfP
 // pt_accum; the rule and the lane code: pt_path.h MomentSched, moment_err).
 // A pass renders a LIST of pixels: k_accum_select_* build it (err, the active
 // predicate, an ordered compaction), k_render_list adds k samples to each
-// listed pixel, k_accum_resolve writes S / n as a framebuffer.
-struct ListK {
-    int32_t W, H, bounces, rr_depth;   // rr_depth -1: off
-    uint64_t seed;
-    uint32_t split, split_log2;
-    uint32_t n_list, npix;
-    uint64_t lanes;   // work-items of the launch (a multiple of 64): the moment home's stride
-    AdaptK A;
-};
+// listed pixel, k_accum_resolve writes S / n as a framebuffer (ListK:
+// pt_render.h).
 // The lane's home of S and Q across the bounce loop: 0 the lane's registers
 // (MomentRegs), 1 a device buffer [6][lanes], touched only when a path ends
 // (MomentMem).  Both stay at 128 VGPRs / 64 B scratch; the registers are 5%
@@ -675,6 +668,60 @@ __global__ __launch_bounds__(256) void k_color(SceneK S, const int32_t* __restri
     const D3 col = ok ? nee<false, false>(S, P, ld3(normal + 3 * i), obj[i], -1, uu, sp, &c)
                           : nee<true, false>(S, P, ld3(normal + 3 * i), obj[i], -1, uu, sp, &c);
     out[3 * i] = col.x; out[3 * i + 1] = col.y; out[3 * i + 2] = col.z;
+}
+
+// ------------------------------- wavefront, list form (pt_accum) --
+// The list form of the wavefront render (BVH scenes, render_wavefront with a
+// WfList): k_wf_shade_list (pt_shade.h) for k_wf_shade, and the two kernels
+// below for k_wf_primary and k_wf_final; the walk kernels and the sort only
+// see the path slots, the query records and the lists.
+// The primary rays, one work-item per list entry (the entry's `split` slots
+// share it): CQP[entry], spill home in the entry's first slot, list entry =
+// entry (k_wf_closest's wshift = split_log2).
+__global__ __launch_bounds__(256) void k_wf_primary_list(SceneK S, ListK R, const uint32_t* __restrict__ list,
+                                                         const uint32_t* __restrict__ accN,
+                                                         WfPath* __restrict__ W, WfClosestQ* __restrict__ CQP,
+                                                         int32_t* __restrict__ qlist, int32_t* counters) {
+    const uint32_t entry = blockIdx.x * 256u + threadIdx.x;
+    uint32_t want = 0;
+    if (entry < R.n_list) {
+        const uint32_t slot = entry << R.split_log2;
+        const ListJob j = list_job(S, R, list, accN, slot);
+        if (j.valid) want = wf_start(S, j.J, j.d0, &W[slot], &CQP[entry]);
+    }
+    wf_append((want & kWfWantClosest) != 0, counters, qlist, (int32_t)entry);
+}
+// k_render_list's epilogue over the slots' sums (home[6][slots], one block of
+// 256 per 256 slots): an entry's slots reduce S and Q in store_pixel's xor
+// order and slot 0 adds them to the accumulator with plain loads and stores.
+__global__ __launch_bounds__(256) void k_wf_final_list(ListK R, const uint32_t* __restrict__ list,
+                                                       const double* __restrict__ home, uint32_t slots,
+                                                       double* __restrict__ accS, double* __restrict__ accQ,
+                                                       uint32_t* __restrict__ accN) {
+    const uint32_t tid = blockIdx.x * 256u + threadIdx.x;   // < slots
+    const uint32_t entry = tid >> R.split_log2, c = tid & (R.split - 1u);
+    const uint32_t e = entry < R.n_list ? list[entry] : 0xffffffffu;
+    const bool valid = e < R.npix;   // the same for all slots of an entry
+    const double* h = home + tid;
+    D3 s = d3(0, 0, 0), q = d3(0, 0, 0);
+    if (valid) {
+        s = d3(h[0], h[slots], h[2 * (size_t)slots]);
+        q = d3(h[3 * (size_t)slots], h[4 * (size_t)slots], h[5 * (size_t)slots]);
+    }
+    for (uint32_t m = 1; m < R.split; m <<= 1) {
+        s.x += __shfl_xor(s.x, (int)m); s.y += __shfl_xor(s.y, (int)m); s.z += __shfl_xor(s.z, (int)m);
+        q.x += __shfl_xor(q.x, (int)m); q.y += __shfl_xor(q.y, (int)m); q.z += __shfl_xor(q.z, (int)m);
+    }
+    if (valid && c == 0) {
+        const uint32_t k = adapt_k(accN[e], R.A);
+        if (k > 0) {
+            double* ps = accS + (size_t)e * 3;
+            double* pq = accQ + (size_t)e * 3;
+            ps[0] += s.x; ps[1] += s.y; ps[2] += s.z;
+            pq[0] += q.x; pq[1] += q.y; pq[2] += q.z;
+            accN[e] += k;
+        }
+    }
 }
 
 // ---------------------------------------------------------------- API --
@@ -1030,9 +1077,30 @@ static uint64_t min_lanes_of(int n_cu) {
 // queries it appended.  A slot runs at most n_samples x bounces bounces plus
 // the primary ray, so that many steps (+1 to finish the last bounce) drain
 // every slot; steps after that would find no work.
-static int render_wavefront(pt_scene* s, const RenderK& R, dim3 grid, void* out_dev, hipStream_t st,
-                            uint32_t flags, pt_stats* stats) {
+//
+// The list form (L, an accumulator pass: pt_accum_render): the same loop over
+// the slots of the active list's entries, with the list kernels for the
+// shade, primary and final steps and the slots' moment home [6][slots] beside
+// the path records.  The host knows the pass's smallest k only, so the steps
+// come from the largest k the rule allows.  Every pass initialises every slot
+// it launches (k_wf_shade_list's step 0): s->wf holds whatever the previous
+// pass or render left.
+struct WfList {
+    ListK R;
+    const uint32_t* list;
+    double *S, *Q;
+    uint32_t* n;
+    int32_t max_k;   // the most samples the pass adds to a pixel
+};
+static int render_wavefront(pt_scene* s, const RenderK& R, const WfList* L, dim3 grid, void* out_dev,
+                            hipStream_t st, uint32_t flags, pt_stats* stats) {
     const size_t slots = (size_t)grid.x * 256;
+    // primary queries (one per pixel / list entry), slots per query, samples per slot
+    const uint32_t n_prim = L ? L->R.n_list : R.npix;
+    const uint32_t split_log2 = L ? L->R.split_log2 : R.split_log2;
+    const int32_t split = (int32_t)(1u << split_log2);
+    const int32_t per_slot = ((L ? L->max_k : R.spp) + split - 1) / split;
+    const int32_t steps = per_slot * (L ? L->R.bounces : R.bounces) + 2;
     const size_t sz_w = slots * sizeof(WfPath), sz_s = slots * sizeof(WfShadowQ),
                  sz_c = slots * sizeof(WfClosestQ), sz_l = 4 * slots * sizeof(int32_t);
     const unsigned sh_blocks =
@@ -1046,7 +1114,7 @@ static int render_wavefront(pt_scene* s, const RenderK& R, dim3 grid, void* out_
                  sz_ocd = ovf_n * cl_blocks * 256 * 2;
     const size_t off_s = sz_w, off_c = off_s + sz_s, off_l = off_c + sz_c, off_n = off_l + sz_l;
     const size_t off_os = off_n + 256, off_ocr = off_os + sz_os, off_ocd = off_ocr + sz_ocr;
-    const size_t sz_p = (size_t)R.npix * sizeof(WfClosestQ);   // the primary queries, per pixel
+    const size_t sz_p = (size_t)n_prim * sizeof(WfClosestQ);   // the primary queries
     const size_t off_p = (off_ocd + sz_ocd + 255) / 256 * 256;
     // PT_WF_BIN: the shadow list's keys (3 slots x u16), the sorted list
     // (3 slots x i32), the sort's count matrix, its scan and scan storage
@@ -1059,7 +1127,9 @@ static int render_wavefront(pt_scene* s, const RenderK& R, dim3 grid, void* out_
                  sz_lo = PT_WF_BIN ? 3 * slots * sizeof(int32_t) : 0;
     const size_t off_k = (off_p + sz_p + 255) / 256 * 256, off_lo = (off_k + sz_k + 255) / 256 * 256,
                  off_t = (off_lo + sz_lo + 255) / 256 * 256;
-    const size_t need = off_t + sz_tmp + 256;
+    // the list form's moment home
+    const size_t off_h = (off_t + sz_tmp + 255) / 256 * 256, sz_h = L ? 6 * slots * sizeof(double) : 0;
+    const size_t need = off_h + sz_h + 256;
     if (need > s->wf_bytes) {
         if (s->wf) (void)hipFree(s->wf);
         s->wf = nullptr;
@@ -1084,6 +1154,7 @@ static int render_wavefront(pt_scene* s, const RenderK& R, dim3 grid, void* out_
     WfClosestQ* CQP = (WfClosestQ*)(b + off_p);
     uint16_t* keys = PT_WF_BIN ? (uint16_t*)(b + off_k) : nullptr;
     int32_t* lists_o = (int32_t*)(b + off_lo);
+    double* home = (double*)(b + off_h);
 #if PT_WF_BIN
     uint32_t* bin_hist = (uint32_t*)(b + off_t);
     uint32_t* bin_rowsum = bin_hist + (size_t)kBins * kBinBlocks;
@@ -1104,8 +1175,6 @@ static int render_wavefront(pt_scene* s, const RenderK& R, dim3 grid, void* out_
         return hipGetLastError();
     };
 #endif
-    const int32_t per_slot = (R.spp + (int32_t)R.split - 1) / (int32_t)R.split;
-    const int32_t steps = per_slot * R.bounces + 2;
     const bool wcount = (flags & PT_FLAG_WALK_COUNT) != 0 && stats;
     const bool times = (flags & PT_FLAG_KERNEL_TIMES) != 0 && stats;
     unsigned long long* wc = (unsigned long long*)s->stats;   // [0..2] shadow, [3..5] closest
@@ -1128,7 +1197,7 @@ static int render_wavefront(pt_scene* s, const RenderK& R, dim3 grid, void* out_
     auto closest_walk = [&](hipStream_t on, int32_t step) {
         const int32_t* l = lists + 3 * slots;
         WfClosestQ* q = step == 0 ? CQP : CQ;
-        const uint32_t ws = step == 0 ? R.split_log2 : 0u;
+        const uint32_t ws = step == 0 ? split_log2 : 0u;
         if (s->dev.bunitc) {
             if (wcount) hipLaunchKernelGGL((k_wf_closest<true, true>), dim3(cl_blocks), dim3(256), 0, on, s->dev, W, q, l, counters + 2, PT_WF_THR_CLOSEST, wc + 3, ovf_cr, ovf_cd, ws);
             else hipLaunchKernelGGL((k_wf_closest<true, false>), dim3(cl_blocks), dim3(256), 0, on, s->dev, W, q, l, counters + 2, PT_WF_THR_CLOSEST, wc + 3, ovf_cr, ovf_cd, ws);
@@ -1151,12 +1220,21 @@ static int render_wavefront(pt_scene* s, const RenderK& R, dim3 grid, void* out_
     for (int32_t step = 0; step < steps; ++step) {
         HIPCHK(hipMemsetAsync(counters, 0, 4 * sizeof(int32_t), st));
         HIPCHK(mark(step, 0, 0, st));
-        hipLaunchKernelGGL(k_wf_shade, dim3((unsigned)((slots + kShadeBlock - 1) / kShadeBlock)),
-                           dim3(kShadeBlock), 0, st, s->dev, R, step, W, SQ, CQ,
-                           (const WfClosestQ*)CQP, lists, counters, (uint32_t)slots, keys);
-        if (step == 0)
-            hipLaunchKernelGGL(k_wf_primary, dim3((R.npix + 255) / 256), dim3(256), 0, st, s->dev, R, W,
-                               CQP, lists + 3 * slots, counters + 2);
+        const dim3 sgrid((unsigned)((slots + kShadeBlock - 1) / kShadeBlock)), pgrid((n_prim + 255) / 256);
+        if (L) {
+            hipLaunchKernelGGL(k_wf_shade_list, sgrid, dim3(kShadeBlock), 0, st, s->dev, L->R, step, L->list,
+                               (const uint32_t*)L->n, W, SQ, CQ, (const WfClosestQ*)CQP, lists, counters,
+                               (uint32_t)slots, keys, home);
+            if (step == 0)
+                hipLaunchKernelGGL(k_wf_primary_list, pgrid, dim3(256), 0, st, s->dev, L->R, L->list,
+                                   (const uint32_t*)L->n, W, CQP, lists + 3 * slots, counters + 2);
+        } else {
+            hipLaunchKernelGGL(k_wf_shade, sgrid, dim3(kShadeBlock), 0, st, s->dev, R, step, W, SQ, CQ,
+                               (const WfClosestQ*)CQP, lists, counters, (uint32_t)slots, keys);
+            if (step == 0)
+                hipLaunchKernelGGL(k_wf_primary, pgrid, dim3(256), 0, st, s->dev, R, W, CQP,
+                                   lists + 3 * slots, counters + 2);
+        }
         HIPCHK(mark(step, 0, 1, st));
         sorted = false;
         if (step + 1 < steps) {
@@ -1190,7 +1268,11 @@ static int render_wavefront(pt_scene* s, const RenderK& R, dim3 grid, void* out_
             if (side) HIPCHK(hipStreamWaitEvent(st, s->wf_ev_walk, 0));
         }
     }
-    hipLaunchKernelGGL(k_wf_final, grid, dim3(256), 0, st, s->dev, R, (const WfPath*)W, out_dev);
+    if (L)
+        hipLaunchKernelGGL(k_wf_final_list, grid, dim3(256), 0, st, L->R, L->list, (const double*)home,
+                           (uint32_t)slots, L->S, L->Q, L->n);
+    else
+        hipLaunchKernelGGL(k_wf_final, grid, dim3(256), 0, st, s->dev, R, (const WfPath*)W, out_dev);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s->ev1, st));
     s->timed = true;
@@ -1306,7 +1388,7 @@ int pt_render_device(pt_scene* s, const pt_render_params* p, void* out_dev, void
     const bool wavefront = s->dev.n_bnode > 0 && !count && !f64 &&
                            !(p->flags & PT_FLAG_MEGAKERNEL) && s->dev.n_qnode > 0 &&
                            s->dev.qstack <= kWalkStack && (uint64_t)grid.x * 256u < ((uint64_t)1 << 29);
-    if (wavefront) return render_wavefront(s, R, grid, out_dev, st, p->flags, stats);
+    if (wavefront) return render_wavefront(s, R, nullptr, grid, out_dev, st, p->flags, stats);
     if (count) HIPCHK(hipMemsetAsync(s->stats, 0, sizeof(StatsDev), st));
     HIPCHK(hipEventRecord(s->ev0, st));
     if (f64) {
@@ -1518,6 +1600,11 @@ int pt_accum_select(pt_accum* a, const pt_adapt_params* ap, void* stream, uint32
 }
 
 int pt_accum_render(pt_accum* a, const pt_render_params* p, const pt_adapt_params* ap, void* stream) {
+    return pt_accum_render_stats(a, p, ap, stream, nullptr);
+}
+
+int pt_accum_render_stats(pt_accum* a, const pt_render_params* p, const pt_adapt_params* ap, void* stream,
+                          pt_stats* stats) {
     int rc = validate(p);
     if (rc) return rc;
     if (!a) return fail(PT_EINVAL, "null accumulator");
@@ -1530,12 +1617,15 @@ int pt_accum_render(pt_accum* a, const pt_render_params* p, const pt_adapt_param
         p->sample_begin != 0 || p->out_row_stride != 0 || p->lanes_per_pixel != 0)
         return fail(PT_EINVAL, "an accumulator pass renders the whole frame: row_begin 0, row_end height, "
                                "row_step 1, sample_begin 0, out_row_stride 0, lanes_per_pixel 0");
-    if (p->flags & ~(uint32_t)(PT_FLAG_RR | PT_FLAG_FORCE_F64))
-        return fail(PT_EINVAL, "unsupported flag bits: an accumulator pass takes PT_FLAG_RR and PT_FLAG_FORCE_F64 only");
+    if (p->flags & ~(uint32_t)(PT_FLAG_RR | PT_FLAG_FORCE_F64 | PT_FLAG_MEGAKERNEL | PT_FLAG_WALK_COUNT |
+                               PT_FLAG_KERNEL_TIMES))
+        return fail(PT_EINVAL, "unsupported flag bits: an accumulator pass takes PT_FLAG_RR, PT_FLAG_FORCE_F64, "
+                               "PT_FLAG_MEGAKERNEL, PT_FLAG_WALK_COUNT and PT_FLAG_KERNEL_TIMES only");
     if (p->spp != ap->max_spp) return fail(PT_EINVAL, "spp must be the budget max_spp");
     pt_scene* s = a->scene;
     DeviceGuard g(s->device);
     hipStream_t st = (hipStream_t)stream;
+    if (stats) memset(stats, 0, sizeof(*stats));
     rc = pt_accum_select(a, ap, stream, nullptr, nullptr);
     if (rc) return rc;
     const AccumMeta m = a->list_meta;
@@ -1560,6 +1650,24 @@ int pt_accum_render(pt_accum* a, const pt_render_params* p, const pt_adapt_param
     const uint64_t blocks = (threads + kRenderBlock - 1) / kRenderBlock;
     R.lanes = blocks * kRenderBlock;
     if (R.lanes >= ((uint64_t)1 << 32)) return fail(PT_EINVAL, "launch needs 2^32 or more work-items (32-bit lane index)");
+    const bool f64 = (p->flags & PT_FLAG_FORCE_F64) != 0;
+    // BVH scenes take the pass through the wavefront kernels (render_wavefront's
+    // list form) under pt_render_device's conditions; the same split, so S, Q
+    // and n are the single kernel's bit for bit
+    const uint64_t wf_blocks = (threads + 255) / 256;
+    if (bvh && !f64 && !(p->flags & PT_FLAG_MEGAKERNEL) && s->dev.n_qnode > 0 &&
+        s->dev.qstack <= kWalkStack && wf_blocks * 256u < ((uint64_t)1 << 29)) {
+        rc = accum_begin(a, st);
+        if (rc) return rc;
+        a->list_valid = false;   // the pass changes n, S, Q
+        WfList L;
+        L.R = R;
+        L.R.lanes = wf_blocks * 256u;
+        L.list = a->list;
+        L.S = a->S; L.Q = a->Q; L.n = a->n;
+        L.max_k = (int32_t)std::min(A.step_spp, A.max_spp);
+        return render_wavefront(s, RenderK{}, &L, dim3((unsigned)wf_blocks), nullptr, st, p->flags, stats);
+    }
 #if PT_MOMENT_HOME
     if (R.lanes > a->home_lanes) {   // (the previous pass may still read the old one: ordered by the free)
         if (a->home) HIPCHK(hipFree(a->home));
@@ -1574,7 +1682,6 @@ int pt_accum_render(pt_accum* a, const pt_render_params* p, const pt_adapt_param
     if (rc) return rc;
     a->list_valid = false;   // the pass changes n, S, Q
     const dim3 grid((unsigned)blocks), block(kRenderBlock);
-    const bool f64 = (p->flags & PT_FLAG_FORCE_F64) != 0;
     if (f64) {
         hipLaunchKernelGGL((k_render_list<true, true>), grid, block, 0, st, s->dev, R, a->list, a->S, a->Q, a->n, a->home);
     } else if (bvh) {

@@ -92,6 +92,57 @@ __device__ __forceinline__ SlotJob slot_job(const SceneK& S, const RenderK& R, u
     return j;
 }
 
+// An accumulator pass (pt_accum, pt_hip.hip "adaptive sampling"): the launch
+// renders a LIST of pixels.
+struct ListK {
+    int32_t W, H, bounces, rr_depth;   // rr_depth -1: off
+    uint64_t seed;
+    uint32_t split, split_log2;
+    uint32_t n_list, npix;
+    uint64_t lanes;   // work-items of the launch (a multiple of 64): the moment home's stride
+    AdaptK A;
+};
+// Work-item -> (list entry, sample slice) of a pass through the wavefront
+// kernels, k_render_list's mapping: `split` adjacent slots share the entry's
+// pixel e and stride the k = adapt_k(n[e]) samples the pass adds, from sample
+// n[e] on.  An entry that is no pixel of the frame is never dereferenced.
+struct ListJob {
+    LaneJob J;
+    D3 d0;
+    uint32_t e, k;
+    bool valid;
+};
+__device__ __forceinline__ ListJob list_job(const SceneK& S, const ListK& R, const uint32_t* __restrict__ list,
+                                            const uint32_t* __restrict__ accN, uint32_t tid) {
+    ListJob j;
+    const uint32_t entry = tid >> R.split_log2, c = tid & (R.split - 1u);
+    j.e = entry < R.n_list ? list[entry] : 0xffffffffu;
+    j.valid = j.e < R.npix;   // the same for all slots of an entry
+    j.k = 0;
+    j.d0 = d3(0, 0, 0);
+    j.J = LaneJob{};
+    // (the launch's constants outside the branch: they stay wave-uniform, and
+    // rng_block takes its key in scalar registers)
+    j.J.seed = R.seed;
+    j.J.sample_stride = (int32_t)R.split;
+    j.J.bounces = R.bounces;
+    j.J.rr_depth = R.rr_depth;
+    if (j.valid) {
+        const uint32_t n0 = accN[j.e];
+        j.k = adapt_k(n0, R.A);
+        const int32_t row = (int32_t)(j.e / (uint32_t)R.W);
+        const int32_t ix = (int32_t)j.e - row * R.W, iy = R.H - 1 - row;
+        const D3 eye = ld3(S.eye);
+        const double x = linspace_at(S.ortho[0], S.ortho[2], R.W, ix);
+        const double y = linspace_at(S.ortho[1], S.ortho[3], R.H, iy);
+        j.d0 = d3(x - eye.x, y - eye.y, 0.0 - eye.z);
+        j.J.pixel = (uint32_t)ix * (uint32_t)R.H + (uint32_t)iy;
+        j.J.sample0 = (int32_t)(n0 + c);
+        j.J.n_samples = c < j.k ? (int32_t)((j.k - c + R.split - 1u) >> R.split_log2) : 0;
+    }
+    return j;
+}
+
 // Sum of a pixel's sample colours over its `split` work-items (fixed xor
 // order: deterministic), / spp (main.py:277), into the framebuffer.
 __device__ __forceinline__ void store_pixel(const RenderK& R, const SlotJob& j, D3 acc, void* out,

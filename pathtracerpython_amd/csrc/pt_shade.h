@@ -1,6 +1,7 @@
 // pt_shade.h — the wavefront path's list appends and its shade step
-// (k_wf_shade), shared by pt_hip.hip and pt_shade.hip: k_wf_shade is compiled
-// in a translation unit of its own (pt_shade.hip) so that it gets its own
+// (k_wf_shade; k_wf_shade_list, its list form for accumulator passes), shared
+// by pt_hip.hip and pt_shade.hip: the shade kernels are compiled in a
+// translation unit of their own (pt_shade.hip) so that they get their own
 // code-generation flags (build.py UNITS), as the K2 kernel does (pt_k2.hip).
 #pragma once
 #include "pt_render.h"
@@ -163,10 +164,54 @@ __global__ __launch_bounds__(kShadeBlock) void k_wf_shade(SceneK S, RenderK R, i
     wf_append((want & kWfWantClosest) != 0, &counters[2], lists + 3 * (size_t)slots, (int32_t)tid);
 #endif
 }
+// The list form (an accumulator pass, pt_accum_render): slot -> (list entry,
+// sample slice) by list_job, and a path's colour goes to the slot's six sums
+// when the path ends (wf_finish's WfMoments home, home[6][slots]).  Step 0
+// initialises every slot of the launch and its sums: the buffers hold the
+// state of an earlier pass or render.
+__global__ __launch_bounds__(kShadeBlock) void k_wf_shade_list(
+    SceneK S, ListK R, int32_t step, const uint32_t* __restrict__ list, const uint32_t* __restrict__ accN,
+    WfPath* __restrict__ W, WfShadowQ* __restrict__ SQ, WfClosestQ* __restrict__ CQ,
+    const WfClosestQ* __restrict__ CQP, int32_t* __restrict__ lists, int32_t* counters, uint32_t slots,
+    uint16_t* __restrict__ keys, double* __restrict__ home) {
+    const uint32_t tid = blockIdx.x * (uint32_t)kShadeBlock + threadIdx.x;
+    uint32_t want = 0;
+#if PT_WF_BIN
+    uint32_t skey = 0;
+#endif
+    WfMoments M{{home + tid, (size_t)slots}};
+    if (tid >= slots) {   // (the last block of a kShadeBlock grid over 256-slot blocks)
+    } else if (step == 0) {   // the primary queries are k_wf_primary_list's (one per entry)
+        const ListJob j = list_job(S, R, list, accN, tid);
+        M.clear();
+        W[tid].acc[0] = W[tid].acc[1] = W[tid].acc[2] = 0.0;
+        W[tid].put_rkey(j.J);
+        W[tid].set(j.valid && j.J.n_samples > 0 && j.J.bounces > 0 ? kWfPrimary : kWfDone, false, 0);
+    } else if ((tid >> R.split_log2) < R.n_list && W[tid].state() != kWfDone) {
+        const ListJob j = list_job(S, R, list, accN, tid);
+#if PT_WF_BIN
+        want = wf_shade<true>(S, j.J, j.d0, &W[tid], &SQ[tid], &CQ[tid], &CQP[tid >> R.split_log2], M);
+        skey = want >> 16;
+        want &= 0xffffu;
+#else
+        want = wf_shade(S, j.J, j.d0, &W[tid], &SQ[tid], &CQ[tid], &CQP[tid >> R.split_log2], M);
+#endif
+    }
+#if PT_WF_BIN
+    wf_append_block(want, counters, lists, lists + 3 * (size_t)slots, (int32_t)tid, keys, skey);
+#else
+    wf_append_block(want, counters, lists, lists + 3 * (size_t)slots, (int32_t)tid);
+#endif
+}
 #elif !defined(PT_SHADE_UNIT)
 __global__ __launch_bounds__(kShadeBlock) void k_wf_shade(SceneK S, RenderK R, int32_t step,
                                                   WfPath* __restrict__ W, WfShadowQ* __restrict__ SQ,
                                                   WfClosestQ* __restrict__ CQ, const WfClosestQ* __restrict__ CQP,
                                                   int32_t* __restrict__ lists, int32_t* counters,
                                                   uint32_t slots, uint16_t* __restrict__ keys);
+__global__ __launch_bounds__(kShadeBlock) void k_wf_shade_list(
+    SceneK S, ListK R, int32_t step, const uint32_t* __restrict__ list, const uint32_t* __restrict__ accN,
+    WfPath* __restrict__ W, WfShadowQ* __restrict__ SQ, WfClosestQ* __restrict__ CQ,
+    const WfClosestQ* __restrict__ CQP, int32_t* __restrict__ lists, int32_t* counters, uint32_t slots,
+    uint16_t* __restrict__ keys, double* __restrict__ home);
 #endif

@@ -311,8 +311,18 @@ PT_HD uint32_t wf_begin_bounce(const SceneK& S, const LaneJob& J, WfPath* W, WfS
 // true when the slot's next bounce is to be started (state kWfBegin; the
 // second half is wf_begin_bounce).  pq: the slot's primary query (the GPU
 // shares one per pixel, k_wf_primary; the host emulation has one per slot, cq)
+//
+// Home: where a path's colour goes when the path ends.  WfSum (the uniform
+// render): nowhere, W->acc runs on over the slot's samples.  WfMoments (the
+// list form, an accumulator pass): MomentSched's rule (pt_path.h) — the
+// colour is added to the slot's six sums and W->acc restarts at 0, wherever
+// `done` is set below; a primary ray that escapes or hits the light adds its
+// constant n_samples times, as render_lane_moments does.
+struct WfSum { static constexpr bool kMoments = false; };
+struct WfMoments : MomentMem { static constexpr bool kMoments = true; };
+template <class Home>
 PT_HD bool wf_finish(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, const WfShadowQ* shq,
-                     const WfClosestQ* cq, const WfClosestQ* pq) {
+                     const WfClosestQ* cq, const WfClosestQ* pq, Home home) {
     const Spill sp{W->sp, 1};
     if (W->state() == kWfPrimary) {   // k_render: closest(eye, d0) then render_lane's prologue
         D3 P0 = d3(0, 0, 0);
@@ -321,7 +331,11 @@ PT_HD bool wf_finish(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, const 
         if (tri0 < 0 || tri0 >= S.n_obj_tri) {   // primary ray escapes or hits the light
             const D3 v = tri0 < 0 ? d3(0, 0, 0) : ld3(S.kd + kKdLightRgb);
             D3 acc = d3(0, 0, 0);
-            for (int i = 0; i < J.n_samples; ++i) acc = acc + v;
+            if constexpr (Home::kMoments) {
+                for (int i = 0; i < J.n_samples; ++i) home.add(v);
+            } else {
+                for (int i = 0; i < J.n_samples; ++i) acc = acc + v;
+            }
             W->acc[0] = acc.x; W->acc[1] = acc.y; W->acc[2] = acc.z;
             W->set(kWfDone, false, 0);
             return false;
@@ -371,6 +385,10 @@ PT_HD bool wf_finish(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, const 
         }
     }
     if (done) {
+        if constexpr (Home::kMoments) {   // MomentSched::advance
+            home.add(acc);
+            acc = d3(0, 0, 0);
+        }
         ++si;
         if (si < J.n_samples) {   // next sample from the cached primary hit
             b = 0;
@@ -391,15 +409,19 @@ PT_HD bool wf_finish(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, const 
     W->set(kWfBegin, false, b);   // (begin_bounce sets the state and trace)
     return true;
 }
+PT_HD bool wf_finish(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, const WfShadowQ* shq,
+                     const WfClosestQ* cq, const WfClosestQ* pq) {
+    return wf_finish(S, J, d0, W, shq, cq, pq, WfSum{});
+}
 
 // Shade step >= 1: wf_finish, then the next bounce's start.  Returns the
 // queries wanted.  (One call site of wf_begin_bounce: round 4 started the
 // next bounce from two, inlined twice — 141 instead of 113 VGPRs for
 // k_wf_shade, the same time)
-template <bool KEY = false>
+template <bool KEY = false, class Home = WfSum>
 PT_HD uint32_t wf_shade(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, WfShadowQ* shq,
-                        WfClosestQ* cq, const WfClosestQ* pq) {
-    return wf_finish(S, J, d0, W, shq, cq, pq) ? wf_begin_bounce<KEY>(S, J, W, shq, cq) : 0u;
+                        WfClosestQ* cq, const WfClosestQ* pq, Home home = Home{}) {
+    return wf_finish(S, J, d0, W, shq, cq, pq, home) ? wf_begin_bounce<KEY>(S, J, W, shq, cq) : 0u;
 }
 
 }  // namespace pt

@@ -119,12 +119,14 @@ class Renderer:
         return (img, fb.cpu().numpy()) if return_fb else img
 
     def render_adaptive(self, width=None, height=None, max_spp=64, bounces=1, seed=None,
-                        rr=False, rr_depth=3, tol=0.05, **rule):
+                        rr=False, rr_depth=3, tol=0.05, megakernel=False, **rule):
         """Render to the noise target `tol` within max_spp samples per pixel
-        (adaptive.render_adaptive: fb, counts, err, passes, samples)."""
+        (adaptive.render_adaptive: fb, counts, err, passes, samples).
+        megakernel=True: a BVH scene's passes run the single kernel instead of
+        the wavefront kernels (the same result, bit for bit)."""
         from .adaptive import render_adaptive
         return render_adaptive(self, width, height, max_spp, bounces, seed, rr, rr_depth, tol,
-                               **rule)
+                               megakernel=megakernel, **rule)
 
     def last_kernel_ms(self):
         ms = C.c_float(0)

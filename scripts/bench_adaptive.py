@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Measure the adaptive sampler (dev tool; prints one JSON document).
 
-    python3 scripts/bench_adaptive.py [--parts a,b] [--reps N] [--out FILE]
+    python3 scripts/bench_adaptive.py [--parts a,b | --parts c] [--reps N] [--out FILE]
 
 The K2 shape: Cornell 512x512, 4 bounces, seed 9, budget 64 samples per pixel.
   a  throughput of the list kernel: tol 0, min = max = 64 in one pass of 64 and
@@ -12,6 +12,11 @@ The K2 shape: Cornell 512x512, 4 bounces, seed 9, budget 64 samples per pixel.
      time of the whole run, RMSE against a 4096-spp uniform frame of another
      seed, and beside it the RMSE of a uniform render of the same total sample
      count; each also as a relative RMSE in the stop rule's normalisation
+  c  BVH scenes, the K5 shape (synth, 100k triangles, 1024x1024, 4 bounces,
+     budget 64): the wavefront list form beside the single-kernel list pass
+     (megakernel=True) and the uniform wavefront render — (i) one pass of 64,
+     (ii) 8 passes of 8, (iii) whole runs at tol 0.05 and 0.02 (min 8, step 8):
+     samples, passes, wall time.  Written to its own document (--out).
 Reads none of bench.py's artifacts.  Times are medians over --reps rounds
 after --warmup rounds, with min and max."""
 import argparse
@@ -41,6 +46,113 @@ def rel_rmse(x, ref, floor=0.01):
     return float(np.sqrt(np.mean(e ** 2)))
 
 
+def part_c(args):
+    """The K5 shape: both list paths and the uniform wavefront render in
+    interleaved rounds of one process."""
+    import tempfile
+
+    import torch
+    from pathtracerpython_amd import _native, scene_reader
+    from pathtracerpython_amd._abi import make_adapt
+    from pathtracerpython_amd.adaptive import Accumulator, run_passes
+    from pathtracerpython_amd.render import Renderer
+    from pathtracerpython_amd.synth import write_k5_scene
+    scene_reader.VERBOSE = False
+    Wc = Hc = 1024
+    n_tris = 100_000
+    sc = scene_reader.Scene(write_k5_scene(tempfile.mkdtemp(), n_tris=n_tris, seed=0, size=Wc))
+    npix = Wc * Hc
+    res = {"shape": {"scene": "K5 synth", "n_tris": n_tris, "width": Wc, "height": Hc, "bounces": BOUNCES,
+                     "seed": SEED, "budget": BUDGET},
+           "build_id": _native.build_id(), "device": torch.cuda.get_device_name(0),
+           "reps": args.reps, "warmup": args.warmup}
+    with Renderer(sc) as r, Accumulator(r, Wc, Hc) as acc:
+        params = {"wavefront": r.params(Wc, Hc, BUDGET, BOUNCES, SEED),
+                  "single_kernel": r.params(Wc, Hc, BUDGET, BOUNCES, SEED, megakernel=True)}
+        fb = torch.empty((Hc, Wc, 3), dtype=torch.float32, device="cuda")
+
+        def uniform():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            r.render_device(params["wavefront"], fb.data_ptr(), 0)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3, r.last_kernel_ms()
+
+        def adaptive(path, adapt):
+            """(wall ms of reset + every select and pass, summed pass kernel ms, passes)"""
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            acc.reset()
+            passes = run_passes(acc, params[path], adapt)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3, passes
+
+        def pass_kernel_ms(path, adapt):
+            acc.reset()
+            out = []
+            while acc.select(adapt)[0]:
+                acc.render(params[path], adapt)
+                out.append(r.last_kernel_ms())
+            return out
+
+        one = make_adapt(0.0, BUDGET, BUDGET, BUDGET)
+        eight = make_adapt(0.0, BUDGET, BUDGET, 8)
+        legs = [("uniform_wavefront", None, None)] + \
+               [("%s_%s" % (path, tag), path, adapt) for tag, adapt in (("1x64", one), ("8x8", eight))
+                for path in ("wavefront", "single_kernel")]
+        wall = {name: [] for name, _, _ in legs}
+        kern = {name: [] for name, _, _ in legs}
+        for i in range(args.warmup + args.reps):
+            for name, path, adapt in legs:
+                if path is None:
+                    w, k = uniform()
+                else:
+                    w, _ = adaptive(path, adapt)
+                    k = sum(pass_kernel_ms(path, adapt))
+                if i >= args.warmup:
+                    wall[name].append(w)
+                    kern[name].append(k)
+        t = {}
+        for name in wall:
+            t[name] = {"wall_ms": stat(wall[name]), "kernel_ms": stat(kern[name]),
+                       "msamples_per_s_kernel": npix * BUDGET / statistics.median(kern[name]) / 1e3,
+                       "msamples_per_s_wall": npix * BUDGET / statistics.median(wall[name]) / 1e3}
+        for name in wall:
+            for base in ("uniform_wavefront", "single_kernel_" + name.rsplit("_", 1)[-1]):
+                if name != base and base in t:
+                    t[name]["kernel_ratio_to_" + base] = (t[name]["kernel_ms"]["median"] /
+                                                          t[base]["kernel_ms"]["median"])
+                    t[name]["wall_ratio_to_" + base] = (t[name]["wall_ms"]["median"] /
+                                                        t[base]["wall_ms"]["median"])
+        res["throughput"] = t
+        runs = []
+        for tol in (0.05, 0.02):
+            adapt = make_adapt(tol, BUDGET, 8, 8, 0.01)
+            walls = {"wavefront": [], "single_kernel": []}
+            got = {}
+            for i in range(args.warmup + args.reps):
+                for path in walls:
+                    w, passes = adaptive(path, adapt)
+                    if i >= args.warmup:
+                        walls[path].append(w)
+                    d = acc.read(n=True)
+                    got[path] = (passes, int(d["n"].sum()))
+            assert got["wavefront"] == got["single_kernel"]   # the same run on either path
+            passes, total = got["wavefront"]
+            row = {"tol": tol, "min_spp": 8, "step_spp": 8, "floor": 0.01, "samples": total,
+                   "fraction_of_uniform_budget": total / (npix * BUDGET),
+                   "passes": [list(x) for x in passes]}
+            for path in walls:
+                row[path] = {"wall_ms": stat(walls[path]), "pass_kernel_ms": pass_kernel_ms(path, adapt)}
+            row["wall_ratio_wavefront_to_single_kernel"] = (row["wavefront"]["wall_ms"]["median"] /
+                                                            row["single_kernel"]["wall_ms"]["median"])
+            row["wall_ratio_wavefront_to_uniform_budget"] = (row["wavefront"]["wall_ms"]["median"] /
+                                                             t["uniform_wavefront"]["wall_ms"]["median"])
+            runs.append(row)
+        res["adaptive"] = runs
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parts", default="a,b")
@@ -49,6 +161,15 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
+    torch.cuda.set_device(0)
+    if args.parts == "c":   # the K5 shape: a document of its own
+        text = json.dumps(part_c(args), indent=1)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        print(text)
+        return
     from pathtracerpython_amd import _native, scene_reader
     from pathtracerpython_amd._abi import make_adapt
     from pathtracerpython_amd.adaptive import Accumulator, run_passes
