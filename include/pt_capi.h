@@ -289,6 +289,102 @@ int pt_accum_resolve_device(pt_accum* acc, uint32_t flags, void* out_rgb_dev, vo
 int pt_accum_read(pt_accum* acc, double* S, double* Q, uint32_t* n, double* err,
                   uint32_t* list, uint32_t list_cap, uint32_t* list_len);
 
+/* Denoising an adaptive render on the device (additive; build extension — the
+ * reference has no filter).  An edge-avoiding a-trous filter over the frame,
+ * guided by the per-pixel variance of the mean (from an accumulator's S, Q, n)
+ * and by the first hit of each pixel's primary ray.  It changes no sample: it
+ * produces a second, filtered frame.  Pixel e = row*W + col in image
+ * orientation (row = H-1-iy, col = ix).  Everything is f64, each operation
+ * rounded on its own, in exactly this order (IEEE division and sqrt, no fma).
+ *
+ * Inputs per pixel: colour c[3], variance of the mean v[3], features obj
+ * (i32), N[3], P[3].  From an accumulator:
+ *     n >= 2:  c = S/n,  v = (max(0, Q - S*S/n)/(n-1))/n
+ *     n == 1:  c = S,    v = c*c      (variance unknown: lean on the neighbours)
+ *     n == 0:  c = v = 0
+ * Constants: A = (0.2126, 0.7152, 0.0722), B_k = A_k*A_k,
+ * H5 = (1/16, 1/4, 3/8, 1/4, 1/16), G = (1/4, 1/2, 1/4).  max(0, x) is
+ * x > 0 ? x : 0.
+ * Iteration i = 0 .. iters-1, stride s = 2^i, reading (c, v), writing (c', v'):
+ *  1. l = (A0*c0 + A1*c1) + A2*c2, vl = (B0*v0 + B1*v1) + B2*v2 at every pixel.
+ *  2. At pixel p: vf = sum of (G[dy+1]*G[dx+1]) * vl[clamped (row+dy, col+dx)],
+ *     dy outer and dx inner over -1..1, accumulated from 0.0;
+ *     dl = sigma_l*sqrt(vf) + eps.
+ *  3. Taps dy outer, dx inner over -2..2 at q = (row+dy*s, col+dx*s).  A tap
+ *     outside the frame, or with obj[q] != obj[p], is skipped.  Otherwise
+ *         w = H5[dy+2]*H5[dx+2]
+ *         if obj[p] >= 0:
+ *             nd = max(0, (Np0*Nq0 + Np1*Nq1) + Np2*Nq2); nd = nd*nd, normal_sq times
+ *             D = Pq - Pp; dist = sqrt((D0*D0 + D1*D1) + D2*D2)
+ *             pd = |(Np0*D0 + Np1*D1) + Np2*D2|
+ *             xz = dist > 0 ? pd/(dist*sigma_z) : 0
+ *             wz = max(0, 1 - xz); wz = wz*wz;  w = (w*nd)*wz
+ *         xl = |l[q] - l[p]| / dl
+ *         w = w * (1/((1 + xl) + 0.5*(xl*xl)))
+ *         num_k += w*c[q][k];  vnum_k += (w*w)*v[q][k];  den += w
+ *  4. c'_k = num_k/den, v'_k = vnum_k/(den*den) (the centre tap makes den > 0).
+ * Requires 1 <= iters <= 8, 0 <= normal_sq <= 8, sigma_l > 0, sigma_z > 0,
+ * eps > 0, reserved 0 (PT_EINVAL otherwise); frames of 2^30 pixels or more
+ * are refused.  N of a hit pixel is a unit vector (the centre tap's weight is
+ * (N.N)^(2^normal_sq)).  Defaults of the Python layer: iters 5, sigma_l 2.0,
+ * sigma_z 0.1, eps 1e-10, normal_sq 5.                                       */
+typedef struct pt_denoise_params {
+    double sigma_l;          /* luminance stop, in standard deviations        */
+    double sigma_z;          /* plane-distance stop, relative to the tap's distance */
+    double eps;              /* added to the luminance stop's scale           */
+    int32_t iters;           /* iterations; iteration i has stride 2^i        */
+    int32_t normal_sq;       /* the normal stop is (Np.Nq)^(2^normal_sq)      */
+    int32_t reserved;        /* 0 */
+} pt_denoise_params;         /* 40 bytes (4 of tail padding) */
+
+/* The filter on caller-provided DEVICE arrays of the current device, scene-free
+ * like pt_image_u8_device: c, v, N, P [height*width][3] f64, obj
+ * [height*width] i32 (read-only); out_rgb and out_var (may be NULL)
+ * [height*width][3] float32, or float64 with PT_FLAG_OUT_F64 in flags (the
+ * only flag).  The call owns its scratch: two (c, v) frames, 96 B per pixel,
+ * allocated and freed on `stream` (stream-ordered).  Asynchronous on `stream`. */
+int pt_denoise_device(int32_t width, int32_t height, const pt_denoise_params* params,
+                      const double* c, const double* v, const int32_t* obj, const double* N,
+                      const double* P, uint32_t flags, void* out_rgb, void* out_var, void* stream);
+/* Same, synchronous, with host arrays. */
+int pt_denoise(int32_t width, int32_t height, const pt_denoise_params* params, const double* c,
+               const double* v, const int32_t* obj, const double* N, const double* P,
+               uint32_t flags, void* out_rgb, void* out_var);
+
+/* First-hit features of the accumulator's frame, one primary ray per pixel
+ * (the ray a render builds; closest hit as pt_intersect_objects finds it):
+ * tri (i32, -1 for an escape), obj = tri_obj[tri] (the light is n_obj, an
+ * escape -1), N = tri_n[tri] as the scene descriptor holds it (no flip, no
+ * renormalisation), P = the f64 hit point; N = P = 0 for an escape.  Computed
+ * once per accumulator and kept (a second call does nothing); allocated at
+ * the first call, 56 B per pixel, so an accumulator that is never denoised
+ * costs nothing more.  Asynchronous on `stream`. */
+int pt_accum_features(pt_accum* acc, void* stream);
+/* Synchronous copy-out (computes the features first when missing); NULL
+ * pointers are skipped.  tri, obj: [height*width] i32; N, P:
+ * [height*width][3] f64. */
+int pt_accum_read_features(pt_accum* acc, int32_t* tri, int32_t* obj, double* N, double* P);
+/* The filtered frame of the accumulator's present state: moments -> (c, v),
+ * the features when missing, params->iters iterations, then out_rgb_dev and
+ * out_var_dev (may be NULL) as pt_denoise_device writes them; flags:
+ * PT_FLAG_OUT_F64 only.  S, Q, n, err and the list are left untouched, and a
+ * run continues after it as if it had not happened.  Ordered on the scene
+ * handle like every accumulator launch.  The accumulator keeps the scratch
+ * from the first call on: two (c, v) frames, 96 B per pixel, beside the 56 B
+ * per pixel of features — 152 B per pixel, 2.6 GB at 4096 x 4096.
+ * Asynchronous on `stream`. */
+int pt_accum_denoise_device(pt_accum* acc, const pt_denoise_params* params, uint32_t flags,
+                            void* out_rgb_dev, void* out_var_dev, void* stream);
+
+/* Measurement hook (scripts/bench_denoise.py).  While enabled, a denoise call
+ * records a HIP event around each of its launches, waits for them (the call
+ * is then synchronous) and keeps the times in ms: k_accum_moments (the
+ * accumulator form only), each iteration, the final store.  The call sets the
+ * switch and copies out the times of the last timed denoise: up to cap values
+ * into ms (may be NULL with cap 0), their number into *n (may be NULL).
+ * Process-wide; off by default. */
+int pt_denoise_times(int32_t enable, float* ms, int32_t cap, int32_t* n);
+
 /* Batched replacement of intersect_objects (main.py:83-122).
  * rays: [n][6] f64 (origin, direction — direction need not be normalised).
  * out_tri [n]: closest triangle index or -1 (None); out_p [n][3]: hit point.

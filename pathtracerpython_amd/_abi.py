@@ -60,6 +60,22 @@ def make_adapt(tol, max_spp, min_spp=8, step_spp=8, floor=0.01):
     return a
 
 
+class PtDenoiseParams(C.Structure):
+    """pt_denoise_params (include/pt_capi.h): the filter of a denoise."""
+    _fields_ = [("sigma_l", C.c_double), ("sigma_z", C.c_double), ("eps", C.c_double),
+                ("iters", C.c_int32), ("normal_sq", C.c_int32), ("reserved", C.c_int32)]
+
+
+DENOISE_DEFAULTS = dict(iters=5, sigma_l=2.0, sigma_z=0.1, eps=1e-10, normal_sq=5)
+
+
+def make_denoise(iters=5, sigma_l=2.0, sigma_z=0.1, eps=1e-10, normal_sq=5):
+    d = PtDenoiseParams()
+    d.sigma_l, d.sigma_z, d.eps = float(sigma_l), float(sigma_z), float(eps)
+    d.iters, d.normal_sq = int(iters), int(normal_sq)
+    return d
+
+
 class PtMesh(C.Structure):
     """pt_mesh (include/pt_capi.h): a mesh read by pt_obj_load."""
     _fields_ = [("n_vert", C.c_int64), ("n_tri", C.c_int64), ("n_skip", C.c_int64),

@@ -26,16 +26,20 @@ import numpy as np
 
 from . import _native
 from ._abi import (PT_FLAG_FORCE_F64, PT_FLAG_MEGAKERNEL, PT_FLAG_OUT_F64, PT_FLAG_RR, PtStats,
-                   make_adapt, make_params)
+                   make_adapt, make_denoise, make_params)
 
 
 class AdaptiveResult:
     """fb (H, W, 3) f64 mean colours; counts (H, W) u32 samples per pixel;
     err (H, W) f64 the last error estimates; passes [(n_active,
-    samples_added)]; samples the total."""
+    samples_added)]; samples the total.  After a run with denoise: denoised
+    (H, W, 3) f64 the filtered frame, denoised_var (H, W, 3) f64 its variance
+    estimate, features dict(tri, obj (H, W) i32; N, P (H, W, 3) f64) of the
+    first hits; None otherwise."""
 
-    def __init__(self, fb, counts, err, passes):
+    def __init__(self, fb, counts, err, passes, denoised=None, denoised_var=None, features=None):
         self.fb, self.counts, self.err = fb, counts, err
+        self.denoised, self.denoised_var, self.features = denoised, denoised_var, features
         self.passes = list(passes)
         self.samples = int(sum(s for _, s in self.passes))
 
@@ -142,6 +146,45 @@ class Accumulator:
             out["list"] = lst[:ln.value].copy()
         return out
 
+    def features(self, stream=None):
+        """The first-hit features of the frame (pt_accum_features, computed
+        once and kept on the device): dict(tri, obj (H, W) i32 — -1 for an
+        escape; N, P (H, W, 3) f64 the hit triangle's normal and the hit
+        point, 0 for an escape)."""
+        H, W = self.height, self.width
+        _native.check(self._lib.pt_accum_features(self._h, C.c_void_p(stream or 0)), "pt_accum_features")
+        out = dict(tri=np.zeros((H, W), dtype=np.int32), obj=np.zeros((H, W), dtype=np.int32),
+                   N=np.zeros((H, W, 3), dtype=np.float64), P=np.zeros((H, W, 3), dtype=np.float64))
+        ip, dp = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+        _native.check(self._lib.pt_accum_read_features(
+            self._h, out["tri"].ctypes.data_as(ip), out["obj"].ctypes.data_as(ip),
+            out["N"].ctypes.data_as(dp), out["P"].ctypes.data_as(dp)), "pt_accum_read_features")
+        return out
+
+    def denoise_device(self, out_ptr, var_ptr=None, f64=True, stream=None, **params):
+        """The filtered frame of the present state into device buffers
+        (pt_accum_denoise_device; params: make_denoise's)."""
+        d = make_denoise(**params)
+        _native.check(self._lib.pt_accum_denoise_device(
+            self._h, C.byref(d), PT_FLAG_OUT_F64 if f64 else 0, C.c_void_p(out_ptr),
+            C.c_void_p(var_ptr or 0), C.c_void_p(stream or 0)), "pt_accum_denoise_device")
+
+    def denoise(self, f64=True, **params):
+        """(filtered frame, its variance), (H, W, 3) f64 (f32 with f64=False):
+        the edge-avoiding filter of include/pt_capi.h (pt_denoise_params) on
+        the accumulator's present moments.  S, Q, n and the list stay as
+        they are."""
+        import torch
+        H, W = self.height, self.width
+        dt = torch.float64 if f64 else torch.float32
+        dev = self.renderer.device
+        with torch.cuda.device(torch.cuda.current_device() if dev is None else int(dev)):
+            out = torch.empty((H, W, 3), dtype=dt, device="cuda")
+            var = torch.empty((H, W, 3), dtype=dt, device="cuda")
+            s = torch.cuda.current_stream().cuda_stream
+            self.denoise_device(out.data_ptr(), var.data_ptr(), f64, s, **params)
+            return out.cpu().numpy(), var.cpu().numpy()
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.pt_accum_destroy(self._h)
@@ -181,14 +224,19 @@ def run_passes(acc, params, adapt, on_pass=None, max_passes=None):
 
 def render_adaptive(renderer, width=None, height=None, max_spp=64, bounces=1, seed=None, rr=False,
                     rr_depth=3, tol=0.05, min_spp=8, step_spp=8, floor=0.01, force_f64=False,
-                    on_pass=None, megakernel=False):
+                    on_pass=None, megakernel=False, denoise=None):
     """Render until err <= tol everywhere or a pixel has max_spp samples.
 
     renderer: a render.Renderer.  on_pass(i, n_active, samples_added) after
     each pass.  megakernel=True: scenes with a BVH take their passes through
     the single kernel instead of the wavefront kernels (the same result, bit
-    for bit).  Returns an AdaptiveResult."""
+    for bit).  denoise: None, True (the default filter) or a dict of
+    make_denoise's parameters — the result then also holds the filtered
+    frame, its variance and the first-hit features (Accumulator.denoise).
+    Returns an AdaptiveResult."""
     check_rule(tol, max_spp, min_spp, step_spp, floor)
+    if denoise is not None and denoise is not True and not isinstance(denoise, dict):
+        raise ValueError("denoise: None, True or a dict of filter parameters")
     width = int(renderer.scene.width if width is None else width)
     height = int(renderer.scene.height if height is None else height)
     seed = renderer.scene.seed if seed is None else seed
@@ -200,6 +248,10 @@ def render_adaptive(renderer, width=None, height=None, max_spp=64, bounces=1, se
     with Accumulator(renderer, width, height) as acc:
         passes = run_passes(acc, params, adapt, on_pass)
         d = acc.read(S=True, n=True, err=True)
+        den = var = feat = None
+        if denoise is not None:
+            den, var = acc.denoise(**(denoise if isinstance(denoise, dict) else {}))
+            feat = acc.features()
     n = d["n"]
     fb = np.where(n[..., None] > 0, d["S"] / np.maximum(n, 1)[..., None], 0.0)
-    return AdaptiveResult(fb, n, d["err"], passes)
+    return AdaptiveResult(fb, n, d["err"], passes, den, var, feat)

@@ -23,6 +23,7 @@
 #include "pt_prepare.h"
 #include "pt_image.h"
 #include "pt_ingest.h"
+#include "pt_denoise.h"
 
 using namespace pt;
 
@@ -1472,6 +1473,12 @@ struct pt_accum {
     bool list_valid = false;
     AccumMeta list_meta{};
     pt_adapt_params list_params{};
+    // denoising (pt_accum_features / pt_accum_denoise_device), allocated at
+    // first use: the first-hit features and the filter's two (c, v) frames
+    int32_t *f_tri = nullptr, *f_obj = nullptr;
+    double *f_N = nullptr, *f_P = nullptr;
+    bool features_valid = false;
+    double* dn[4] = {nullptr, nullptr, nullptr, nullptr};   // c, v of frame A; c, v of frame B
 };
 
 static int check_adapt(const pt_adapt_params* a, AdaptK* A) {
@@ -1510,7 +1517,8 @@ void pt_accum_destroy(pt_accum* a) {
     {
         DeviceGuard g(a->scene->device);
         if (a->stream) (void)hipStreamSynchronize(a->stream);
-        void* bufs[] = {a->S, a->Q, a->err, a->n, a->list, a->bcount, a->meta, a->home};
+        void* bufs[] = {a->S, a->Q, a->err, a->n, a->list, a->bcount, a->meta, a->home,
+                        a->f_tri, a->f_obj, a->f_N, a->f_P, a->dn[0], a->dn[1], a->dn[2], a->dn[3]};
         for (void* b : bufs)
             if (b) (void)hipFree(b);
         if (a->stream) (void)hipStreamDestroy(a->stream);
@@ -1731,6 +1739,265 @@ int pt_accum_read(pt_accum* a, double* S, double* Q, uint32_t* n, double* err, u
         }
     }
     return PT_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------ denoise --
+static int check_denoise(const pt_denoise_params* d, DenoiseK* K) {
+    if (!d) return fail(PT_EINVAL, "null denoise params");
+    if (d->iters < 1 || d->iters > 8) return fail(PT_EINVAL, "need 1 <= iters <= 8");
+    if (d->normal_sq < 0 || d->normal_sq > 8) return fail(PT_EINVAL, "need 0 <= normal_sq <= 8");
+    if (!(d->sigma_l > 0.0)) return fail(PT_EINVAL, "sigma_l must be > 0");
+    if (!(d->sigma_z > 0.0)) return fail(PT_EINVAL, "sigma_z must be > 0");
+    if (!(d->eps > 0.0)) return fail(PT_EINVAL, "eps must be > 0");
+    if (d->reserved != 0) return fail(PT_EINVAL, "reserved must be 0");
+    K->sigma_l = d->sigma_l; K->sigma_z = d->sigma_z; K->eps = d->eps;
+    K->normal_sq = d->normal_sq; K->pad = 0;
+    return PT_OK;
+}
+// pt_denoise_times: while on, a denoise records a HIP event around each of its
+// launches, waits for them and keeps the times (moments when there are any,
+// the iterations, the store).  Process-wide, like pt_test_fault_inject.
+static std::atomic<int32_t> g_dn_times_on{0};
+static std::mutex g_dn_times_mu;
+static std::vector<float> g_dn_times;
+namespace {
+struct DnTimer {
+    bool on;
+    hipStream_t st;
+    std::vector<hipEvent_t> ev;
+    DnTimer(hipStream_t s) : on(g_dn_times_on.load() != 0), st(s) { mark(); }
+    void mark() {   // an event after what was launched so far
+        if (!on) return;
+        hipEvent_t e = nullptr;
+        if (hipEventCreate(&e) != hipSuccess) { on = false; return; }
+        ev.push_back(e);
+        (void)hipEventRecord(e, st);
+    }
+    ~DnTimer() {
+        if (!ev.empty() && hipEventSynchronize(ev.back()) == hipSuccess) {
+            std::vector<float> t;
+            for (size_t i = 1; i < ev.size(); ++i) {
+                float ms = 0.f;
+                (void)hipEventElapsedTime(&ms, ev[i - 1], ev[i]);
+                t.push_back(ms);
+            }
+            std::lock_guard<std::mutex> g(g_dn_times_mu);
+            g_dn_times.swap(t);
+        }
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
+};
+}  // namespace
+// The iterations and the final store.  (c, v): the input frame, which may be
+// frame A of `buf` (the accumulator's moments) — the first iteration then
+// writes frame B; src and dst of a launch are never the same frame.
+static int denoise_launch(int32_t W, int32_t H, const DenoiseK& K, int32_t iters, const double* c,
+                          const double* v, const int32_t* obj, const double* N, const double* P,
+                          double* const buf[4], uint32_t flags, void* out, void* out_var,
+                          hipStream_t st, DnTimer* tm) {
+    const uint32_t npix = (uint32_t)((int64_t)W * H);
+    const dim3 grid((npix + kDnBlock - 1u) / kDnBlock), block(kDnBlock);
+    int dst = c == buf[0] ? 1 : 0;
+    for (int32_t i = 0; i < iters; ++i) {
+        hipLaunchKernelGGL(k_denoise_iter, grid, block, 0, st, W, H, npix, (int32_t)1 << i, K, c, v, obj, N, P,
+                           buf[2 * dst], buf[2 * dst + 1]);
+        tm->mark();
+        c = buf[2 * dst];
+        v = buf[2 * dst + 1];
+        dst ^= 1;
+    }
+    const uint64_t n3 = (uint64_t)npix * 3u;
+    const dim3 sgrid((unsigned)((n3 + kDnBlock - 1u) / kDnBlock));
+    if (flags & PT_FLAG_OUT_F64)
+        hipLaunchKernelGGL(k_denoise_store<double>, sgrid, block, 0, st, c, v, n3, (double*)out, (double*)out_var);
+    else
+        hipLaunchKernelGGL(k_denoise_store<float>, sgrid, block, 0, st, c, v, n3, (float*)out, (float*)out_var);
+    tm->mark();
+    HIPCHK(hipGetLastError());
+    return PT_OK;
+}
+static int check_frame(int32_t width, int32_t height) {
+    if (width <= 0 || height <= 0) return fail(PT_EINVAL, "need width, height > 0");
+    if ((int64_t)width * height >= (int64_t)1 << 30) return fail(PT_EINVAL, "frame too large (2^30 pixels or more)");
+    return PT_OK;
+}
+// the features of the accumulator's frame, once (accum_begin was called)
+static int accum_features_launch(pt_accum* a, hipStream_t st) {
+    if (a->features_valid) return PT_OK;
+    const size_t np = a->npix;
+    if (!a->f_tri) {
+        const bool ok = hipMalloc((void**)&a->f_tri, np * sizeof(int32_t)) == hipSuccess &&
+                        hipMalloc((void**)&a->f_obj, np * sizeof(int32_t)) == hipSuccess &&
+                        hipMalloc((void**)&a->f_N, np * 3 * sizeof(double)) == hipSuccess &&
+                        hipMalloc((void**)&a->f_P, np * 3 * sizeof(double)) == hipSuccess;
+        if (!ok) {
+            for (void** b : {(void**)&a->f_tri, (void**)&a->f_obj, (void**)&a->f_N, (void**)&a->f_P}) {
+                if (*b) (void)hipFree(*b);
+                *b = nullptr;
+            }
+            return fail(PT_ENOMEM, "hipMalloc features");
+        }
+    }
+    pt_scene* s = a->scene;
+    const dim3 grid((a->npix + 255u) / 256u), block(256);
+    if (s->dev.n_bnode > 0)
+        hipLaunchKernelGGL((k_features<true>), grid, block, 0, st, s->dev, a->W, a->H, a->npix, a->f_tri, a->f_obj,
+                           a->f_N, a->f_P);
+    else
+        hipLaunchKernelGGL((k_features<false>), grid, block, 0, st, s->dev, a->W, a->H, a->npix, a->f_tri, a->f_obj,
+                           a->f_N, a->f_P);
+    HIPCHK(hipGetLastError());
+    a->features_valid = true;
+    return PT_OK;
+}
+
+extern "C" {
+
+int pt_denoise_device(int32_t width, int32_t height, const pt_denoise_params* params, const double* c,
+                      const double* v, const int32_t* obj, const double* N, const double* P, uint32_t flags,
+                      void* out_rgb, void* out_var, void* stream) {
+    int rc = check_frame(width, height);
+    if (rc) return rc;
+    DenoiseK K;
+    rc = check_denoise(params, &K);
+    if (rc) return rc;
+    if (!c || !v || !obj || !N || !P || !out_rgb) return fail(PT_EINVAL, "null buffer");
+    if (flags & ~(uint32_t)PT_FLAG_OUT_F64) return fail(PT_EINVAL, "denoise takes PT_FLAG_OUT_F64 only");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t frame = (size_t)width * height * 3 * sizeof(double);
+    double* scratch = nullptr;
+    // one frame pair when a single iteration never reads what it wrote
+    const int frames = params->iters > 1 ? 4 : 2;
+    if (hipMallocAsync((void**)&scratch, frame * frames, st) != hipSuccess)
+        return fail(PT_ENOMEM, "hipMallocAsync denoise scratch");
+    double* buf[4] = {scratch, scratch + frame / sizeof(double), nullptr, nullptr};
+    if (frames == 4) {
+        buf[2] = scratch + 2 * (frame / sizeof(double));
+        buf[3] = scratch + 3 * (frame / sizeof(double));
+    }
+    {
+        DnTimer tm(st);
+        rc = denoise_launch(width, height, K, params->iters, c, v, obj, N, P, buf, flags, out_rgb, out_var, st, &tm);
+    }
+    const hipError_t e = hipFreeAsync(scratch, st);
+    if (!rc && e != hipSuccess) rc = fail(PT_EHIP, std::string("hipFreeAsync: ") + hipGetErrorString(e));
+    return rc;
+}
+
+int pt_denoise(int32_t width, int32_t height, const pt_denoise_params* params, const double* c, const double* v,
+               const int32_t* obj, const double* N, const double* P, uint32_t flags, void* out_rgb,
+               void* out_var) {
+    int rc = check_frame(width, height);
+    if (rc) return rc;
+    DenoiseK K;
+    rc = check_denoise(params, &K);
+    if (rc) return rc;
+    if (!c || !v || !obj || !N || !P || !out_rgb) return fail(PT_EINVAL, "null buffer");
+    if (flags & ~(uint32_t)PT_FLAG_OUT_F64) return fail(PT_EINVAL, "denoise takes PT_FLAG_OUT_F64 only");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PT_ENODEV, "no HIP device");
+    const size_t np = (size_t)width * height;
+    const size_t out_bytes = np * 3 * ((flags & PT_FLAG_OUT_F64) ? sizeof(double) : sizeof(float));
+    double *d_c = nullptr, *d_v = nullptr, *d_N = nullptr, *d_P = nullptr;
+    int32_t* d_obj = nullptr;
+    void *d_out = nullptr, *d_var = nullptr;
+    rc = dev_alloc_copy(&d_c, c, np * 3);
+    if (!rc) rc = dev_alloc_copy(&d_v, v, np * 3);
+    if (!rc) rc = dev_alloc_copy(&d_N, N, np * 3);
+    if (!rc) rc = dev_alloc_copy(&d_P, P, np * 3);
+    if (!rc) rc = dev_alloc_copy(&d_obj, obj, np);
+    if (!rc && hipMalloc(&d_out, out_bytes) != hipSuccess) rc = fail(PT_ENOMEM, "hipMalloc failed");
+    if (!rc && out_var && hipMalloc(&d_var, out_bytes) != hipSuccess) rc = fail(PT_ENOMEM, "hipMalloc failed");
+    if (!rc) rc = pt_denoise_device(width, height, params, d_c, d_v, d_obj, d_N, d_P, flags, d_out, d_var, nullptr);
+    if (!rc) {
+        hipError_t e = hipStreamSynchronize(nullptr);
+        if (e == hipSuccess) e = hipMemcpy(out_rgb, d_out, out_bytes, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && out_var) e = hipMemcpy(out_var, d_var, out_bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(PT_EHIP, std::string("pt_denoise: ") + hipGetErrorString(e));
+    }
+    for (void* p : {(void*)d_c, (void*)d_v, (void*)d_N, (void*)d_P, (void*)d_obj, d_out, d_var})
+        if (p) (void)hipFree(p);
+    return rc;
+}
+
+int pt_denoise_times(int32_t enable, float* ms, int32_t cap, int32_t* n) {
+    if (cap < 0 || (cap > 0 && !ms)) return fail(PT_EINVAL, "bad buffer");
+    g_dn_times_on.store(enable ? 1 : 0);
+    std::lock_guard<std::mutex> g(g_dn_times_mu);
+    if (n) *n = (int32_t)g_dn_times.size();
+    for (int32_t i = 0; i < cap && i < (int32_t)g_dn_times.size(); ++i) ms[i] = g_dn_times[i];
+    return PT_OK;
+}
+
+int pt_accum_features(pt_accum* a, void* stream) {
+    if (!a) return fail(PT_EINVAL, "null accumulator");
+    if (a->features_valid) return PT_OK;
+    DeviceGuard g(a->scene->device);
+    hipStream_t st = (hipStream_t)stream;
+    int rc = accum_begin(a, st);
+    if (rc) return rc;
+    rc = accum_features_launch(a, st);
+    if (rc) return rc;
+    return accum_end(a, st);
+}
+
+int pt_accum_read_features(pt_accum* a, int32_t* tri, int32_t* obj, double* N, double* P) {
+    if (!a) return fail(PT_EINVAL, "null accumulator");
+    pt_scene* s = a->scene;
+    DeviceGuard g(s->device);
+    hipStream_t st = a->stream;
+    int rc = pt_accum_features(a, st);
+    if (rc) return rc;
+    if (s->timed) HIPCHK(hipStreamWaitEvent(st, s->ev1, 0));
+    const size_t np = a->npix;
+    if (tri) HIPCHK(hipMemcpyAsync(tri, a->f_tri, np * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (obj) HIPCHK(hipMemcpyAsync(obj, a->f_obj, np * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (N) HIPCHK(hipMemcpyAsync(N, a->f_N, np * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (P) HIPCHK(hipMemcpyAsync(P, a->f_P, np * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return PT_OK;
+}
+
+int pt_accum_denoise_device(pt_accum* a, const pt_denoise_params* params, uint32_t flags, void* out_rgb_dev,
+                            void* out_var_dev, void* stream) {
+    if (!a) return fail(PT_EINVAL, "null accumulator");
+    DenoiseK K;
+    int rc = check_denoise(params, &K);
+    if (rc) return rc;
+    if (!out_rgb_dev) return fail(PT_EINVAL, "null output");
+    if (flags & ~(uint32_t)PT_FLAG_OUT_F64) return fail(PT_EINVAL, "denoise takes PT_FLAG_OUT_F64 only");
+    rc = check_frame(a->W, a->H);
+    if (rc) return rc;
+    DeviceGuard g(a->scene->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (!a->dn[0]) {
+        const size_t frame = (size_t)a->npix * 3 * sizeof(double);
+        bool ok = true;
+        for (int i = 0; i < 4 && ok; ++i) ok = hipMalloc((void**)&a->dn[i], frame) == hipSuccess;
+        if (!ok) {
+            for (int i = 0; i < 4; ++i) {
+                if (a->dn[i]) (void)hipFree(a->dn[i]);
+                a->dn[i] = nullptr;
+            }
+            return fail(PT_ENOMEM, "hipMalloc denoise scratch");
+        }
+    }
+    rc = accum_begin(a, st);
+    if (rc) return rc;
+    rc = accum_features_launch(a, st);
+    if (rc) return rc;
+    {
+        DnTimer tm(st);
+        hipLaunchKernelGGL(k_accum_moments, dim3((a->npix + kDnBlock - 1u) / kDnBlock), dim3(kDnBlock), 0, st, a->S,
+                           a->Q, a->n, a->npix, a->dn[0], a->dn[1]);
+        tm.mark();
+        rc = denoise_launch(a->W, a->H, K, params->iters, a->dn[0], a->dn[1], a->f_obj, a->f_N, a->f_P, a->dn,
+                            flags, out_rgb_dev, out_var_dev, st, &tm);
+    }
+    if (rc) return rc;
+    return accum_end(a, st);
 }
 
 }  // extern "C"

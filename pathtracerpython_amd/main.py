@@ -11,7 +11,9 @@ one rank process per GPU, rows interleaved, one RCCL gather; launch.py),
 --chunk-spp K [--checkpoint F] (the samples in launches of K, resumable from
 F; progressive.py), --noise TOL [--min-spp N] [--step-spp K] [--save-aov P]
 (adaptive sampling to the noise target TOL with -r as the per-pixel budget;
-adaptive.py).  The
+adaptive.py), --denoise [--denoise-iters N] [--denoise-sigma S] (the
+edge-avoiding filter on the device: --out / --save-raw get the filtered
+frame; without --noise the -r samples go through the accumulator).  The
 reference's interactive 3-D viewer flags (--show-scene, --show-normals,
 --show-screen, --show-inter -> plot.py) are accepted and ignored with a
 notice: the pyqtgraph viewer is out of scope.
@@ -54,7 +56,16 @@ def setup(argv=None):
     parser.add_argument('--step-spp', type=int, default=8,
                         help='with --noise: samples a pass adds per active pixel')
     parser.add_argument('--save-aov', default=None, metavar='PREFIX',
-                        help='with --noise: write PREFIX_counts.npy and PREFIX_err.npy')
+                        help='with --noise or --denoise: write PREFIX_counts.npy, _err.npy, '
+                             '_obj.npy, _normal.npy, _point.npy, _var.npy (and _noisy.npy '
+                             'with --denoise)')
+    parser.add_argument('--denoise', default=False, action='store_true',
+                        help='filter the frame on the device (variance- and first-hit-guided '
+                             'a-trous filter); --out / --save-raw get the filtered frame')
+    parser.add_argument('--denoise-iters', type=int, default=5,
+                        help='with --denoise: iterations (stride 2^i), 1..8')
+    parser.add_argument('--denoise-sigma', type=float, default=2.0,
+                        help='with --denoise: the luminance stop in standard deviations')
     return parser.parse_args(argv)
 
 
@@ -110,9 +121,20 @@ def check_args(args):
         raise SystemExit('--checkpoint needs --chunk-spp')
     if args.chunk_spp and args.devices > 1:
         raise SystemExit('--chunk-spp runs on one device (--devices 1)')
+    if args.denoise:
+        if args.devices > 1:
+            raise SystemExit('--denoise runs on one device (--devices 1)')
+        if args.chunk_spp or args.checkpoint:
+            raise SystemExit('--denoise does not combine with --chunk-spp / --checkpoint')
+        if not 1 <= args.denoise_iters <= 8:
+            raise SystemExit('--denoise-iters: need 1 <= iters <= 8')
+        if not args.denoise_sigma > 0:
+            raise SystemExit('--denoise-sigma must be > 0')
+        if args.noise is None and args.n_rays < 2:
+            raise SystemExit('--denoise needs -r >= 2 (the variance of one sample is unknown)')
     if args.noise is None:
-        if args.save_aov:
-            raise SystemExit('--save-aov needs --noise')
+        if args.save_aov and not args.denoise:
+            raise SystemExit('--save-aov needs --noise or --denoise')
         return
     if args.chunk_spp or args.checkpoint:
         raise SystemExit('--noise does not combine with --chunk-spp / --checkpoint')
@@ -152,19 +174,34 @@ def main(argv=None):
         return finish(args, arr, fb)
     with Renderer(scene) as r:
         chunks = []
-        if args.noise is not None:   # adaptive sampling (adaptive.py)
+        if args.noise is not None or args.denoise:   # through the accumulator (adaptive.py)
             from .render import image_u8
-            res = r.render_adaptive(W, H, args.n_rays, args.n_bounces, args.seed, args.rr,
-                                    tol=args.noise, min_spp=min(args.min_spp, args.n_rays),
-                                    step_spp=args.step_spp)
-            fb = res.fb
+            dn = dict(iters=args.denoise_iters, sigma_l=args.denoise_sigma) if args.denoise else None
+            if args.noise is not None:   # adaptive sampling
+                res = r.render_adaptive(W, H, args.n_rays, args.n_bounces, args.seed, args.rr,
+                                        tol=args.noise, min_spp=min(args.min_spp, args.n_rays),
+                                        step_spp=args.step_spp, denoise=dn)
+            else:   # --denoise alone: the uniform render, min_spp = max_spp = -r (also yields Q)
+                res = r.render_adaptive(W, H, args.n_rays, args.n_bounces, args.seed, args.rr,
+                                        tol=0.0, min_spp=args.n_rays, step_spp=args.n_rays, denoise=dn)
+            fb = res.denoised if args.denoise else res.fb
             arr = image_u8(fb) if W == H else None
             uniform = W * H * args.n_rays
-            print(f'adaptive: {len(res.passes)} passes, {res.samples} samples, '
-                  f'{res.samples / uniform:.3f} of the uniform budget ({uniform})')
+            if args.noise is not None:
+                print(f'adaptive: {len(res.passes)} passes, {res.samples} samples, '
+                      f'{res.samples / uniform:.3f} of the uniform budget ({uniform})')
+            if args.denoise:
+                print(f'denoise: {args.denoise_iters} iterations, sigma {args.denoise_sigma:g}')
             if args.save_aov:
                 np.save(args.save_aov + '_counts.npy', res.counts)
                 np.save(args.save_aov + '_err.npy', res.err)
+                if args.denoise:
+                    feat = res.features
+                    np.save(args.save_aov + '_obj.npy', feat['obj'])
+                    np.save(args.save_aov + '_normal.npy', feat['N'])
+                    np.save(args.save_aov + '_point.npy', feat['P'])
+                    np.save(args.save_aov + '_var.npy', res.denoised_var)
+                    np.save(args.save_aov + '_noisy.npy', res.fb)
             chunks.append(res.samples)
         elif args.chunk_spp:   # chunked, resumable (progressive.py)
             from .progressive import render_progressive

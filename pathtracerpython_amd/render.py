@@ -19,7 +19,8 @@ import numpy as np
 
 from . import _native
 from ._abi import (PT_FLAG_COUNT, PT_FLAG_FORCE_F64, PT_FLAG_KERNEL_TIMES, PT_FLAG_MEGAKERNEL,
-                   PT_FLAG_OUT_F64, PT_FLAG_RR, PT_FLAG_WALK_COUNT, PtStats, band_rows, make_params)
+                   PT_FLAG_OUT_F64, PT_FLAG_RR, PT_FLAG_WALK_COUNT, PtStats, band_rows, make_denoise,
+                   make_params)
 from .pack import pack_scene
 
 _dp = C.POINTER(C.c_double)
@@ -119,14 +120,16 @@ class Renderer:
         return (img, fb.cpu().numpy()) if return_fb else img
 
     def render_adaptive(self, width=None, height=None, max_spp=64, bounces=1, seed=None,
-                        rr=False, rr_depth=3, tol=0.05, megakernel=False, **rule):
+                        rr=False, rr_depth=3, tol=0.05, megakernel=False, denoise=None, **rule):
         """Render to the noise target `tol` within max_spp samples per pixel
         (adaptive.render_adaptive: fb, counts, err, passes, samples).
         megakernel=True: a BVH scene's passes run the single kernel instead of
-        the wavefront kernels (the same result, bit for bit)."""
+        the wavefront kernels (the same result, bit for bit).  denoise: None,
+        True or a dict of filter parameters — also the filtered frame, its
+        variance and the first-hit features."""
         from .adaptive import render_adaptive
         return render_adaptive(self, width, height, max_spp, bounces, seed, rr, rr_depth, tol,
-                               megakernel=megakernel, **rule)
+                               megakernel=megakernel, denoise=denoise, **rule)
 
     def last_kernel_ms(self):
         ms = C.c_float(0)
@@ -273,6 +276,30 @@ def image_u8(fb):
                                             PT_FLAG_OUT_F64 if fb.dtype == np.float64 else 0,
                                             C.c_void_p(out.ctypes.data)), "pt_image_u8")
     return out
+
+
+def denoise(c, v, obj, N, P, f64=True, **params):
+    """The edge-avoiding filter of include/pt_capi.h (pt_denoise_params) on
+    host arrays, computed on the GPU (pt_denoise): c, v, N, P (H, W, 3) f64 —
+    colour, variance of the mean, first-hit normal and point; obj (H, W) i32
+    (-1: an escape).  params: iters, sigma_l, sigma_z, eps, normal_sq.
+    Returns (filtered frame, its variance), f64 (f32 with f64=False)."""
+    obj = np.ascontiguousarray(obj, dtype=np.int32)
+    if obj.ndim != 2:
+        raise ValueError("obj must be (H, W)")
+    H, W = obj.shape
+    arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (c, v, N, P)]
+    if any(a.shape != (H, W, 3) for a in arrs):
+        raise ValueError("c, v, N and P must be (H, W, 3)")
+    dt = np.float64 if f64 else np.float32
+    out, var = np.zeros((H, W, 3), dtype=dt), np.zeros((H, W, 3), dtype=dt)
+    d = make_denoise(**params)
+    vp = [C.c_void_p(a.ctypes.data) for a in arrs]
+    _native.check(_native.lib().pt_denoise(W, H, C.byref(d), vp[0], vp[1], C.c_void_p(obj.ctypes.data),
+                                           vp[2], vp[3], PT_FLAG_OUT_F64 if f64 else 0,
+                                           C.c_void_p(out.ctypes.data), C.c_void_p(var.ctypes.data)),
+                  "pt_denoise")
+    return out, var
 
 
 def to_list_order(fb):
