@@ -289,6 +289,82 @@ int pt_accum_resolve_device(pt_accum* acc, uint32_t flags, void* out_rgb_dev, vo
 int pt_accum_read(pt_accum* acc, double* S, double* Q, uint32_t* n, double* err,
                   uint32_t* list, uint32_t list_cap, uint32_t* list_len);
 
+/* A band on the accumulator (v7, additive): the select, and with it every
+ * pass, is restricted to the rows pt_band_rows() names — row_begin <= iy <
+ * row_end with iy % row_step == row_phase — so that N accumulators, one per
+ * device, can each run the pass loop of their own rows with no exchange until
+ * the end (a pixel's trajectory through the passes depends on nothing but its
+ * own S, Q, n; the RNG key is (seed, pixel, sample, bounce)).  The default
+ * band is (0, height, 1, 0) with lanes_per_pixel 0: the whole frame, exactly
+ * the accumulator without a band.  The allocations stay whole-frame; only the
+ * work is restricted.
+ *
+ * Select on a band: the grid covers the band's rows*width pixels; band pixel b
+ * is (j = b / width, ix = b % width) with j counting the band's rows top-first
+ * (iy descending), so e = (height-1-iy)*width + ix ascends with b and the list
+ * stays ascending and unique.  With the default band b == e.  err is written
+ * only inside the band; a band with no rows launches nothing and selects
+ * (0, 0).
+ *
+ * lanes_per_pixel = L > 0: a pass uses
+ *     split = min(L, largest power of two <= min(kmin, 64))
+ * lanes per pixel (kmin: the smallest k of a listed pixel) instead of the
+ * library's own choice, which depends on the list's length and so on the band.
+ * Why a fixed L makes a banded run bit-identical to the whole-frame run: in a
+ * run that starts from an empty accumulator every active pixel is listed in
+ * every pass (an active pixel that is not rendered stays active), so all
+ * active pixels share one n and therefore one k = kmin — in the whole-frame
+ * run and in every band alike, pass by pass.  A fixed L then gives every pixel
+ * the same lane count, hence the same samples per lane and the same xor-order
+ * sum of the lanes' partial S and Q, wherever it is rendered.  With L = 0 the
+ * lane counts may differ between the bands and the sums agree to the sum order
+ * (~1e-15 relative); n is the same either way.
+ *
+ * pt_accum_render keeps its contract: the band and the lane count live on the
+ * accumulator, not in pt_render_params (whose row_* and lanes_per_pixel fields
+ * must stay at the whole-frame values there). */
+typedef struct pt_accum_band {
+    int32_t row_begin, row_end, row_step, row_phase;  /* the rows pt_band_rows() names */
+    int32_t lanes_per_pixel;  /* 0: chosen per pass as today; else a power of two <= 64 */
+    int32_t reserved;         /* 0 */
+} pt_accum_band;              /* 24 bytes */
+/* Requires row_step >= 1, 0 <= row_phase < row_step, 0 <= row_begin <= row_end
+ * <= height, lanes_per_pixel 0 or a power of two <= 64, reserved 0; anything
+ * else is PT_EINVAL and leaves the accumulator and its band as they were.  May
+ * be called at any time; it invalidates the last select's list and changes
+ * nothing else.  While the band's rows are not the whole frame,
+ * pt_accum_features, pt_accum_read_features and pt_accum_denoise_device return
+ * PT_EINVAL (the neighbour rows are empty); pt_accum_resolve_device and
+ * pt_accum_read work on the whole frame as ever. */
+int pt_accum_set_band(pt_accum* acc, const pt_accum_band* band);
+
+/* Band tiles: the state of a band's P = rows*width pixels as one flat buffer,
+ * the pixels top-first (ascending e), in four sections:
+ *     S    [P][3] f64  at byte 0
+ *     Q    [P][3] f64  at byte 24 P
+ *     err  [P]    f64  at byte 48 P
+ *     n    [P]    u32  at byte 56 P
+ * 60 P bytes (pt_accum_tile_bytes; rows >= 0, width > 0).  One flat buffer so
+ * that it crosses devices with a 1-D copy.
+ * pt_accum_export_band_device packs the accumulator's own band into tile_dev;
+ * pt_accum_import_band_device scatters a tile into the rows of `band` (its
+ * lanes_per_pixel is ignored), overwriting S, Q, err and n there and
+ * invalidating the list; it does not change the accumulator's own band.
+ * tile_dev is 8-byte aligned device memory of the accumulator's device.  One
+ * HBM-bound kernel each; asynchronous on `stream`, ordered on the scene handle
+ * like every accumulator launch.  One whole-frame accumulator out of N banded
+ * ones: import the tiles of bands 1..N-1 into band 0's accumulator, then set
+ * the default band — it can be read, resolved, denoised or run further. */
+int pt_accum_tile_bytes(int32_t width, int32_t rows, uint64_t* bytes);
+int pt_accum_export_band_device(pt_accum* acc, void* tile_dev, void* stream);
+int pt_accum_import_band_device(pt_accum* acc, const pt_accum_band* band,
+                                const void* tile_dev, void* stream);
+/* The host counterpart of pt_accum_read, synchronous: whole-frame S, Q
+ * ([height*width][3] f64) and n ([height*width] u32) — all three required —
+ * replace the accumulator's; err becomes +inf everywhere and the list is
+ * invalidated.  A run continues from the written state as from its own. */
+int pt_accum_write(pt_accum* acc, const double* S, const double* Q, const uint32_t* n);
+
 /* Denoising an adaptive render on the device (additive; build extension — the
  * reference has no filter).  An edge-avoiding a-trous filter over the frame,
  * guided by the per-pixel variance of the mean (from an accumulator's S, Q, n)

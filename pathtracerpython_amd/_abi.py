@@ -60,6 +60,34 @@ def make_adapt(tol, max_spp, min_spp=8, step_spp=8, floor=0.01):
     return a
 
 
+class PtAccumBand(C.Structure):
+    """pt_accum_band (include/pt_capi.h): the rows an accumulator works on and
+    the fixed lanes per pixel of its passes."""
+    _fields_ = [("row_begin", C.c_int32), ("row_end", C.c_int32), ("row_step", C.c_int32),
+                ("row_phase", C.c_int32), ("lanes_per_pixel", C.c_int32), ("reserved", C.c_int32)]
+
+    def rows(self):
+        return (self.row_begin, self.row_end, self.row_step, self.row_phase)
+
+
+def make_band(height, row_begin=0, row_end=None, row_step=1, row_phase=0, lanes_per_pixel=0):
+    b = PtAccumBand()
+    b.row_begin, b.row_end = int(row_begin), int(height if row_end is None else row_end)
+    b.row_step, b.row_phase = int(row_step), int(row_phase)
+    b.lanes_per_pixel = int(lanes_per_pixel)
+    return b
+
+
+def band_pixels(width, height, band):
+    """numpy twin of band_pixel (pt_path.h): the whole-frame pixel indices
+    e = (height-1-iy)*width + ix of the band's pixels, band rows top-first —
+    an ascending int64 array of rows*width entries."""
+    import numpy as np
+    iy = np.array(band_rows(height, *band.rows())[::-1], dtype=np.int64)
+    e = (height - 1 - iy)[:, None] * width + np.arange(width, dtype=np.int64)[None, :]
+    return e.reshape(-1)
+
+
 class PtDenoiseParams(C.Structure):
     """pt_denoise_params (include/pt_capi.h): the filter of a denoise."""
     _fields_ = [("sigma_l", C.c_double), ("sigma_z", C.c_double), ("eps", C.c_double),

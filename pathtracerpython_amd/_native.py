@@ -7,7 +7,7 @@ raise `NativeError` — loudly, never silently.
 import ctypes as C
 import os
 
-from ._abi import PtAdaptParams, PtDenoiseParams, PtMesh, PtRenderParams, PtSceneDesc, PtStats  # noqa: F401 (PtMesh re-exported)
+from ._abi import PtAccumBand, PtAdaptParams, PtDenoiseParams, PtMesh, PtRenderParams, PtSceneDesc, PtStats  # noqa: F401 (PtMesh re-exported)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PT_HIP_LIB", os.path.join(HERE, "_lib", "libpt_hip.so"))
@@ -62,6 +62,12 @@ def _bind(lib):
         "pt_accum_resolve_device": ([vp, C.c_uint32, vp, vp], C.c_int),
         "pt_accum_read": ([vp, dp, dp, C.POINTER(C.c_uint32), dp, C.POINTER(C.c_uint32), C.c_uint32,
                            C.POINTER(C.c_uint32)], C.c_int),
+        # bands, band tiles, host restore (v7, additive)
+        "pt_accum_set_band": ([vp, C.POINTER(PtAccumBand)], C.c_int),
+        "pt_accum_tile_bytes": ([C.c_int32, C.c_int32, C.POINTER(C.c_uint64)], C.c_int),
+        "pt_accum_export_band_device": ([vp, vp, vp], C.c_int),
+        "pt_accum_import_band_device": ([vp, C.POINTER(PtAccumBand), vp, vp], C.c_int),
+        "pt_accum_write": ([vp, dp, dp, C.POINTER(C.c_uint32)], C.c_int),
         # denoising (additive)
         "pt_denoise_device": ([C.c_int32, C.c_int32, C.POINTER(PtDenoiseParams), vp, vp, vp, vp, vp,
                                C.c_uint32, vp, vp, vp], C.c_int),
@@ -88,7 +94,8 @@ EXPORTS = ("pt_api_version", "pt_last_error", "pt_build_id", "pt_test_fault_inje
            "pt_accum_create", "pt_accum_destroy", "pt_accum_reset", "pt_accum_select",
            "pt_accum_render", "pt_accum_render_stats", "pt_accum_resolve_device", "pt_accum_read",
            "pt_denoise_device", "pt_denoise", "pt_denoise_times", "pt_accum_features", "pt_accum_read_features",
-           "pt_accum_denoise_device")
+           "pt_accum_denoise_device", "pt_accum_set_band", "pt_accum_tile_bytes",
+           "pt_accum_export_band_device", "pt_accum_import_band_device", "pt_accum_write")
 
 
 def lib():

@@ -18,15 +18,26 @@ is empty.  The keyed RNG makes sample s of a pixel the same draw whichever
 pass renders it, so a pixel that stopped at n samples holds what a uniform
 render of n samples gives it (to ~1e-15 relative: the sum order).  The
 list's length is the one value the host reads per pass.
+
+A pixel's trajectory through the passes depends on nothing but its own S, Q
+and n.  So an accumulator can be restricted to a band of rows (set_band) and
+N of them, one per device, run their own pass loops with no exchange until
+the end (render.MultiRenderer.render_adaptive; band tiles move the state:
+export_band / import_band); and a run can be cut between any two passes and
+continued from its moments (AccumCheckpoint, Accumulator.write).
 """
 import ctypes as C
+import json
+import os
+import time
 import weakref
 
 import numpy as np
 
 from . import _native
-from ._abi import (PT_FLAG_FORCE_F64, PT_FLAG_MEGAKERNEL, PT_FLAG_OUT_F64, PT_FLAG_RR, PtStats,
-                   make_adapt, make_denoise, make_params)
+from ._abi import (PT_FLAG_FORCE_F64, PT_FLAG_MEGAKERNEL, PT_FLAG_OUT_F64, PT_FLAG_RR, PtAccumBand,
+                   PtStats, band_pixels, make_adapt, make_band, make_denoise, make_params)
+from .progressive import scene_fingerprint
 
 
 class AdaptiveResult:
@@ -35,10 +46,13 @@ class AdaptiveResult:
     samples_added)]; samples the total.  After a run with denoise: denoised
     (H, W, 3) f64 the filtered frame, denoised_var (H, W, 3) f64 its variance
     estimate, features dict(tri, obj (H, W) i32; N, P (H, W, 3) f64) of the
-    first hits; None otherwise."""
+    first hits; None otherwise.  After a run with moments=True: S, Q
+    (H, W, 3) f64, the sums the run ended with; None otherwise."""
 
-    def __init__(self, fb, counts, err, passes, denoised=None, denoised_var=None, features=None):
+    def __init__(self, fb, counts, err, passes, denoised=None, denoised_var=None, features=None,
+                 S=None, Q=None):
         self.fb, self.counts, self.err = fb, counts, err
+        self.S, self.Q = S, Q
         self.denoised, self.denoised_var, self.features = denoised, denoised_var, features
         self.passes = list(passes)
         self.samples = int(sum(s for _, s in self.passes))
@@ -70,10 +84,26 @@ def pass_samples(n, min_spp, max_spp, step_spp):
     return max(0, min(step_spp, goal - n))
 
 
-class Accumulator:
-    """A `pt_accum` of one (width, height) frame of a Renderer's scene."""
+def tile_bytes(width, rows):
+    """Bytes of a band tile of rows*width pixels (pt_accum_tile_bytes)."""
+    return 60 * int(rows) * int(width)
 
-    def __init__(self, renderer, width, height):
+
+def tile_sections(buf, pixels):
+    """The four sections of a band tile held in the uint8 array `buf`
+    (include/pt_capi.h): views S, Q (P, 3) f64, err (P,) f64, n (P,) u32."""
+    P = int(pixels)
+    return dict(S=buf[:24 * P].view(np.float64).reshape(P, 3),
+                Q=buf[24 * P:48 * P].view(np.float64).reshape(P, 3),
+                err=buf[48 * P:56 * P].view(np.float64), n=buf[56 * P:60 * P].view(np.uint32))
+
+
+class Accumulator:
+    """A `pt_accum` of one (width, height) frame of a Renderer's scene; band
+    (a PtAccumBand, _abi.make_band): the rows it works on and the fixed lanes
+    per pixel of its passes (default: the whole frame, chosen per pass)."""
+
+    def __init__(self, renderer, width, height, band=None):
         self._lib = renderer._lib
         self.renderer = renderer
         self.width, self.height = int(width), int(height)
@@ -86,6 +116,76 @@ class Accumulator:
         if not hasattr(renderer, "_accums"):
             renderer._accums = weakref.WeakSet()
         renderer._accums.add(self)
+        self.band = make_band(self.height)
+        if band is not None:
+            self.set_band(band)
+
+    def set_band(self, band):
+        """Restrict the selects, and so the passes, to the rows of `band`
+        (pt_accum_set_band); make_band(height) is the whole frame again."""
+        _native.check(self._lib.pt_accum_set_band(self._h, C.byref(band)), "pt_accum_set_band")
+        b = PtAccumBand()
+        C.pointer(b)[0] = band
+        self.band = b
+
+    def _device(self):
+        import torch
+        dev = self.renderer.device
+        return torch.cuda.device(torch.cuda.current_device() if dev is None else int(dev))
+
+    def export_band_device(self, ptr, stream=None):
+        """The band's tile (include/pt_capi.h: S, Q, err, n of its pixels,
+        top-first) into tile_bytes() of device memory at ptr, asynchronous."""
+        _native.check(self._lib.pt_accum_export_band_device(self._h, C.c_void_p(ptr), C.c_void_p(stream or 0)),
+                      "pt_accum_export_band_device")
+
+    def export_band(self):
+        """dict of numpy S, Q (P, 3) f64, err (P,) f64, n (P,) u32 for the P
+        pixels of the band's rows, in the order of _abi.band_pixels."""
+        import torch
+        P = len(band_pixels(self.width, self.height, self.band))
+        with self._device():
+            tile = torch.empty(max(60 * P, 8), dtype=torch.uint8, device="cuda")
+            self.export_band_device(tile.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            buf = tile.cpu().numpy()
+        return {k: v.copy() for k, v in tile_sections(buf, P).items()}
+
+    def import_band(self, band, tile, stream=None):
+        """Overwrite S, Q, err and n of the rows of `band` with a tile: a
+        device pointer (int) of this accumulator's device — asynchronous on
+        `stream` — or the dict form of export_band (copied up first).  The
+        accumulator's own band stays."""
+        if isinstance(tile, dict):
+            import torch
+            P = len(band_pixels(self.width, self.height, band))
+            buf = np.zeros(max(60 * P, 8), dtype=np.uint8)
+            sec = tile_sections(buf, P)
+            for k in ("S", "Q", "err", "n"):
+                sec[k][...] = np.asarray(tile[k]).reshape(sec[k].shape)
+            with self._device():
+                dev = torch.from_numpy(buf).cuda()
+                s = torch.cuda.current_stream().cuda_stream
+                _native.check(self._lib.pt_accum_import_band_device(
+                    self._h, C.byref(band), C.c_void_p(dev.data_ptr()), C.c_void_p(s)),
+                    "pt_accum_import_band_device")
+                torch.cuda.current_stream().synchronize()   # dev is freed on return
+            return
+        _native.check(self._lib.pt_accum_import_band_device(
+            self._h, C.byref(band), C.c_void_p(int(tile)), C.c_void_p(stream or 0)),
+            "pt_accum_import_band_device")
+
+    def write(self, S, Q, n):
+        """Replace the whole frame's S, Q (H, W, 3) f64 and n (H, W) u32
+        (pt_accum_write, synchronous): err becomes +inf, the list is dropped."""
+        H, W = self.height, self.width
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        Q = np.ascontiguousarray(Q, dtype=np.float64)
+        n = np.ascontiguousarray(n, dtype=np.uint32)
+        if S.shape != (H, W, 3) or Q.shape != (H, W, 3) or n.shape != (H, W):
+            raise ValueError("write: S, Q must be (H, W, 3) and n (H, W)")
+        dp = C.POINTER(C.c_double)
+        _native.check(self._lib.pt_accum_write(self._h, S.ctypes.data_as(dp), Q.ctypes.data_as(dp),
+                                               n.ctypes.data_as(C.POINTER(C.c_uint32))), "pt_accum_write")
 
     def reset(self, stream=None):
         _native.check(self._lib.pt_accum_reset(self._h, C.c_void_p(stream or 0)), "pt_accum_reset")
@@ -177,8 +277,7 @@ class Accumulator:
         import torch
         H, W = self.height, self.width
         dt = torch.float64 if f64 else torch.float32
-        dev = self.renderer.device
-        with torch.cuda.device(torch.cuda.current_device() if dev is None else int(dev)):
+        with self._device():
             out = torch.empty((H, W, 3), dtype=dt, device="cuda")
             var = torch.empty((H, W, 3), dtype=dt, device="cuda")
             s = torch.cuda.current_stream().cuda_stream
@@ -203,28 +302,80 @@ class Accumulator:
             pass
 
 
-def run_passes(acc, params, adapt, on_pass=None, max_passes=None):
-    """The pass loop on an accumulator (anything with select / render): select,
-    stop on an empty list, render.  Returns [(n_active, samples_added)]."""
-    passes = []
-    # every pass adds at least one sample to each listed pixel, so a run has at
-    # most max_spp passes (+1 for the closing select): a longer one is a bug
-    limit = int(adapt.max_spp) + 1 if max_passes is None else int(max_passes)
+def _pass_loop(acc, params, adapt, on_pass, limit, done=(), stop_after=None, after_pass=None):
+    """select, stop on an empty list, render — continuing the passes `done`.
+    Returns (passes, finished): finished False when stop_after passes were
+    made in this call and the list is not empty."""
+    passes = list(done)
+    made = 0
     while True:
         n_active, k = acc.select(adapt)
         if n_active == 0:
-            return passes
+            return passes, True
+        if stop_after is not None and made >= stop_after:
+            return passes, False
         if len(passes) >= limit:
             raise RuntimeError(f"adaptive run did not end within {limit} passes")
         acc.render(params, adapt)
         passes.append((int(n_active), int(k)))
+        made += 1
+        if after_pass is not None:
+            after_pass(passes)
         if on_pass is not None:
             on_pass(len(passes), int(n_active), int(k))
 
 
+def run_passes(acc, params, adapt, on_pass=None, max_passes=None):
+    """The pass loop on an accumulator (anything with select / render): select,
+    stop on an empty list, render.  Returns [(n_active, samples_added)]."""
+    # every pass adds at least one sample to each listed pixel, so a run has at
+    # most max_spp passes (+1 for the closing select): a longer one is a bug
+    limit = int(adapt.max_spp) + 1 if max_passes is None else int(max_passes)
+    return _pass_loop(acc, params, adapt, on_pass, limit)[0]
+
+
+class AccumCheckpoint:
+    """The moments of an adaptive run in one .npz file (written whole to a
+    temporary name, then renamed over the old one, as progressive.Checkpoint):
+    S, Q, n and the passes made so far.  The key is what defines a sample —
+    scene, size, bounces, seed, rr, rr_depth, lanes_per_pixel; the stop rule
+    is stored beside it but is no part of it: resuming with a lower tol or a
+    larger budget is the point of keeping moments."""
+
+    def __init__(self, path):
+        self.path = str(path)
+
+    def load(self, key):
+        """dict(S, Q, n, passes, rule) when the file holds a run with this
+        key; None when there is no file.  A file of another render is an
+        error, not a silent restart."""
+        if not os.path.exists(self.path):
+            return None
+        with np.load(self.path, allow_pickle=False) as z:
+            got = json.loads(str(z["key"]))
+            if got != key:
+                raise ValueError(f"checkpoint {self.path} belongs to another render: {got} != {key}")
+            passes = [(int(a), int(k)) for a, k in np.array(z["passes"]).reshape(-1, 2)]
+            return dict(S=np.array(z["S"], dtype=np.float64), Q=np.array(z["Q"], dtype=np.float64),
+                        n=np.array(z["n"], dtype=np.uint32), passes=passes,
+                        rule=json.loads(str(z["rule"])))
+
+    def save(self, key, rule, S, Q, n, passes):
+        tmp = self.path + ".tmp.npz"
+        np.savez(tmp, key=np.array(json.dumps(key, sort_keys=True)),
+                 rule=np.array(json.dumps(rule, sort_keys=True)), S=S, Q=Q, n=np.asarray(n, dtype=np.uint32),
+                 passes=np.array(passes, dtype=np.int64).reshape(-1, 2))
+        os.replace(tmp, self.path)
+
+    def remove(self):
+        if os.path.exists(self.path):
+            os.remove(self.path)
+
+
 def render_adaptive(renderer, width=None, height=None, max_spp=64, bounces=1, seed=None, rr=False,
                     rr_depth=3, tol=0.05, min_spp=8, step_spp=8, floor=0.01, force_f64=False,
-                    on_pass=None, megakernel=False, denoise=None):
+                    on_pass=None, megakernel=False, denoise=None, lanes_per_pixel=0, checkpoint=None,
+                    checkpoint_every=1, max_passes=None, moments=False):
     """Render until err <= tol everywhere or a pixel has max_spp samples.
 
     renderer: a render.Renderer.  on_pass(i, n_active, samples_added) after
@@ -233,10 +384,19 @@ def render_adaptive(renderer, width=None, height=None, max_spp=64, bounces=1, se
     for bit).  denoise: None, True (the default filter) or a dict of
     make_denoise's parameters — the result then also holds the filtered
     frame, its variance and the first-hit features (Accumulator.denoise).
+    lanes_per_pixel: 0 lets the library choose per pass; a fixed power of two
+    makes the moments independent of how the frame is split into bands
+    (include/pt_capi.h, pt_accum_band).  checkpoint: a path (or
+    AccumCheckpoint) to resume from and to write after every
+    checkpoint_every-th pass and at the end.  max_passes: stop after this
+    many passes in this call (returns None when passes remain, the
+    checkpoint written).  moments=True: the result also holds S and Q.
     Returns an AdaptiveResult."""
     check_rule(tol, max_spp, min_spp, step_spp, floor)
     if denoise is not None and denoise is not True and not isinstance(denoise, dict):
         raise ValueError("denoise: None, True or a dict of filter parameters")
+    if int(checkpoint_every) < 1:
+        raise ValueError("checkpoint_every must be >= 1")
     width = int(renderer.scene.width if width is None else width)
     height = int(renderer.scene.height if height is None else height)
     seed = renderer.scene.seed if seed is None else seed
@@ -245,13 +405,158 @@ def render_adaptive(renderer, width=None, height=None, max_spp=64, bounces=1, se
         (PT_FLAG_MEGAKERNEL if megakernel else 0)
     params = make_params(width, height, max_spp, bounces, seed, flags, rr_depth)
     adapt = make_adapt(tol, max_spp, min_spp, step_spp, floor)
-    with Accumulator(renderer, width, height) as acc:
-        passes = run_passes(acc, params, adapt, on_pass)
-        d = acc.read(S=True, n=True, err=True)
+    ck = checkpoint if isinstance(checkpoint, AccumCheckpoint) or checkpoint is None \
+        else AccumCheckpoint(checkpoint)
+    key = rule = state = None
+    if ck is not None:
+        key = {"scene": scene_fingerprint(renderer.packed), "width": width, "height": height,
+               "bounces": int(bounces), "seed": int(params.seed), "rr": bool(rr),
+               "rr_depth": int(rr_depth), "lanes_per_pixel": int(lanes_per_pixel)}
+        rule = {"tol": float(tol), "min_spp": int(min_spp), "max_spp": int(max_spp),
+                "step_spp": int(step_spp), "floor": float(floor)}
+        state = ck.load(key)
+        if state is not None and (state["S"].shape != (height, width, 3) or
+                                  state["Q"].shape != (height, width, 3) or
+                                  state["n"].shape != (height, width)):
+            raise ValueError(f"checkpoint state does not fit the render: {state['S'].shape}")
+    # (the whole frame; a band only to carry the fixed lane count)
+    kw = dict(band=make_band(height, lanes_per_pixel=lanes_per_pixel)) if lanes_per_pixel else {}
+    with Accumulator(renderer, width, height, **kw) as acc:
+        done = []
+        if state is not None:
+            acc.write(state["S"], state["Q"], state["n"])
+            done = state["passes"]
+
+        def save(passes):
+            m = acc.read(S=True, Q=True, n=True)
+            ck.save(key, rule, m["S"], m["Q"], m["n"], passes)
+
+        def after_pass(passes):
+            if (len(passes) - len(done)) % int(checkpoint_every) == 0:
+                save(passes)
+        # at most max_spp passes take a pixel from 0 to max_spp, whatever rule
+        # the earlier part of a resumed run followed (+1: the closing select)
+        limit = len(done) + int(adapt.max_spp) + 1
+        passes, finished = _pass_loop(acc, params, adapt, on_pass, limit, done, max_passes,
+                                      after_pass if ck is not None else None)
+        if ck is not None and (len(passes) - len(done)) % int(checkpoint_every) != 0:
+            save(passes)
+        if not finished:
+            return None
+        d = acc.read(S=True, Q=bool(moments), n=True, err=True)
         den = var = feat = None
         if denoise is not None:
             den, var = acc.denoise(**(denoise if isinstance(denoise, dict) else {}))
             feat = acc.features()
     n = d["n"]
     fb = np.where(n[..., None] > 0, d["S"] / np.maximum(n, 1)[..., None], 0.0)
-    return AdaptiveResult(fb, n, d["err"], passes, den, var, feat)
+    return AdaptiveResult(fb, n, d["err"], passes, den, var, feat,
+                          *((d["S"], d["Q"]) if moments else ()))
+
+
+def transfer_band(src, dst, band):
+    """The state of src's band (an Accumulator whose band is `band`) into the
+    same rows of dst, device to device: export into a tile on src's device,
+    one 1-D copy to dst's device (none when they share it), import."""
+    import torch
+    P = len(band_pixels(src.width, src.height, band))
+    if P == 0:
+        return
+    with src._device():
+        tile = torch.empty(60 * P, dtype=torch.uint8, device="cuda")
+        src.export_band_device(tile.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        torch.cuda.current_stream().synchronize()
+    with dst._device():
+        there = tile.to(torch.device("cuda", torch.cuda.current_device()))
+        stream = torch.cuda.current_stream()
+        stream.synchronize()   # the copy has landed
+        dst.import_band(band, there.data_ptr(), stream.cuda_stream)
+        stream.synchronize()   # before the tiles are freed
+
+
+def _drain(accs):
+    """Wait for the accumulators' devices; the time afterwards."""
+    import torch
+    for a in accs:
+        with a._device():
+            torch.cuda.synchronize()
+    return time.perf_counter()
+
+
+def render_adaptive_multi(renderers, width=None, height=None, max_spp=64, bounces=1, seed=None, rr=False,
+                          rr_depth=3, tol=0.05, min_spp=8, step_spp=8, floor=0.01, force_f64=False,
+                          on_pass=None, megakernel=False, denoise=None, lanes_per_pixel=0,
+                          moments=False, timings=None):
+    """render_adaptive on the renderers of a render.MultiRenderer (one scene
+    on N devices): device d gets a banded accumulator of the rows
+    distributed.rank_band(H, d, N) and runs its own pass loop — a round-robin
+    of select, then render, over the devices that still list pixels; the
+    render is asynchronous, so the devices work at the same time.  At the end
+    the tiles of bands 1..N-1 move into device 0's accumulator, which becomes
+    whole-frame and is read (and denoised) there.  passes[i] is the sum over
+    the devices of their pass i: the one-device run's.  With a fixed
+    lanes_per_pixel the moments are the one-device run's bit for bit, with 0
+    to the sum order (pt_accum_band).  on_pass is called once per round.
+    timings: a dict that receives passes_ms and merge_ms (wall time; the
+    devices are then drained between the two — scripts/bench_adaptive.py)."""
+    from .distributed import rank_band
+    check_rule(tol, max_spp, min_spp, step_spp, floor)
+    if denoise is not None and denoise is not True and not isinstance(denoise, dict):
+        raise ValueError("denoise: None, True or a dict of filter parameters")
+    r0 = renderers[0]
+    N = len(renderers)
+    width = int(r0.scene.width if width is None else width)
+    height = int(r0.scene.height if height is None else height)
+    seed = r0.scene.seed if seed is None else seed
+    seed = 0 if seed is None else int(seed)
+    flags = (PT_FLAG_RR if rr else 0) | (PT_FLAG_FORCE_F64 if force_f64 else 0) | \
+        (PT_FLAG_MEGAKERNEL if megakernel else 0)
+    params = make_params(width, height, max_spp, bounces, seed, flags, rr_depth)
+    adapt = make_adapt(tol, max_spp, min_spp, step_spp, floor)
+    bands = [make_band(height, *rank_band(height, d, N), lanes_per_pixel=lanes_per_pixel)
+             for d in range(N)]
+    accs = []
+    try:
+        for r, b in zip(renderers, bands):
+            accs.append(Accumulator(r, width, height, band=b))
+        rounds = []
+        live = list(range(N))
+        t0 = time.perf_counter()
+        while live:
+            if len(rounds) > int(adapt.max_spp):
+                raise RuntimeError(f"adaptive run did not end within {int(adapt.max_spp) + 1} passes")
+            still, n_sum, k_sum = [], 0, 0
+            for d in live:   # a device whose list is empty has finished: it leaves the round-robin
+                n_active, k = accs[d].select(adapt)
+                if n_active == 0:
+                    continue
+                accs[d].render(params, adapt)
+                still.append(d)
+                n_sum, k_sum = n_sum + int(n_active), k_sum + int(k)
+            live = still
+            if live:
+                rounds.append((n_sum, k_sum))
+                if on_pass is not None:
+                    on_pass(len(rounds), n_sum, k_sum)
+        acc = accs[0]
+        if timings is not None:
+            t1 = _drain(accs)
+        for d in range(1, N):
+            transfer_band(accs[d], acc, bands[d])
+        acc.set_band(make_band(height, lanes_per_pixel=lanes_per_pixel))
+        if timings is not None:
+            t2 = _drain(accs[:1])
+            timings.update(passes_ms=(t1 - t0) * 1e3, merge_ms=(t2 - t1) * 1e3)
+        # (the bands' last selects left err; the merged frame carries it)
+        m = acc.read(S=True, Q=bool(moments), n=True, err=True)
+        den = var = feat = None
+        if denoise is not None:
+            den, var = acc.denoise(**(denoise if isinstance(denoise, dict) else {}))
+            feat = acc.features()
+    finally:
+        for a in accs:
+            a.close()
+    n = m["n"]
+    fb = np.where(n[..., None] > 0, m["S"] / np.maximum(n, 1)[..., None], 0.0)
+    return AdaptiveResult(fb, n, m["err"], rounds, den, var, feat,
+                          *((m["S"], m["Q"]) if moments else ()))

@@ -508,19 +508,25 @@ struct AccumMeta {
     unsigned long long ksum;
 };
 constexpr uint32_t kSelBlock = 256;
-__device__ __forceinline__ uint32_t sel_pixel(uint32_t npix, bool* in) {
-    const uint64_t e = (uint64_t)blockIdx.x * kSelBlock + threadIdx.x;
-    *in = e < (uint64_t)npix;
-    return (uint32_t)e;
+// The select's work-item -> pixel.  Whole frame (BAND false): item b of npix
+// is pixel e = b.  Band form (BAND true): the grid covers the band's B.npix
+// pixels only, item b is band pixel b -> e = band_pixel(B, b) (pt_path.h);
+// e ascends with b, so blocks, bcount and the list keep their order.
+template <bool BAND>
+__device__ __forceinline__ uint32_t sel_pixel(uint32_t npix, const BandK& B, bool* in) {
+    const uint64_t b = (uint64_t)blockIdx.x * kSelBlock + threadIdx.x;
+    *in = b < (uint64_t)(BAND ? B.npix : npix);
+    return BAND ? (*in ? band_pixel(B, (uint32_t)b) : 0u) : (uint32_t)b;
 }
 // 1. err of every pixel, the active pixels of each block counted
+template <bool BAND>
 __global__ __launch_bounds__(kSelBlock) void k_accum_select_count(
     const double* __restrict__ accS, const double* __restrict__ accQ, const uint32_t* __restrict__ accN,
-    uint32_t npix, AdaptK A, double* __restrict__ err, uint32_t* __restrict__ bcount,
+    uint32_t npix, BandK B, AdaptK A, double* __restrict__ err, uint32_t* __restrict__ bcount,
     AccumMeta* __restrict__ meta) {
     __shared__ uint32_t wc[kSelBlock / 64];
     bool in;
-    const uint32_t e = sel_pixel(npix, &in);
+    const uint32_t e = sel_pixel<BAND>(npix, B, &in);
     bool act = false;
     uint32_t k = 0;
     if (in) {
@@ -577,12 +583,13 @@ __global__ __launch_bounds__(1024) void k_accum_select_scan(uint32_t* __restrict
     if (t == 0) meta->count = carry;
 }
 // 3. the active pixels of each block, in order, from the block's offset on
+template <bool BAND>
 __global__ __launch_bounds__(kSelBlock) void k_accum_select_scatter(
-    const double* __restrict__ err, const uint32_t* __restrict__ accN, uint32_t npix, AdaptK A,
+    const double* __restrict__ err, const uint32_t* __restrict__ accN, uint32_t npix, BandK B, AdaptK A,
     const uint32_t* __restrict__ boff, uint32_t* __restrict__ list) {
     __shared__ uint32_t wc[kSelBlock / 64];
     bool in;
-    const uint32_t e = sel_pixel(npix, &in);
+    const uint32_t e = sel_pixel<BAND>(npix, B, &in);
     const bool act = in && adapt_active(accN[e], err[e], A);
     const unsigned long long b = __ballot(act);
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
@@ -595,6 +602,52 @@ __global__ __launch_bounds__(kSelBlock) void k_accum_select_scatter(
 __global__ __launch_bounds__(256) void k_accum_reset(double* __restrict__ err, uint32_t npix) {
     const uint64_t e = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (e < (uint64_t)npix) err[e] = (double)INFINITY;
+}
+// Band tiles (include/pt_capi.h): the band's P = B.npix pixels top-first as
+// S [P][3], Q [P][3], err [P] f64 and n [P] u32.  A band row is contiguous in
+// the accumulator as in the tile (3W f64 of S and of Q, W of err and of n), so
+// one work-item moves element u < 3P of S and of Q, and the first P of them
+// also pixel u's err and n: every access is an 8- or 4-byte vector access that
+// is coalesced along the row.  HBM-bound, one read and one write of the band.
+__device__ __forceinline__ bool tile_item(const BandK& B, uint64_t* u, size_t* at3, uint32_t* e) {
+    *u = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const uint64_t P = B.npix;
+    if (*u >= 3u * P) return false;
+    const uint64_t row3 = 3u * (uint64_t)B.W;
+    const uint64_t j = *u / row3, c = *u - j * row3;
+    *at3 = (size_t)(((uint64_t)(B.H - 1 - B.iy_top) + j * (uint64_t)B.step) * row3 + c);
+    *e = *u < P ? band_pixel(B, (uint32_t)*u) : 0u;
+    return true;
+}
+__global__ __launch_bounds__(256) void k_accum_export_band(
+    const double* __restrict__ accS, const double* __restrict__ accQ, const double* __restrict__ err,
+    const uint32_t* __restrict__ accN, BandK B, double* __restrict__ tS, double* __restrict__ tQ,
+    double* __restrict__ tE, uint32_t* __restrict__ tN) {
+    uint64_t u;
+    size_t at3;
+    uint32_t e;
+    if (!tile_item(B, &u, &at3, &e)) return;
+    tS[u] = accS[at3];
+    tQ[u] = accQ[at3];
+    if (u < (uint64_t)B.npix) {
+        tE[u] = err[e];
+        tN[u] = accN[e];
+    }
+}
+__global__ __launch_bounds__(256) void k_accum_import_band(
+    const double* __restrict__ tS, const double* __restrict__ tQ, const double* __restrict__ tE,
+    const uint32_t* __restrict__ tN, BandK B, double* __restrict__ accS, double* __restrict__ accQ,
+    double* __restrict__ err, uint32_t* __restrict__ accN) {
+    uint64_t u;
+    size_t at3;
+    uint32_t e;
+    if (!tile_item(B, &u, &at3, &e)) return;
+    accS[at3] = tS[u];
+    accQ[at3] = tQ[u];
+    if (u < (uint64_t)B.npix) {
+        err[e] = tE[u];
+        accN[e] = tN[u];
+    }
 }
 // S / n (0 where n = 0) as a framebuffer of k_render's layout (the whole frame)
 __global__ __launch_bounds__(256) void k_accum_resolve(const double* __restrict__ accS,
@@ -1479,7 +1532,32 @@ struct pt_accum {
     double *f_N = nullptr, *f_P = nullptr;
     bool features_valid = false;
     double* dn[4] = {nullptr, nullptr, nullptr, nullptr};   // c, v of frame A; c, v of frame B
+    // the band the select works on (pt_accum_set_band; default: the whole
+    // frame, whose select is the whole-frame kernels') and the fixed lanes
+    // per pixel of a pass (0: choose_split)
+    BandK band{};
+    bool whole = true;
+    uint32_t lanes_per_pixel = 0;
 };
+
+// pt_accum_band -> BandK, or PT_EINVAL
+static int check_band(const pt_accum* a, const pt_accum_band* b, BandK* B) {
+    if (!b) return fail(PT_EINVAL, "null band");
+    if (b->row_step < 1) return fail(PT_EINVAL, "band: row_step must be >= 1");
+    if (b->row_phase < 0 || b->row_phase >= b->row_step) return fail(PT_EINVAL, "band: need 0 <= row_phase < row_step");
+    if (b->row_begin < 0 || b->row_end > a->H || b->row_begin > b->row_end)
+        return fail(PT_EINVAL, "band: need 0 <= row_begin <= row_end <= height");
+    const int32_t L = b->lanes_per_pixel;
+    if (L < 0 || L > 64 || (L & (L - 1)) != 0) return fail(PT_EINVAL, "band: lanes_per_pixel must be 0 or a power of two <= 64");
+    if (b->reserved != 0) return fail(PT_EINVAL, "band: reserved must be 0");
+    *B = band_make(a->W, a->H, b->row_begin, b->row_end, b->row_step, b->row_phase);
+    return PT_OK;
+}
+static int check_whole(const pt_accum* a, const char* what) {
+    if (a->whole) return PT_OK;
+    return fail(PT_EINVAL, std::string(what) + " needs the whole frame: the accumulator's band leaves rows empty "
+                                               "(pt_accum_set_band with the default band first)");
+}
 
 static int check_adapt(const pt_adapt_params* a, AdaptK* A) {
     if (!a) return fail(PT_EINVAL, "null adapt params");
@@ -1554,6 +1632,7 @@ int pt_accum_create(pt_scene* s, int32_t width, int32_t height, pt_accum** out) 
     a->W = width; a->H = height;
     a->npix = (uint32_t)((int64_t)width * height);
     a->nblocks = (uint32_t)(((uint64_t)a->npix + kSelBlock - 1) / kSelBlock);
+    a->band = band_make(width, height, 0, height, 1, 0);
     const size_t np = a->npix;
     const bool ok = hipMalloc((void**)&a->S, np * 3 * sizeof(double)) == hipSuccess &&
                     hipMalloc((void**)&a->Q, np * 3 * sizeof(double)) == hipSuccess &&
@@ -1586,12 +1665,22 @@ int pt_accum_select(pt_accum* a, const pt_adapt_params* ap, void* stream, uint32
         if (rc) return rc;
         a->list_valid = false;
         HIPCHK(hipMemsetAsync(a->meta, 0, sizeof(AccumMeta), st));
-        const dim3 grid(a->nblocks), block(kSelBlock);
-        hipLaunchKernelGGL(k_accum_select_count, grid, block, 0, st, a->S, a->Q, a->n, a->npix, A, a->err,
-                           a->bcount, a->meta);
-        hipLaunchKernelGGL(k_accum_select_scan, dim3(1), dim3(1024), 0, st, a->bcount, a->nblocks, a->meta);
-        hipLaunchKernelGGL(k_accum_select_scatter, grid, block, 0, st, a->err, a->n, a->npix, A, a->bcount,
-                           a->list);
+        // the grid: the frame's blocks, or the band's (<= the frame's: bcount fits)
+        const uint32_t nb = a->whole ? a->nblocks : (uint32_t)(((uint64_t)a->band.npix + kSelBlock - 1) / kSelBlock);
+        const dim3 grid(nb), block(kSelBlock);
+        if (a->whole) {
+            hipLaunchKernelGGL(k_accum_select_count<false>, grid, block, 0, st, a->S, a->Q, a->n, a->npix, a->band,
+                               A, a->err, a->bcount, a->meta);
+            hipLaunchKernelGGL(k_accum_select_scan, dim3(1), dim3(1024), 0, st, a->bcount, nb, a->meta);
+            hipLaunchKernelGGL(k_accum_select_scatter<false>, grid, block, 0, st, a->err, a->n, a->npix, a->band,
+                               A, a->bcount, a->list);
+        } else if (nb > 0) {   // (a band with no rows: nothing to launch, the zeroed meta is its select)
+            hipLaunchKernelGGL(k_accum_select_count<true>, grid, block, 0, st, a->S, a->Q, a->n, a->npix, a->band,
+                               A, a->err, a->bcount, a->meta);
+            hipLaunchKernelGGL(k_accum_select_scan, dim3(1), dim3(1024), 0, st, a->bcount, nb, a->meta);
+            hipLaunchKernelGGL(k_accum_select_scatter<true>, grid, block, 0, st, a->err, a->n, a->npix, a->band,
+                               A, a->bcount, a->list);
+        }
         rc = accum_end(a, st);
         if (rc) return rc;
         // the pass's one host synchronisation: the list's length (with the
@@ -1647,8 +1736,14 @@ int pt_accum_render_stats(pt_accum* a, const pt_render_params* p, const pt_adapt
     R.seed = p->seed;
     // lanes per pixel: choose_split's rule for a launch of the list's pixels
     // whose pixels take at least kmin samples
-    R.split = choose_split((uint64_t)a->npix, (uint64_t)m.count, (int32_t)std::min(kmin, 64u), bvh,
-                           min_lanes_of(s->n_cu));
+    if (a->lanes_per_pixel == 0) {
+        R.split = choose_split((uint64_t)a->npix, (uint64_t)m.count, (int32_t)std::min(kmin, 64u), bvh,
+                               min_lanes_of(s->n_cu));
+    } else {   // the band's fixed count, capped at the pass's samples (pt_accum_band)
+        uint32_t cap = 1;
+        while (cap * 2u <= std::min(kmin, 64u)) cap *= 2u;
+        R.split = std::min(a->lanes_per_pixel, cap);
+    }
     R.split_log2 = 0;
     while ((1u << R.split_log2) < R.split) ++R.split_log2;
     R.n_list = m.count;
@@ -1738,6 +1833,96 @@ int pt_accum_read(pt_accum* a, double* S, double* Q, uint32_t* n, double* err, u
             HIPCHK(hipStreamSynchronize(st));
         }
     }
+    return PT_OK;
+}
+
+int pt_accum_set_band(pt_accum* a, const pt_accum_band* band) {
+    if (!a) return fail(PT_EINVAL, "null accumulator");
+    BandK B;
+    int rc = check_band(a, band, &B);
+    if (rc) return rc;
+    a->band = B;
+    a->whole = B.npix == a->npix;   // every row: begin 0, end height, step 1
+    a->lanes_per_pixel = (uint32_t)band->lanes_per_pixel;
+    a->list_valid = false;
+    a->list_meta = AccumMeta{};
+    return PT_OK;
+}
+
+int pt_accum_tile_bytes(int32_t width, int32_t rows, uint64_t* bytes) {
+    if (!bytes) return fail(PT_EINVAL, "null output");
+    if (width <= 0 || rows < 0) return fail(PT_EINVAL, "tile: need width > 0 and rows >= 0");
+    *bytes = (uint64_t)60 * (uint64_t)rows * (uint64_t)width;
+    return PT_OK;
+}
+
+// the four sections of a tile of P pixels
+static void tile_sections(void* tile, uint64_t P, double** tS, double** tQ, double** tE, uint32_t** tN) {
+    char* t = (char*)tile;
+    *tS = (double*)t;
+    *tQ = (double*)(t + 24 * P);
+    *tE = (double*)(t + 48 * P);
+    *tN = (uint32_t*)(t + 56 * P);
+}
+
+int pt_accum_export_band_device(pt_accum* a, void* tile_dev, void* stream) {
+    if (!a) return fail(PT_EINVAL, "null accumulator");
+    const BandK B = a->band;
+    if (B.npix == 0) return PT_OK;   // no rows: an empty tile
+    if (!tile_dev || ((uintptr_t)tile_dev & 7u)) return fail(PT_EINVAL, "tile: need 8-byte aligned device memory");
+    DeviceGuard g(a->scene->device);
+    hipStream_t st = (hipStream_t)stream;
+    int rc = accum_begin(a, st);
+    if (rc) return rc;
+    double *tS, *tQ, *tE;
+    uint32_t* tN;
+    tile_sections(tile_dev, B.npix, &tS, &tQ, &tE, &tN);
+    const uint64_t blocks = (3u * (uint64_t)B.npix + 255u) / 256u;
+    hipLaunchKernelGGL(k_accum_export_band, dim3((unsigned)blocks), dim3(256), 0, st, a->S, a->Q, a->err, a->n, B,
+                       tS, tQ, tE, tN);
+    return accum_end(a, st);
+}
+
+int pt_accum_import_band_device(pt_accum* a, const pt_accum_band* band, const void* tile_dev, void* stream) {
+    if (!a) return fail(PT_EINVAL, "null accumulator");
+    BandK B;
+    int rc = check_band(a, band, &B);
+    if (rc) return rc;
+    if (B.npix == 0) return PT_OK;
+    if (!tile_dev || ((uintptr_t)tile_dev & 7u)) return fail(PT_EINVAL, "tile: need 8-byte aligned device memory");
+    DeviceGuard g(a->scene->device);
+    hipStream_t st = (hipStream_t)stream;
+    rc = accum_begin(a, st);
+    if (rc) return rc;
+    a->list_valid = false;   // n, S, Q change
+    a->list_meta = AccumMeta{};
+    double *tS, *tQ, *tE;
+    uint32_t* tN;
+    tile_sections(const_cast<void*>(tile_dev), B.npix, &tS, &tQ, &tE, &tN);
+    const uint64_t blocks = (3u * (uint64_t)B.npix + 255u) / 256u;
+    hipLaunchKernelGGL(k_accum_import_band, dim3((unsigned)blocks), dim3(256), 0, st, tS, tQ, tE, tN, B, a->S, a->Q,
+                       a->err, a->n);
+    return accum_end(a, st);
+}
+
+int pt_accum_write(pt_accum* a, const double* S, const double* Q, const uint32_t* n) {
+    if (!a) return fail(PT_EINVAL, "null accumulator");
+    if (!S || !Q || !n) return fail(PT_EINVAL, "write needs S, Q and n");
+    DeviceGuard g(a->scene->device);
+    hipStream_t st = a->stream;
+    int rc = accum_begin(a, st);
+    if (rc) return rc;
+    a->list_valid = false;
+    a->list_meta = AccumMeta{};
+    const size_t np = a->npix;
+    HIPCHK(hipMemcpyAsync(a->S, S, np * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(a->Q, Q, np * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(a->n, n, np * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(a->meta, 0, sizeof(AccumMeta), st));
+    hipLaunchKernelGGL(k_accum_reset, dim3((a->npix + 255u) / 256u), dim3(256), 0, st, a->err, a->npix);
+    rc = accum_end(a, st);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(st));
     return PT_OK;
 }
 
@@ -1933,6 +2118,7 @@ int pt_denoise_times(int32_t enable, float* ms, int32_t cap, int32_t* n) {
 
 int pt_accum_features(pt_accum* a, void* stream) {
     if (!a) return fail(PT_EINVAL, "null accumulator");
+    if (int rw = check_whole(a, "pt_accum_features")) return rw;
     if (a->features_valid) return PT_OK;
     DeviceGuard g(a->scene->device);
     hipStream_t st = (hipStream_t)stream;
@@ -1945,6 +2131,7 @@ int pt_accum_features(pt_accum* a, void* stream) {
 
 int pt_accum_read_features(pt_accum* a, int32_t* tri, int32_t* obj, double* N, double* P) {
     if (!a) return fail(PT_EINVAL, "null accumulator");
+    if (int rw = check_whole(a, "pt_accum_read_features")) return rw;
     pt_scene* s = a->scene;
     DeviceGuard g(s->device);
     hipStream_t st = a->stream;
@@ -1963,6 +2150,7 @@ int pt_accum_read_features(pt_accum* a, int32_t* tri, int32_t* obj, double* N, d
 int pt_accum_denoise_device(pt_accum* a, const pt_denoise_params* params, uint32_t flags, void* out_rgb_dev,
                             void* out_var_dev, void* stream) {
     if (!a) return fail(PT_EINVAL, "null accumulator");
+    if (int rw = check_whole(a, "pt_accum_denoise_device")) return rw;
     DenoiseK K;
     int rc = check_denoise(params, &K);
     if (rc) return rc;

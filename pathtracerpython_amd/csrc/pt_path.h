@@ -2224,4 +2224,31 @@ PT_HD uint32_t adapt_k(uint32_t n, const AdaptK& A) {
     return A.step_spp < goal - n ? A.step_spp : goal - n;
 }
 
+// A band of an accumulator's frame (include/pt_capi.h, pt_accum_band): the
+// rows row_begin <= iy < row_end with iy % row_step == row_phase, counted
+// top-first.  Band pixel b is (j = b / W, ix = b % W) of band row j, whose
+// image row is iy = iy_top - j*step; its whole-frame index e = (H-1-iy)*W + ix
+// ascends with b.  The whole frame (0, H, 1, 0) gives e == b.
+struct BandK {
+    int32_t W, H, iy_top, step;
+    uint32_t rows, npix;   // npix = rows*W
+};
+// (the arguments are valid: step >= 1, 0 <= phase < step, 0 <= begin <= end <= H)
+PT_HD BandK band_make(int32_t W, int32_t H, int32_t row_begin, int32_t row_end, int32_t row_step,
+                      int32_t row_phase) {
+    const int32_t first = row_begin + (row_phase - row_begin % row_step + row_step) % row_step;
+    const int32_t rows = first < row_end ? (row_end - 1 - first) / row_step + 1 : 0;
+    BandK B;
+    B.W = W; B.H = H; B.step = row_step;
+    B.iy_top = rows > 0 ? first + (rows - 1) * row_step : 0;
+    B.rows = (uint32_t)rows;
+    B.npix = (uint32_t)rows * (uint32_t)W;
+    return B;
+}
+PT_HD uint32_t band_pixel(const BandK& B, uint32_t b) {
+    const uint32_t j = b / (uint32_t)B.W, ix = b - j * (uint32_t)B.W;
+    const uint32_t row = (uint32_t)(B.H - 1 - B.iy_top) + j * (uint32_t)B.step;   // H-1-iy
+    return row * (uint32_t)B.W + ix;
+}
+
 }  // namespace pt

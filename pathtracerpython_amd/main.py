@@ -11,9 +11,12 @@ one rank process per GPU, rows interleaved, one RCCL gather; launch.py),
 --chunk-spp K [--checkpoint F] (the samples in launches of K, resumable from
 F; progressive.py), --noise TOL [--min-spp N] [--step-spp K] [--save-aov P]
 (adaptive sampling to the noise target TOL with -r as the per-pixel budget;
-adaptive.py), --denoise [--denoise-iters N] [--denoise-sigma S] (the
+adaptive.py; with --checkpoint F the run resumes from F and writes it after
+every pass), --denoise [--denoise-iters N] [--denoise-sigma S] (the
 edge-avoiding filter on the device: --out / --save-raw get the filtered
-frame; without --noise the -r samples go through the accumulator).  The
+frame; without --noise the -r samples go through the accumulator),
+--local-devices N (N GPUs of this process, no rank processes: interleaved row
+bands, also for --noise / --denoise; render.MultiRenderer).  The
 reference's interactive 3-D viewer flags (--show-scene, --show-normals,
 --show-screen, --show-inter -> plot.py) are accepted and ignored with a
 notice: the pyqtgraph viewer is out of scope.
@@ -46,8 +49,11 @@ def setup(argv=None):
     parser.add_argument('--chunk-spp', type=int, default=None,
                         help='render the -r samples in launches of this many (progressive.py)')
     parser.add_argument('--checkpoint', default=None,
-                        help='with --chunk-spp: .npz written after every chunk; a rerun '
-                             'resumes from it')
+                        help='with --chunk-spp: .npz written after every chunk; with --noise: '
+                             'the moments, written after every pass; a rerun resumes from it')
+    parser.add_argument('--local-devices', type=int, default=None, metavar='N',
+                        help='render on N GPUs of this process (row bands, no rank processes); '
+                             'also with --noise / --denoise')
     parser.add_argument('--noise', type=float, default=None, metavar='TOL',
                         help='adaptive sampling: stop a pixel at this relative standard error; '
                              '-r becomes the per-pixel sample budget (adaptive.py)')
@@ -117,14 +123,21 @@ def render_ranks(scene, args, W, H):
 
 def check_args(args):
     """Reject flag combinations before any rank process starts."""
-    if args.checkpoint and not args.chunk_spp:
+    if args.local_devices is not None:
+        if args.local_devices < 1:
+            raise SystemExit('--local-devices must be >= 1')
+        if args.devices > 1:
+            raise SystemExit('--local-devices does not combine with --devices > 1 (rank processes)')
+        if args.chunk_spp or args.checkpoint:
+            raise SystemExit('--local-devices does not combine with --chunk-spp / --checkpoint')
+    if args.checkpoint and not args.chunk_spp and args.noise is None:
         raise SystemExit('--checkpoint needs --chunk-spp')
     if args.chunk_spp and args.devices > 1:
         raise SystemExit('--chunk-spp runs on one device (--devices 1)')
     if args.denoise:
         if args.devices > 1:
             raise SystemExit('--denoise runs on one device (--devices 1)')
-        if args.chunk_spp or args.checkpoint:
+        if args.chunk_spp or (args.checkpoint and args.noise is None):
             raise SystemExit('--denoise does not combine with --chunk-spp / --checkpoint')
         if not 1 <= args.denoise_iters <= 8:
             raise SystemExit('--denoise-iters: need 1 <= iters <= 8')
@@ -136,7 +149,7 @@ def check_args(args):
         if args.save_aov and not args.denoise:
             raise SystemExit('--save-aov needs --noise or --denoise')
         return
-    if args.chunk_spp or args.checkpoint:
+    if args.chunk_spp:   # (--noise --checkpoint F alone: the resumable adaptive run)
         raise SystemExit('--noise does not combine with --chunk-spp / --checkpoint')
     if args.devices > 1:
         raise SystemExit('--noise runs on one device (--devices 1)')
@@ -145,6 +158,25 @@ def check_args(args):
         check_rule(args.noise, args.n_rays, min(args.min_spp, args.n_rays), args.step_spp)
     except ValueError as e:
         raise SystemExit(f'--noise: {e} (-r is max_spp)')
+
+
+def local_device_ids(n):
+    """The devices of --local-devices n: 0..n-1, all of which must exist."""
+    from ._native import device_count
+    have = device_count()
+    if n > have:
+        raise SystemExit(f'--local-devices {n} but this process sees {have} GPU(s)')
+    return list(range(n))
+
+
+def adaptive_args(args):
+    """The render_adaptive arguments of --noise / --denoise."""
+    dn = dict(iters=args.denoise_iters, sigma_l=args.denoise_sigma) if args.denoise else None
+    if args.noise is not None:   # adaptive sampling
+        return dict(tol=args.noise, min_spp=min(args.min_spp, args.n_rays), step_spp=args.step_spp,
+                    denoise=dn)
+    # --denoise alone: the uniform render, min_spp = max_spp = -r (also yields Q)
+    return dict(tol=0.0, min_spp=args.n_rays, step_spp=args.n_rays, denoise=dn)
 
 
 def main(argv=None):
@@ -172,36 +204,30 @@ def main(argv=None):
         if rank != 0:
             return None
         return finish(args, arr, fb)
+    through_accum = args.noise is not None or args.denoise   # (adaptive.py)
+    if args.local_devices is not None:   # N GPUs of this process (render.MultiRenderer)
+        from .render import MultiRenderer, image_u8
+        with MultiRenderer(scene, local_device_ids(args.local_devices)) as m:
+            if through_accum:
+                res = m.render_adaptive(W, H, args.n_rays, args.n_bounces, args.seed, args.rr,
+                                        **adaptive_args(args))
+                fb = report_adaptive(args, res, W, H)
+            else:
+                fb = m.render(W, H, args.n_rays, args.n_bounces, args.seed, args.rr, out_f64=True)
+            arr = image_u8(fb) if W == H else None
+        spp = f'up to {args.n_rays}' if args.noise is not None else f'{args.n_rays}'
+        print(f'render: {W}x{H}, {spp} spp, {args.n_bounces} bounces on {args.local_devices} '
+              f'local GPUs')
+        return finish(args, arr, fb)
     with Renderer(scene) as r:
         chunks = []
-        if args.noise is not None or args.denoise:   # through the accumulator (adaptive.py)
+        if through_accum:
             from .render import image_u8
-            dn = dict(iters=args.denoise_iters, sigma_l=args.denoise_sigma) if args.denoise else None
-            if args.noise is not None:   # adaptive sampling
-                res = r.render_adaptive(W, H, args.n_rays, args.n_bounces, args.seed, args.rr,
-                                        tol=args.noise, min_spp=min(args.min_spp, args.n_rays),
-                                        step_spp=args.step_spp, denoise=dn)
-            else:   # --denoise alone: the uniform render, min_spp = max_spp = -r (also yields Q)
-                res = r.render_adaptive(W, H, args.n_rays, args.n_bounces, args.seed, args.rr,
-                                        tol=0.0, min_spp=args.n_rays, step_spp=args.n_rays, denoise=dn)
-            fb = res.denoised if args.denoise else res.fb
+            ck = dict(checkpoint=args.checkpoint) if args.checkpoint else {}
+            res = r.render_adaptive(W, H, args.n_rays, args.n_bounces, args.seed, args.rr,
+                                    **adaptive_args(args), **ck)
+            fb = report_adaptive(args, res, W, H)
             arr = image_u8(fb) if W == H else None
-            uniform = W * H * args.n_rays
-            if args.noise is not None:
-                print(f'adaptive: {len(res.passes)} passes, {res.samples} samples, '
-                      f'{res.samples / uniform:.3f} of the uniform budget ({uniform})')
-            if args.denoise:
-                print(f'denoise: {args.denoise_iters} iterations, sigma {args.denoise_sigma:g}')
-            if args.save_aov:
-                np.save(args.save_aov + '_counts.npy', res.counts)
-                np.save(args.save_aov + '_err.npy', res.err)
-                if args.denoise:
-                    feat = res.features
-                    np.save(args.save_aov + '_obj.npy', feat['obj'])
-                    np.save(args.save_aov + '_normal.npy', feat['N'])
-                    np.save(args.save_aov + '_point.npy', feat['P'])
-                    np.save(args.save_aov + '_var.npy', res.denoised_var)
-                    np.save(args.save_aov + '_noisy.npy', res.fb)
             chunks.append(res.samples)
         elif args.chunk_spp:   # chunked, resumable (progressive.py)
             from .progressive import render_progressive
@@ -226,6 +252,28 @@ def main(argv=None):
         spp = f'up to {args.n_rays}' if args.noise is not None else f'{args.n_rays}'
         print(f'render: {W}x{H}, {spp} spp, {args.n_bounces} bounces, {last}')
     return finish(args, arr, fb)
+
+
+def report_adaptive(args, res, W, H):
+    """The lines and --save-aov files of a run through the accumulator; returns
+    the frame --out / --save-raw get."""
+    uniform = W * H * args.n_rays
+    if args.noise is not None:
+        print(f'adaptive: {len(res.passes)} passes, {res.samples} samples, '
+              f'{res.samples / uniform:.3f} of the uniform budget ({uniform})')
+    if args.denoise:
+        print(f'denoise: {args.denoise_iters} iterations, sigma {args.denoise_sigma:g}')
+    if args.save_aov:
+        np.save(args.save_aov + '_counts.npy', res.counts)
+        np.save(args.save_aov + '_err.npy', res.err)
+        if args.denoise:
+            feat = res.features
+            np.save(args.save_aov + '_obj.npy', feat['obj'])
+            np.save(args.save_aov + '_normal.npy', feat['N'])
+            np.save(args.save_aov + '_point.npy', feat['P'])
+            np.save(args.save_aov + '_var.npy', res.denoised_var)
+            np.save(args.save_aov + '_noisy.npy', res.fb)
+    return res.denoised if args.denoise else res.fb
 
 
 def finish(args, arr, fb):

@@ -126,7 +126,9 @@ class Renderer:
         megakernel=True: a BVH scene's passes run the single kernel instead of
         the wavefront kernels (the same result, bit for bit).  denoise: None,
         True or a dict of filter parameters — also the filtered frame, its
-        variance and the first-hit features."""
+        variance and the first-hit features.  rule: min_spp, step_spp, floor,
+        force_f64, on_pass, and lanes_per_pixel, checkpoint, checkpoint_every,
+        max_passes (a fixed lane count; a resumable run)."""
         from .adaptive import render_adaptive
         return render_adaptive(self, width, height, max_spp, bounces, seed, rr, rr_depth, tol,
                                megakernel=megakernel, denoise=denoise, **rule)
@@ -241,6 +243,22 @@ class MultiRenderer:
                                               C.c_void_p(out.ctypes.data), C.byref(st)),
                       "pt_render_multi")
         return (out, st.as_dict()) if stats else out
+
+    def render_adaptive(self, width=None, height=None, max_spp=64, bounces=1, seed=None,
+                        rr=False, rr_depth=3, tol=0.05, megakernel=False, denoise=None, **rule):
+        """Renderer.render_adaptive over the devices (no checkpointing): one
+        banded accumulator per device, each running the pass loop of its own
+        interleaved rows; the bands' tiles are merged on the first device,
+        which also runs the denoise (adaptive.render_adaptive_multi).  With a
+        fixed lanes_per_pixel the result is the one-device run's bit for bit."""
+        from . import adaptive
+        for k in ("checkpoint", "checkpoint_every", "max_passes"):
+            if k in rule:
+                raise ValueError(f"MultiRenderer.render_adaptive does not take {k}: a multi-device "
+                                 "run is not checkpointed")
+        return adaptive.render_adaptive_multi(self.renderers, width, height, max_spp, bounces, seed,
+                                              rr, rr_depth, tol, megakernel=megakernel,
+                                              denoise=denoise, **rule)
 
     def close(self):
         for r in self.renderers:

@@ -17,6 +17,12 @@ The K2 shape: Cornell 512x512, 4 bounces, seed 9, budget 64 samples per pixel.
      (megakernel=True) and the uniform wavefront render — (i) one pass of 64,
      (ii) 8 passes of 8, (iii) whole runs at tol 0.05 and 0.02 (min 8, step 8):
      samples, passes, wall time.  Written to its own document (--out).
+  d  row bands (--parts d [--parent-root DIR]; its own document): (a) the part-b
+     tol-0.05 run on this build and on the parent commit's (DIR: a built copy
+     of its package and include/) in alternating child processes of one
+     command, --rounds rounds each; (b) MultiRenderer.render_adaptive on [0], [0, 0], [0]*4 (and on all
+     GPUs when there are several): wall time of the run and of the merge;
+     (c) the export and import kernels on one band of 8 of a 4096 x 4096 frame
 Reads none of bench.py's artifacts.  Times are medians over --reps rounds
 after --warmup rounds, with min and max."""
 import argparse
@@ -153,17 +159,144 @@ def part_c(args):
     return res
 
 
+def cornell_scene():
+    from pathtracerpython_amd import scene_reader
+    scene_reader.VERBOSE = False
+    return scene_reader.Scene(os.path.join(ROOT, "scenes", "cornell", "cornellroom.sdl"))
+
+
+def part_d_child(args):
+    """One process of part d (a): the tol-0.05 K2 run, wall ms of each rep."""
+    import torch
+    from pathtracerpython_amd import _native
+    from pathtracerpython_amd._abi import make_adapt
+    from pathtracerpython_amd.adaptive import Accumulator, run_passes
+    from pathtracerpython_amd.render import Renderer
+    adapt = make_adapt(0.05, BUDGET, 8, 8, 0.01)
+    walls = []
+    with Renderer(cornell_scene()) as r, Accumulator(r, W, H) as acc:
+        p = r.params(W, H, BUDGET, BOUNCES, SEED)
+        for i in range(args.warmup + args.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            acc.reset()
+            passes = run_passes(acc, p, adapt)
+            torch.cuda.synchronize()
+            if i >= args.warmup:
+                walls.append((time.perf_counter() - t0) * 1e3)
+        total = int(acc.read(n=True)["n"].sum())
+    return {"build_id": _native.build_id(), "wall_ms": walls, "samples": total, "passes": len(passes)}
+
+
+def part_d(args):
+    import subprocess
+
+    import torch
+    from pathtracerpython_amd import _native
+    from pathtracerpython_amd._abi import make_band
+    from pathtracerpython_amd.adaptive import Accumulator, tile_bytes
+    from pathtracerpython_amd.render import MultiRenderer, Renderer
+    res = {"shape": {"width": W, "height": H, "bounces": BOUNCES, "seed": SEED, "budget": BUDGET,
+                     "tol": 0.05, "min_spp": 8, "step_spp": 8},
+           "build_id": _native.build_id(), "device": torch.cuda.get_device_name(0),
+           "gpus": torch.cuda.device_count()}
+    # (a) this build beside the parent's, alternating child processes
+    if args.parent_root:
+        def child(root):
+            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--parts", "d_child", "--reps", "3",
+                                  "--warmup", "2"] + (["--root", root] if root else []),
+                                 capture_output=True, text=True, timeout=120)
+            if out.returncode != 0:
+                raise SystemExit(f"part d child ({root or 'this build'}) failed:\n{out.stderr[-2000:]}")
+            return json.loads(out.stdout.strip().splitlines()[-1])
+        rows = {"parent": [], "new": []}
+        ids = {}
+        for _ in range(args.rounds):
+            for name, root in (("parent", os.path.abspath(args.parent_root)), ("new", None)):
+                c = child(root)
+                ids[name] = (c["build_id"], c["samples"], c["passes"])
+                rows[name].append(statistics.median(c["wall_ms"]))
+        a = {name: {"build_id": ids[name][0], "samples": ids[name][1], "passes": ids[name][2],
+                    "round_median_wall_ms": stat(rows[name])} for name in rows}
+        a["new_median_inside_parent_spread"] = bool(
+            a["parent"]["round_median_wall_ms"]["min"] <= a["new"]["round_median_wall_ms"]["median"]
+            <= a["parent"]["round_median_wall_ms"]["max"])
+        res["one_accumulator_vs_parent"] = a
+    else:
+        res["one_accumulator_vs_parent"] = "not measured: no --parent-root"
+    # (b) bands on one GPU serialise: the price of the extra selects and the merge, no scaling
+    sc = cornell_scene()
+    kw = dict(max_spp=BUDGET, bounces=BOUNCES, seed=SEED, tol=0.05, min_spp=8, step_spp=8)
+    sets = [[0], [0, 0], [0] * 4]
+    if torch.cuda.device_count() > 1:
+        sets.append(list(range(torch.cuda.device_count())))
+    b = []
+    for ids_ in sets:
+        with MultiRenderer(sc, ids_) as m:
+            walls, merges, passes = [], [], []
+            for i in range(args.warmup + args.reps):
+                t = {}
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                r_ = m.render_adaptive(W, H, timings=t, **kw)
+                wall = (time.perf_counter() - t0) * 1e3
+                if i >= args.warmup:
+                    walls.append(wall)
+                    merges.append(t["merge_ms"])
+                    passes.append(t["passes_ms"])
+        b.append({"devices": ids_, "wall_ms": stat(walls), "passes_ms": stat(passes), "merge_ms": stat(merges),
+                  "samples": r_.samples, "n_passes": len(r_.passes)})
+    res["bands"] = b
+    if torch.cuda.device_count() <= 1:
+        res["n_gpu_scaling"] = "N-GPU scaling not measured"
+    # (c) the tile kernels: 4096^2, one band of 8
+    Wc = Hc = 4096
+    band = make_band(Hc, 0, Hc, 8, 0)
+    nbytes = tile_bytes(Wc, Hc // 8)
+    with Renderer(sc) as r, Accumulator(r, Wc, Hc, band=band) as acc:
+        tile = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+        s = torch.cuda.current_stream().cuda_stream
+        ms = {"export": [], "import": []}
+        for i in range(args.warmup + args.reps):
+            for name, fn in (("export", lambda: acc.export_band_device(tile.data_ptr(), s)),
+                             ("import", lambda: acc.import_band(band, tile.data_ptr(), s))):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                if i >= args.warmup:
+                    ms[name].append(e0.elapsed_time(e1))
+    peak = 6.29e12   # the measured copy rate of the device (DESIGN.md §5), bytes/s
+    res["tile_kernels"] = {"width": Wc, "height": Hc, "band": [0, Hc, 8, 0], "pixels": Wc * Hc // 8,
+                           "tile_bytes": nbytes}
+    for name in ms:
+        med = statistics.median(ms[name])
+        res["tile_kernels"][name] = {"ms": stat(ms[name]), "bytes_moved": 2 * nbytes,
+                                     "share_of_copy_rate": 2 * nbytes / (med * 1e-3) / peak}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parts", default="a,b")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=10, help="part d (a): child processes per build")
+    ap.add_argument("--parent-root", default=None,
+                    help="part d (a): a directory with the parent commit's built package and include/")
+    ap.add_argument("--root", default=None, help="(part d's children) import the package from here")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.root:
+        sys.path.insert(0, os.path.abspath(args.root))
     import torch
     torch.cuda.set_device(0)
-    if args.parts == "c":   # the K5 shape: a document of its own
-        text = json.dumps(part_c(args), indent=1)
+    if args.parts == "d_child":
+        print(json.dumps(part_d_child(args)))
+        return
+    if args.parts in ("c", "d"):   # documents of their own
+        text = json.dumps((part_c if args.parts == "c" else part_d)(args), indent=1)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as f:
