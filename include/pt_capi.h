@@ -63,6 +63,40 @@ extern "C" {
 /* bit 7: reserved (v4's PT_FLAG_TREE_WALK, retired in v5 with the grid-walk
    experiment it selected against; the library rejects it)                */
 #define PT_FLAG_RESERVED7 (1u << 7)
+/* Antialiasing (build extension; v7, additive): sample s of
+ * pixel k = ix*H + iy uses its own primary ray.  s is the absolute sample
+ * index: sample_begin + ... in a uniform render, n[e] + ... in an accumulator
+ * pass.
+ *  1. Jitter block: (w0, w1, ., .) = Philox4x32-10(key = seed,
+ *     ctr = (k, s, 0xFFFFFFFF, 0)).  Bounce 0xFFFFFFFF is used by no path
+ *     (bounces are non-negative int32).
+ *  2. Offsets: jx = u_of(w0) - 0.5, jy = u_of(w1) - 0.5, both in [-0.5, 0.5)
+ *     and exact in f64 (u_of(w) = (w >> 8) / 2^24).  The filter is a box one
+ *     pixel spacing wide.
+ *  3. Pixel spacing: dx = W > 1 ? (x1 - x0)/(W - 1) : 0, dy the same with H
+ *     and the y bounds (ortho = x0 y0 x1 y1).
+ *  4. Shifted window: ax = jx*dx; x0' = x0 + ax; x1' = x1 + ax; the same for
+ *     y.  Every operation is rounded on its own.
+ *  5. Primary ray: x = linspace_at(x0', x1', W, ix), y = linspace_at(y0', y1',
+ *     H, iy) (np.linspace), d0 = (x - eye.x, y - eye.y, 0 - eye.z), origin
+ *     eye; its closest hit is found as for any primary ray.
+ *  6. The rest of sample s is unchanged: the same counters (k, s, bounce,
+ *     slot>>2) and bounce loop.  A primary ray that escapes contributes 0,
+ *     one that hits the light contributes light_rgb — per sample, not per
+ *     pixel.  bounces <= 0 gives 0.
+ * So sample s of pixel k is the reference's sample s of pixel k on a scene
+ * whose ortho is (x0', y0', x1', y1'), and it depends on (seed, k, s) only:
+ * the same draw in whichever launch, pass, band or resumed run takes it.
+ * Allowed beside it: PT_FLAG_RR, PT_FLAG_FORCE_F64, PT_FLAG_OUT_F64,
+ * PT_FLAG_MEGAKERNEL; with PT_FLAG_COUNT, PT_FLAG_WALK_COUNT or
+ * PT_FLAG_KERNEL_TIMES it is PT_EINVAL.  Scenes with a BVH render through the
+ * single kernel (as with PT_FLAG_MEGAKERNEL): the wavefront kernels have no
+ * per-sample primary query yet.  An accumulator remembers the bit of its
+ * first pass since pt_accum_reset / pt_accum_create / pt_accum_write / an
+ * imported tile and refuses a pass with the other value (PT_EINVAL): mixed
+ * passes would mix two definitions of sample s.  Features and the denoiser
+ * keep the centre ray.                                                    */
+#define PT_FLAG_AA (1u << 8)
 
 /*
  * Flattened scene, as produced by scene_reader.Scene
@@ -263,10 +297,12 @@ int pt_accum_select(pt_accum* acc, const pt_adapt_params* a, void* stream,
  * row_begin 0, row_end height, row_step 1, row_phase 0, sample_begin 0,
  * out_row_stride 0, lanes_per_pixel 0, flags within PT_FLAG_RR |
  * PT_FLAG_FORCE_F64 | PT_FLAG_MEGAKERNEL | PT_FLAG_WALK_COUNT |
- * PT_FLAG_KERNEL_TIMES; anything else is PT_EINVAL.  Scenes with a BVH run
+ * PT_FLAG_KERNEL_TIMES | PT_FLAG_AA (one value of PT_FLAG_AA between resets,
+ * see the flag); anything else is PT_EINVAL.  Scenes with a BVH run
  * the pass through the wavefront kernels (shade, sort and walk steps over the
  * slots of the listed pixels) under pt_render_device's conditions, and
- * through the single kernel with PT_FLAG_MEGAKERNEL or PT_FLAG_FORCE_F64;
+ * through the single kernel with PT_FLAG_MEGAKERNEL, PT_FLAG_FORCE_F64 or
+ * PT_FLAG_AA;
  * both use the same lanes per pixel, so S, Q and n are the same bit for bit.
  * Asynchronous on `stream` (after the select's read); pt_last_kernel_ms()
  * gives the pass's kernel time. */

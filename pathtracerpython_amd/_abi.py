@@ -19,6 +19,7 @@ PT_FLAG_MEGAKERNEL = 1 << 4
 PT_FLAG_WALK_COUNT = 1 << 5
 PT_FLAG_KERNEL_TIMES = 1 << 6
 # bit 7: reserved (v4's PT_FLAG_TREE_WALK, retired in v5)
+PT_FLAG_AA = 1 << 8   # antialiasing: a jittered primary ray per sample
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)

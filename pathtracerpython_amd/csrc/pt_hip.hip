@@ -43,6 +43,7 @@ static int fail(int code, const std::string& msg) {
 // ------------------------------------------------------------- kernels --
 // k_render and its launch records: pt_render.h
 #include "pt_render.h"
+#include "pt_aa.h"   // the antialiasing kernels' launchers (pt_aa.hip)
 #if PT_K2_OWN_TU
 extern template __global__ void k_render<false, false, false>(SceneK, RenderK, void*, StatsDev*);
 #endif
@@ -1014,7 +1015,8 @@ int pt_band_rows(const pt_render_params* p, int32_t* rows) {
 }
 
 constexpr uint32_t kKnownFlags = PT_FLAG_RR | PT_FLAG_FORCE_F64 | PT_FLAG_COUNT | PT_FLAG_OUT_F64 |
-                                 PT_FLAG_MEGAKERNEL | PT_FLAG_WALK_COUNT | PT_FLAG_KERNEL_TIMES;
+                                 PT_FLAG_MEGAKERNEL | PT_FLAG_WALK_COUNT | PT_FLAG_KERNEL_TIMES |
+                                 PT_FLAG_AA;
 static int validate(const pt_render_params* p) {
     if (!p) return fail(PT_EINVAL, "null params");
     if (p->width <= 0 || p->height <= 0) return fail(PT_EINVAL, "width/height must be > 0");
@@ -1027,6 +1029,9 @@ static int validate(const pt_render_params* p) {
         return fail(PT_EINVAL, "need row_step > 0 and 0 <= row_phase < row_step");
     if (p->flags & ~kKnownFlags)
         return fail(PT_EINVAL, "unknown flag bits (bit 7, v4's PT_FLAG_TREE_WALK, is retired)");
+    if ((p->flags & PT_FLAG_AA) && (p->flags & (PT_FLAG_COUNT | PT_FLAG_WALK_COUNT | PT_FLAG_KERNEL_TIMES)))
+        return fail(PT_EINVAL, "PT_FLAG_AA does not combine with PT_FLAG_COUNT, PT_FLAG_WALK_COUNT or "
+                               "PT_FLAG_KERNEL_TIMES: the antialiasing kernels do not count");
     if (p->out_row_stride != 0 && (int64_t)p->out_row_stride < (int64_t)p->width * 3)
         return fail(PT_EINVAL, "out_row_stride must be 0 or >= width*3");
     if (p->lanes_per_pixel != 0) {
@@ -1439,13 +1444,18 @@ int pt_render_device(pt_scene* s, const pt_render_params* p, void* out_dev, void
     // only the single kernel implements; and for launches of 2^29 or more
     // path slots, beyond the shadow lists' (slot << 2) | ray entries — the
     // single kernel's framebuffer is the same bit for bit)
-    const bool wavefront = s->dev.n_bnode > 0 && !count && !f64 &&
+    // (and for antialiased launches: the wavefront kernels have no per-sample
+    // primary query)
+    const bool aa = (p->flags & PT_FLAG_AA) != 0;
+    const bool wavefront = s->dev.n_bnode > 0 && !count && !f64 && !aa &&
                            !(p->flags & PT_FLAG_MEGAKERNEL) && s->dev.n_qnode > 0 &&
                            s->dev.qstack <= kWalkStack && (uint64_t)grid.x * 256u < ((uint64_t)1 << 29);
     if (wavefront) return render_wavefront(s, R, nullptr, grid, out_dev, st, p->flags, stats);
     if (count) HIPCHK(hipMemsetAsync(s->stats, 0, sizeof(StatsDev), st));
     HIPCHK(hipEventRecord(s->ev0, st));
-    if (f64) {
+    if (aa) {   // (validate: never with count)
+        pt_aa_render(f64, s->dev.n_bnode > 0, rgrid, st, s->dev, R, out_dev);
+    } else if (f64) {
         if (count) hipLaunchKernelGGL((k_render<true, true, true>), rgrid, rblock, 0, st, s->dev, R, out_dev, s->stats);
         else hipLaunchKernelGGL((k_render<true, false, true>), rgrid, rblock, 0, st, s->dev, R, out_dev, s->stats);
     } else if (s->dev.n_bnode > 0) {   // scenes with meshes: the BVH instantiation
@@ -1538,6 +1548,9 @@ struct pt_accum {
     BandK band{};
     bool whole = true;
     uint32_t lanes_per_pixel = 0;
+    // PT_FLAG_AA of the passes since the last reset, write or import (-1: none
+    // yet): a pass with the other value is refused
+    int aa = -1;
 };
 
 // pt_accum_band -> BandK, or PT_EINVAL
@@ -1612,6 +1625,7 @@ int pt_accum_reset(pt_accum* a, void* stream) {
     if (rc) return rc;
     a->list_valid = false;
     a->list_meta = AccumMeta{};
+    a->aa = -1;
     HIPCHK(hipMemsetAsync(a->S, 0, (size_t)a->npix * 3 * sizeof(double), st));
     HIPCHK(hipMemsetAsync(a->Q, 0, (size_t)a->npix * 3 * sizeof(double), st));
     HIPCHK(hipMemsetAsync(a->n, 0, (size_t)a->npix * sizeof(uint32_t), st));
@@ -1715,10 +1729,14 @@ int pt_accum_render_stats(pt_accum* a, const pt_render_params* p, const pt_adapt
         return fail(PT_EINVAL, "an accumulator pass renders the whole frame: row_begin 0, row_end height, "
                                "row_step 1, sample_begin 0, out_row_stride 0, lanes_per_pixel 0");
     if (p->flags & ~(uint32_t)(PT_FLAG_RR | PT_FLAG_FORCE_F64 | PT_FLAG_MEGAKERNEL | PT_FLAG_WALK_COUNT |
-                               PT_FLAG_KERNEL_TIMES))
+                               PT_FLAG_KERNEL_TIMES | PT_FLAG_AA))
         return fail(PT_EINVAL, "unsupported flag bits: an accumulator pass takes PT_FLAG_RR, PT_FLAG_FORCE_F64, "
-                               "PT_FLAG_MEGAKERNEL, PT_FLAG_WALK_COUNT and PT_FLAG_KERNEL_TIMES only");
+                               "PT_FLAG_MEGAKERNEL, PT_FLAG_WALK_COUNT, PT_FLAG_KERNEL_TIMES and PT_FLAG_AA only");
     if (p->spp != ap->max_spp) return fail(PT_EINVAL, "spp must be the budget max_spp");
+    const bool aa = (p->flags & PT_FLAG_AA) != 0;
+    if (a->aa >= 0 && a->aa != (aa ? 1 : 0))
+        return fail(PT_EINVAL, "this accumulator's passes so far were made with the other value of PT_FLAG_AA: "
+                               "sample s would have two definitions (pt_accum_reset first)");
     pt_scene* s = a->scene;
     DeviceGuard g(s->device);
     hipStream_t st = (hipStream_t)stream;
@@ -1758,11 +1776,12 @@ int pt_accum_render_stats(pt_accum* a, const pt_render_params* p, const pt_adapt
     // list form) under pt_render_device's conditions; the same split, so S, Q
     // and n are the single kernel's bit for bit
     const uint64_t wf_blocks = (threads + 255) / 256;
-    if (bvh && !f64 && !(p->flags & PT_FLAG_MEGAKERNEL) && s->dev.n_qnode > 0 &&
+    if (bvh && !f64 && !aa && !(p->flags & PT_FLAG_MEGAKERNEL) && s->dev.n_qnode > 0 &&
         s->dev.qstack <= kWalkStack && wf_blocks * 256u < ((uint64_t)1 << 29)) {
         rc = accum_begin(a, st);
         if (rc) return rc;
         a->list_valid = false;   // the pass changes n, S, Q
+        a->aa = 0;
         WfList L;
         L.R = R;
         L.R.lanes = wf_blocks * 256u;
@@ -1784,8 +1803,11 @@ int pt_accum_render_stats(pt_accum* a, const pt_render_params* p, const pt_adapt
     rc = accum_begin(a, st);
     if (rc) return rc;
     a->list_valid = false;   // the pass changes n, S, Q
+    a->aa = aa ? 1 : 0;
     const dim3 grid((unsigned)blocks), block(kRenderBlock);
-    if (f64) {
+    if (aa) {
+        pt_aa_render_list(f64, bvh, grid, st, s->dev, R, a->list, a->S, a->Q, a->n);
+    } else if (f64) {
         hipLaunchKernelGGL((k_render_list<true, true>), grid, block, 0, st, s->dev, R, a->list, a->S, a->Q, a->n, a->home);
     } else if (bvh) {
         hipLaunchKernelGGL((k_render_list<false, true>), grid, block, 0, st, s->dev, R, a->list, a->S, a->Q, a->n, a->home);
@@ -1896,6 +1918,7 @@ int pt_accum_import_band_device(pt_accum* a, const pt_accum_band* band, const vo
     if (rc) return rc;
     a->list_valid = false;   // n, S, Q change
     a->list_meta = AccumMeta{};
+    a->aa = -1;              // (the caller vouches for the tile's samples)
     double *tS, *tQ, *tE;
     uint32_t* tN;
     tile_sections(const_cast<void*>(tile_dev), B.npix, &tS, &tQ, &tE, &tN);
@@ -1914,6 +1937,7 @@ int pt_accum_write(pt_accum* a, const double* S, const double* Q, const uint32_t
     if (rc) return rc;
     a->list_valid = false;
     a->list_meta = AccumMeta{};
+    a->aa = -1;   // (the caller vouches for the state it writes)
     const size_t np = a->npix;
     HIPCHK(hipMemcpyAsync(a->S, S, np * 3 * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(a->Q, Q, np * 3 * sizeof(double), hipMemcpyHostToDevice, st));

@@ -2251,4 +2251,217 @@ PT_HD uint32_t band_pixel(const BandK& B, uint32_t b) {
     return row * (uint32_t)B.W + ix;
 }
 
+// ------------------------------------------------------- antialiasing --
+// PT_FLAG_AA (build extension, include/pt_capi.h): sample s of
+// pixel k traces its own primary ray, the reference's ray on a screen window
+// shifted by a keyed jitter of one pixel spacing.  aa_jitter and aa_dir are
+// steps 1-2 and 3-5 of the rule; every f64 operation rounds on its own.
+PT_HD void aa_jitter(uint64_t seed, uint32_t pixel, uint32_t sample, double* jx, double* jy) {
+    uint32_t c[4];
+    rng_block(seed, pixel, sample, 0xFFFFFFFFu, 0u, c);   // a bounce no path uses
+    *jx = u_of(c[0]) - 0.5;
+    *jy = u_of(c[1]) - 0.5;
+}
+// the shifted window (x0', y0', x1', y1') of offsets (jx, jy)
+PT_HD void aa_window(const SceneK& S, int W, int H, double jx, double jy, double o[4]) {
+    const double dx = W > 1 ? (S.ortho[2] - S.ortho[0]) / (double)(W - 1) : 0.0;
+    const double dy = H > 1 ? (S.ortho[3] - S.ortho[1]) / (double)(H - 1) : 0.0;
+    const double ax = jx * dx, ay = jy * dy;
+    o[0] = S.ortho[0] + ax; o[1] = S.ortho[1] + ay;
+    o[2] = S.ortho[2] + ax; o[3] = S.ortho[3] + ay;
+}
+PT_HD D3 aa_dir(const SceneK& S, int W, int H, int ix, int iy, double jx, double jy) {
+    double o[4];
+    aa_window(S, W, H, jx, jy, o);
+    const double x = linspace_at(o[0], o[2], W, ix);
+    const double y = linspace_at(o[1], o[3], H, iy);
+    return d3(x - S.eye[0], y - S.eye[1], 0.0 - S.eye[2]);
+}
+
+// The pixel of a lane whose samples are jittered: the frame and the pixel's
+// place in it, beside LaneJob's key.
+struct AaPixel {
+    int32_t W, H, ix, iy;
+};
+
+// The restart's closest query, closest(S, eye, d0, -1, ..., eye = true) with
+// the eye-frame units tested in the render loop's unit form (PT_AA_PRIMARY_M,
+// the default: origin_q / closest_unit_m, one pair of forms for a quad and
+// the ambiguous members decided in the rare f64 block, as the loop's pass
+// over the light's units) instead of closest_unit's per-triangle form.  Both
+// are conservative filters in front of the same f64 evaluation
+// (closest_finish), so the hit and the hit point are the same bits; the unit
+// form is what tests/hostcheck's filter self-test checks on the eye's records.
+#ifndef PT_AA_PRIMARY_M
+#define PT_AA_PRIMARY_M 1
+#endif
+// The eye's origin terms of the first units (origin_q(unit_eye[u], eye)): the
+// same for every lane and sample, so a wave computes them once (pt_aa.hip
+// aa_eye_fill) into the spill rows the cached primary hit used (kSpD0 on: 5
+// rows x 64 lanes x 8 B = 80 units x 32 B) and the restart reads them back,
+// one 16-B and one 4-B broadcast read per unit instead of 9 to 15 fmaf.  t:
+// [n][8] floats (h, bo0, co0, bo1, co1, -, -, -), the values origin_q gives;
+// n = 0 (the host build): none.
+constexpr int kAaEyeCap = 80;
+struct AaEye {
+    const float* t;
+    int n;
+};
+PT_HD OriginU aa_origin(const AaEye& E, const UnitF& U, int u, F3 o32) {
+    if (u < E.n) {   // wave-uniform
+        const float* r = E.t + 8 * u;
+        OriginU O;
+        O.eh = U.eh;
+        O.eo = U.eo;
+#if PT_VCONST && defined(__HIP_DEVICE_COMPILE__)
+        asm("" : "+v"(O.eh), "+v"(O.eo));   // (as origin_q)
+#endif
+        O.h = r[0]; O.bo0 = r[1]; O.co0 = r[2]; O.bo1 = r[3]; O.co1 = r[4];
+        return O;
+    }
+    return origin_q(U, o32);
+}
+template <bool FORCE64, bool BVH>
+PT_HD int aa_closest(const SceneK& S, const AaEye& E, D3 d0, const Spill& sp, D3* P, Counters* cnt) {
+#if PT_AA_PRIMARY_M && PT_LIGHT_QUAD && PT_QUAD && PT_MARGIN
+    if (!FORCE64) {
+        const D3 eye = ld3(S.kd + kKdEye);
+        const D3 dn = unit(d0);
+        sp.put3(kSpP, eye);
+        sp.put3(kSpNd, d0);
+        const F3 o32 = to_f3(eye - ld3(S.kd + kKdCenter));
+        const F3 d32 = to_f3(dn);
+        ClosestAcc acc = closest_init();
+        for (int u = 0; u < S.n_unit; ++u) {
+            const UnitF U = S.unit_eye[u];
+            const OriginU O = aa_origin(E, U, u, o32);
+            if (closest_unit_m(U, O, U.grp == -1, d32, &acc))   // rare
+                fused_fallback<false, false, true, 2>(S, U, closest_bits_m(U, O, U.grp == -1, d32),
+                                                      nullptr, &acc, sp, cnt, nullptr);
+        }
+        if (BVH && S.n_bnode) {   // the meshes, as closest()
+            if (S.bvh_depth < kBvhStack) {
+                bvh_closest<false>(S, o32, -1, d32, &acc, sp, cnt);
+            } else {
+                ShadowSet none = {};
+                bvh_pass<false, false>(S, o32, -1, false, true, &none, d32, &acc, sp, cnt);
+            }
+        }
+        return closest_finish<false, false, BVH>(S, acc, eye, dn, P, cnt);
+    }
+#endif
+    return closest<FORCE64, false, BVH>(S, ld3(S.eye), d0, -1, sp, P, cnt, true);
+}
+
+// One jittered primary ray: sample `sample` of J.pixel.  Returns the hit as
+// closest() does and leaves the origin (the hit point) and the incoming
+// direction of bounce 0 in the homes kSpP / kSpNd when it is an object's.
+template <bool FORCE64, bool BVH>
+PT_HD int aa_primary(const SceneK& S, const LaneJob& J, const AaPixel& X, const AaEye& E,
+                     uint32_t sample, const Spill& sp, Counters* cnt) {
+    double jx, jy;
+    aa_jitter(J.seed, J.pixel, sample, &jx, &jy);
+    const D3 d0 = aa_dir(S, X.W, X.H, X.ix, X.iy, jx, jy);
+    D3 P;
+    const int t = aa_closest<FORCE64, BVH>(S, E, d0, sp, &P, cnt);
+    if (t >= 0 && t < S.n_obj_tri) {
+        sp.put3(kSpP, P);
+        sp.put3(kSpNd, d0);   // (unnormalised, as the reference holds it: main.py:191)
+    }
+    return t;
+}
+
+// LaneSched's sample order with a primary ray per sample: every sample of
+// the lane, its first included, starts by tracing its own jittered ray
+// (start()).  A sample whose primary ray escapes (0) or hits the light
+// (light_rgb) is complete at once, and start() goes on to the next one until
+// a sample lands on an object or the lane's samples run out.  The restart is
+// a closest query over the eye-frame units by the lanes whose path ended in
+// this iteration; the other lanes of the wave wait for it.
+template <bool FORCE64, bool BVH>
+struct AaSched {
+    const LaneJob& J;
+    AaPixel X;
+    AaEye E;
+    int si;
+    PT_HD uint32_t sample() const { return (uint32_t)(J.sample0 + si * J.sample_stride); }
+    PT_HD uint32_t pixel() const { return J.pixel; }
+    PT_HD bool start(const SceneK& S, const Spill& sp, int* tri, D3* acc, Counters* cnt) {
+        for (; si < J.n_samples; ++si) {
+            const int t = aa_primary<FORCE64, BVH>(S, J, X, E, sample(), sp, cnt);
+            if (t >= 0 && t < S.n_obj_tri) {
+                *tri = t;
+                return true;
+            }
+            if (t >= 0) *acc = *acc + ld3(S.kd + kKdLightRgb);   // main.py:214-215
+        }
+        return false;
+    }
+    template <bool COUNT>
+    PT_HD bool advance(const SceneK& S, bool done, const Spill& sp, int* tri, D3* acc, Counters* cnt) {
+        if (!done) return true;
+        ++si;
+        return start(S, sp, tri, acc, cnt);
+    }
+};
+
+// MomentSched's form: each complete sample's colour goes to the home.
+template <bool FORCE64, bool BVH, class Home>
+struct AaMomentSched {
+    const LaneJob& J;
+    AaPixel X;
+    AaEye E;
+    int si;
+    Home& home;
+    PT_HD uint32_t sample() const { return (uint32_t)(J.sample0 + si * J.sample_stride); }
+    PT_HD uint32_t pixel() const { return J.pixel; }
+    PT_HD bool start(const SceneK& S, const Spill& sp, int* tri, Counters* cnt) {
+        for (; si < J.n_samples; ++si) {
+            const int t = aa_primary<FORCE64, BVH>(S, J, X, E, sample(), sp, cnt);
+            if (t >= 0 && t < S.n_obj_tri) {
+                *tri = t;
+                return true;
+            }
+            home.add(t < 0 ? d3(0, 0, 0) : ld3(S.kd + kKdLightRgb));
+        }
+        return false;
+    }
+    template <bool COUNT>
+    PT_HD bool advance(const SceneK& S, bool done, const Spill& sp, int* tri, D3* acc, Counters* cnt) {
+        if (!done) return true;
+        home.add(*acc);
+        *acc = d3(0, 0, 0);
+        ++si;
+        return start(S, sp, tri, cnt);
+    }
+};
+
+// All samples of one lane with jittered primary rays; returns the SUM of the
+// sample colours (render_lane's contract; bounces <= 0: main.py:192 never
+// runs).
+template <bool FORCE64, bool BVH>
+PT_HD D3 render_lane_aa(const SceneK& S, const LaneJob& J, const AaPixel& X, const AaEye& E,
+                        const Spill& sp, Counters* cnt) {
+    D3 acc = d3(0, 0, 0);
+    if (J.n_samples <= 0 || J.bounces <= 0) return acc;
+    AaSched<FORCE64, BVH> q{J, X, E, 0};
+    int tri = -1;
+    if (q.start(S, sp, &tri, &acc, cnt)) render_loop<FORCE64, false, BVH>(S, J, tri, sp, cnt, q, &acc);
+    return acc;
+}
+// render_lane_moments' form: the lane's J.n_samples colours into `home`.
+template <bool FORCE64, bool BVH, class Home>
+PT_HD void render_lane_moments_aa(const SceneK& S, const LaneJob& J, const AaPixel& X,
+                                  const AaEye& E, const Spill& sp, Counters* cnt, Home& home) {
+    if (J.n_samples <= 0) return;
+    if (J.bounces <= 0) {
+        for (int i = 0; i < J.n_samples; ++i) home.add(d3(0, 0, 0));
+        return;
+    }
+    AaMomentSched<FORCE64, BVH, Home> q{J, X, E, 0, home};
+    int tri = -1;
+    D3 acc = d3(0, 0, 0);
+    if (q.start(S, sp, &tri, cnt)) render_loop<FORCE64, false, BVH>(S, J, tri, sp, cnt, q, &acc);
+}
+
 }  // namespace pt

@@ -115,20 +115,22 @@ def assemble_bands_device(gathered, out, stream=None):
 
 
 def render_distributed(renderer, width, height, spp=1, bounces=1, seed=None, rr=False,
-                       rr_depth=3, group=None, return_tiles=False, transport="device"):
+                       rr_depth=3, group=None, return_tiles=False, transport="device", aa=False):
     """Render `height` rows interleaved over the ranks of `group` on each
     rank's current CUDA/HIP device; returns the framebuffer (float32 numpy) on
     rank 0 and None on the other ranks.
     transport "device": each band into a device tile, one gather to rank 0
     (RCCL with the nccl backend); "host": every band straight into one shared
-    page-locked host frame (HostFrame; the ranks of one node)."""
+    page-locked host frame (HostFrame; the ranks of one node).  aa=True:
+    antialiasing (PT_FLAG_AA; the jitter is keyed by pixel and sample, so a
+    rank's band draws the rays the whole frame would)."""
     import torch
     import torch.distributed as dist
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rb, re, step, phase = rank_band(height, rank, world)
     p = renderer.params(width, height, spp, bounces, seed, rr, rr_depth, row_begin=rb,
-                        row_end=re, row_step=step, row_phase=phase)
+                        row_end=re, row_step=step, row_phase=phase, **({"aa": True} if aa else {}))
     if transport == "host":
         if return_tiles:
             raise ValueError("return_tiles needs the device transport")

@@ -16,7 +16,9 @@ every pass), --denoise [--denoise-iters N] [--denoise-sigma S] (the
 edge-avoiding filter on the device: --out / --save-raw get the filtered
 frame; without --noise the -r samples go through the accumulator),
 --local-devices N (N GPUs of this process, no rank processes: interleaved row
-bands, also for --noise / --denoise; render.MultiRenderer).  The
+bands, also for --noise / --denoise; render.MultiRenderer), --aa
+(antialiasing: a jittered primary ray per sample, PT_FLAG_AA; combines with
+every flag above; scenes with a BVH then render through the single kernel).  The
 reference's interactive 3-D viewer flags (--show-scene, --show-normals,
 --show-screen, --show-inter -> plot.py) are accepted and ignored with a
 notice: the pyqtgraph viewer is out of scope.
@@ -40,6 +42,9 @@ def setup(argv=None):
     parser.add_argument('--show-inter', default=False, action='store_true')
     parser.add_argument('--seed', type=int, default=None, help='RNG key (default: SDL seed)')
     parser.add_argument('--rr', default=False, action='store_true', help='Russian roulette')
+    parser.add_argument('--aa', default=False, action='store_true',
+                        help='antialiasing: a jittered primary ray per sample (box filter one '
+                             'pixel wide); the features and --denoise keep the centre ray')
     parser.add_argument('--size', type=int, nargs=2, metavar=('W', 'H'), default=None)
     parser.add_argument('--save-raw', default=None,
                         help='also save the float framebuffer (.npy, before normalisation)')
@@ -91,7 +96,7 @@ def render_ranks(scene, args, W, H):
     try:
         with Renderer(scene) as r:
             p = r.params(W, H, args.n_rays, args.n_bounces, args.seed, args.rr, out_f64=True,
-                         row_step=world, row_phase=rank)
+                         row_step=world, row_phase=rank, aa=args.aa)
             tile = torch.zeros((max_band_rows(H, world), W, 3), dtype=torch.float64, device="cuda")
             s = torch.cuda.current_stream().cuda_stream
             r.render_device(p, tile.data_ptr(), s)
@@ -174,9 +179,9 @@ def adaptive_args(args):
     dn = dict(iters=args.denoise_iters, sigma_l=args.denoise_sigma) if args.denoise else None
     if args.noise is not None:   # adaptive sampling
         return dict(tol=args.noise, min_spp=min(args.min_spp, args.n_rays), step_spp=args.step_spp,
-                    denoise=dn)
+                    denoise=dn, aa=args.aa)
     # --denoise alone: the uniform render, min_spp = max_spp = -r (also yields Q)
-    return dict(tol=0.0, min_spp=args.n_rays, step_spp=args.n_rays, denoise=dn)
+    return dict(tol=0.0, min_spp=args.n_rays, step_spp=args.n_rays, denoise=dn, aa=args.aa)
 
 
 def main(argv=None):
@@ -196,6 +201,9 @@ def main(argv=None):
     if args.show_scene or args.show_normals or args.show_screen or args.show_inter:
         print('note: the 3-D scene viewer (plot.py) is not part of this build; ignoring --show-*',
               file=sys.stderr)
+    if args.aa and scene_has_bvh(scene):
+        print('note: --aa renders scenes with a BVH through the single kernel (the wavefront '
+              'kernels have no per-sample primary ray yet)', file=sys.stderr)
     rank, _, world = rank_env()
     if world != args.devices:
         raise SystemExit(f'--devices {args.devices} but WORLD_SIZE={world}')
@@ -213,7 +221,8 @@ def main(argv=None):
                                         **adaptive_args(args))
                 fb = report_adaptive(args, res, W, H)
             else:
-                fb = m.render(W, H, args.n_rays, args.n_bounces, args.seed, args.rr, out_f64=True)
+                fb = m.render(W, H, args.n_rays, args.n_bounces, args.seed, args.rr, out_f64=True,
+                              aa=args.aa)
             arr = image_u8(fb) if W == H else None
         spp = f'up to {args.n_rays}' if args.noise is not None else f'{args.n_rays}'
         print(f'render: {W}x{H}, {spp} spp, {args.n_bounces} bounces on {args.local_devices} '
@@ -238,20 +247,29 @@ def main(argv=None):
                 print(f'samples {d}/{n}', flush=True)
             fb = render_progressive(r, W, H, args.n_rays, args.n_bounces, args.seed, args.rr,
                                     chunk_spp=args.chunk_spp, checkpoint=args.checkpoint,
-                                    on_chunk=progress)
+                                    on_chunk=progress, aa=args.aa)
             arr = image_u8(fb) if W == H else None
         elif W == H:   # make_image on the device (utils.py:150-161)
             arr, fb = r.render_image(W, H, spp=args.n_rays, bounces=args.n_bounces,
-                                     seed=args.seed, rr=args.rr, return_fb=True)
+                                     seed=args.seed, rr=args.rr, return_fb=True, aa=args.aa)
         else:        # the reference's placement for W != H (utils.py:154-156), on the host
             fb = r.render(W, H, spp=args.n_rays, bounces=args.n_bounces, seed=args.seed,
-                          rr=args.rr)
+                          rr=args.rr, aa=args.aa)
             arr = None
         last = f'kernel {r.last_kernel_ms():.3f} ms' if chunks or not args.chunk_spp \
             else 'all samples from the checkpoint'
         spp = f'up to {args.n_rays}' if args.noise is not None else f'{args.n_rays}'
         print(f'render: {W}x{H}, {spp} spp, {args.n_bounces} bounces, {last}')
     return finish(args, arr, fb)
+
+
+BVH_MIN_TRIS = 64   # pt_prepare.h kBvhMinTris
+
+
+def scene_has_bvh(scene):
+    """Whether the library builds a BVH for this scene: some object has at
+    least the mesh threshold of triangles (pt_prepare.h kBvhMinTris)."""
+    return any(len(o["geometry"].triangles) >= BVH_MIN_TRIS for o in scene.objects)
 
 
 def report_adaptive(args, res, W, H):

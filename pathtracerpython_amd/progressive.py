@@ -66,15 +66,29 @@ class Checkpoint:
             os.remove(self.path)
 
 
+def run_key(packed, width, height, spp, bounces, seed, rr, rr_depth, chunk_spp, aa=False):
+    """What defines a chunked run's samples and their sum order: a checkpoint
+    holds it, and a file with another key is refused.  "aa" is present only
+    when antialiasing is on, so the keys and files from before it stay valid."""
+    key = {"scene": scene_fingerprint(packed), "width": int(width), "height": int(height),
+           "spp": int(spp), "bounces": int(bounces), "seed": int(seed), "rr": bool(rr),
+           "rr_depth": int(rr_depth), "chunk_spp": int(chunk_spp)}
+    if aa:
+        key["aa"] = True
+    return key
+
+
 def render_progressive(renderer, width=None, height=None, spp=1, bounces=1, seed=None, rr=False,
                        rr_depth=3, chunk_spp=16, checkpoint=None, max_chunks=None,
-                       on_chunk=None):
+                       on_chunk=None, aa=False):
     """Render `spp` samples per pixel in launches of `chunk_spp`.
 
     renderer: a render.Renderer.  checkpoint: a path (or Checkpoint) to
     resume from and write after each chunk.  max_chunks: stop after this many
     chunks in this call (the run is then incomplete: returns None).
-    on_chunk(done, spp): progress callback after each chunk.
+    on_chunk(done, spp): progress callback after each chunk.  aa=True:
+    antialiasing (a jittered primary ray per sample, keyed by the absolute
+    sample index: chunks and resumed runs draw the same rays as one launch).
     Returns the framebuffer (H, W, 3) float64 — the mean over all samples —
     once every sample is done."""
     spp, chunk_spp = int(spp), int(chunk_spp)
@@ -82,9 +96,7 @@ def render_progressive(renderer, width=None, height=None, spp=1, bounces=1, seed
         raise ValueError("spp and chunk_spp must be >= 1")
     p0 = renderer.params(width, height, spp, bounces, seed, rr, rr_depth, out_f64=True)
     W, H = p0.width, p0.height
-    key = {"scene": scene_fingerprint(renderer.packed), "width": W, "height": H, "spp": spp,
-           "bounces": int(bounces), "seed": int(p0.seed), "rr": bool(rr),
-           "rr_depth": int(rr_depth), "chunk_spp": chunk_spp}
+    key = run_key(renderer.packed, W, H, spp, bounces, p0.seed, rr, rr_depth, chunk_spp, aa)
     ck = checkpoint if isinstance(checkpoint, Checkpoint) or checkpoint is None \
         else Checkpoint(checkpoint)
     state = ck.load(key) if ck is not None else None
@@ -97,7 +109,7 @@ def render_progressive(renderer, width=None, height=None, spp=1, bounces=1, seed
             return None
         n = min(chunk_spp, spp - done)
         fb = renderer.render(W, H, n, bounces, seed, rr, rr_depth, out_f64=True,
-                             sample_begin=done)
+                             sample_begin=done, **({"aa": True} if aa else {}))
         acc += fb * n
         done += n
         chunks += 1

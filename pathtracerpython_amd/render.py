@@ -18,7 +18,7 @@ import numbers
 import numpy as np
 
 from . import _native
-from ._abi import (PT_FLAG_COUNT, PT_FLAG_FORCE_F64, PT_FLAG_KERNEL_TIMES, PT_FLAG_MEGAKERNEL,
+from ._abi import (PT_FLAG_AA, PT_FLAG_COUNT, PT_FLAG_FORCE_F64, PT_FLAG_KERNEL_TIMES, PT_FLAG_MEGAKERNEL,
                    PT_FLAG_OUT_F64, PT_FLAG_RR, PT_FLAG_WALK_COUNT, PtStats, band_rows, make_denoise,
                    make_params)
 from .pack import pack_scene
@@ -49,14 +49,15 @@ class Renderer:
     def params(self, width=None, height=None, spp=1, bounces=1, seed=None, rr=False,
                rr_depth=3, force_f64=False, count=False, out_f64=False, row_begin=0,
                row_end=None, row_step=1, row_phase=0, sample_begin=0, megakernel=False,
-               walk_count=False, kernel_times=False, out_row_stride=0, lanes_per_pixel=0):
+               walk_count=False, kernel_times=False, out_row_stride=0, lanes_per_pixel=0, aa=False):
         """megakernel=True: scenes with a BVH render with the single kernel
         instead of the wavefront kernels (the same framebuffer, bit for bit).
         walk_count / kernel_times (wavefront renders): the walks' work counts /
         per-kernel HIP-event times in the stats.  out_row_stride: elements
         between output rows (0: packed).  lanes_per_pixel: 0 lets the
         library choose per launch; a fixed power of two makes any band split
-        bit-identical (include/pt_capi.h)."""
+        bit-identical (include/pt_capi.h).  aa=True: antialiasing, a jittered
+        primary ray per sample (PT_FLAG_AA)."""
         width = int(self.scene.width if width is None else width)
         height = int(self.scene.height if height is None else height)
         seed = self.scene.seed if seed is None else seed
@@ -64,7 +65,8 @@ class Renderer:
         flags = (PT_FLAG_RR if rr else 0) | (PT_FLAG_FORCE_F64 if force_f64 else 0) | \
             (PT_FLAG_COUNT if count else 0) | (PT_FLAG_OUT_F64 if out_f64 else 0) | \
             (PT_FLAG_MEGAKERNEL if megakernel else 0) | \
-            (PT_FLAG_WALK_COUNT if walk_count else 0) | (PT_FLAG_KERNEL_TIMES if kernel_times else 0)
+            (PT_FLAG_WALK_COUNT if walk_count else 0) | (PT_FLAG_KERNEL_TIMES if kernel_times else 0) | \
+            (PT_FLAG_AA if aa else 0)
         return make_params(width, height, spp, bounces, seed, flags, rr_depth, row_begin,
                            row_end, row_step, row_phase, sample_begin, out_row_stride,
                            lanes_per_pixel)
@@ -88,11 +90,12 @@ class Renderer:
 
     def render(self, width=None, height=None, spp=1, bounces=1, seed=None, rr=False,
                rr_depth=3, force_f64=False, stats=False, out_f64=False, megakernel=False,
-               **band):
+               aa=False, **band):
         """Framebuffer (rows, W, 3), float32 (float64 with out_f64); rows = H
-        for a full render.  stats=True also returns the work counters."""
+        for a full render.  stats=True also returns the work counters.
+        aa=True: a jittered primary ray per sample (not with stats)."""
         p = self.params(width, height, spp, bounces, seed, rr, rr_depth, force_f64,
-                        count=stats, out_f64=out_f64, megakernel=megakernel, **band)
+                        count=stats, out_f64=out_f64, megakernel=megakernel, aa=aa, **band)
         return self.render_params(p, stats=stats)
 
     def render_device(self, p, out_ptr, stream=None):
@@ -103,13 +106,13 @@ class Renderer:
                       "pt_render_device")
 
     def render_image(self, width=None, height=None, spp=1, bounces=1, seed=None, rr=False,
-                     rr_depth=3, return_fb=False):
+                     rr_depth=3, return_fb=False, aa=False):
         """make_image's uint8 array (H, W, 3) of a full render, finalised on
         the device (pt_image_u8_device) from the float64 framebuffer; with
         return_fb also that framebuffer.  Square images are exactly what
         make_image (utils.py:150-161) returns for the same colours."""
         import torch
-        p = self.params(width, height, spp, bounces, seed, rr, rr_depth, out_f64=True)
+        p = self.params(width, height, spp, bounces, seed, rr, rr_depth, out_f64=True, aa=aa)
         W, H = p.width, p.height
         fb = torch.empty((H, W, 3), dtype=torch.float64, device="cuda")
         img = torch.empty((H, W, 3), dtype=torch.uint8, device="cuda")
@@ -120,7 +123,8 @@ class Renderer:
         return (img, fb.cpu().numpy()) if return_fb else img
 
     def render_adaptive(self, width=None, height=None, max_spp=64, bounces=1, seed=None,
-                        rr=False, rr_depth=3, tol=0.05, megakernel=False, denoise=None, **rule):
+                        rr=False, rr_depth=3, tol=0.05, megakernel=False, denoise=None, aa=False,
+                        **rule):
         """Render to the noise target `tol` within max_spp samples per pixel
         (adaptive.render_adaptive: fb, counts, err, passes, samples).
         megakernel=True: a BVH scene's passes run the single kernel instead of
@@ -128,10 +132,12 @@ class Renderer:
         True or a dict of filter parameters — also the filtered frame, its
         variance and the first-hit features.  rule: min_spp, step_spp, floor,
         force_f64, on_pass, and lanes_per_pixel, checkpoint, checkpoint_every,
-        max_passes (a fixed lane count; a resumable run)."""
+        max_passes (a fixed lane count; a resumable run).  aa=True: every
+        sample has its own jittered primary ray (the features and the denoiser
+        keep the centre ray)."""
         from .adaptive import render_adaptive
         return render_adaptive(self, width, height, max_spp, bounces, seed, rr, rr_depth, tol,
-                               megakernel=megakernel, denoise=denoise, **rule)
+                               megakernel=megakernel, denoise=denoise, aa=aa, **rule)
 
     def last_kernel_ms(self):
         ms = C.c_float(0)
@@ -230,11 +236,11 @@ class MultiRenderer:
 
     def render(self, width=None, height=None, spp=1, bounces=1, seed=None, rr=False,
                rr_depth=3, stats=False, out_f64=False, row_begin=0, row_end=None,
-               lanes_per_pixel=0):
+               lanes_per_pixel=0, aa=False):
         r0 = self.renderers[0]
         p = r0.params(width, height, spp, bounces, seed, rr, rr_depth, count=stats,
                       out_f64=out_f64, row_begin=row_begin, row_end=row_end,
-                      lanes_per_pixel=lanes_per_pixel)
+                      lanes_per_pixel=lanes_per_pixel, aa=aa)
         rows = r0.band_rows(p)
         out = np.zeros((rows, p.width, 3), dtype=np.float64 if out_f64 else np.float32)
         hs = (C.c_void_p * len(self.renderers))(*[r._h.value for r in self.renderers])
@@ -245,7 +251,8 @@ class MultiRenderer:
         return (out, st.as_dict()) if stats else out
 
     def render_adaptive(self, width=None, height=None, max_spp=64, bounces=1, seed=None,
-                        rr=False, rr_depth=3, tol=0.05, megakernel=False, denoise=None, **rule):
+                        rr=False, rr_depth=3, tol=0.05, megakernel=False, denoise=None, aa=False,
+                        **rule):
         """Renderer.render_adaptive over the devices (no checkpointing): one
         banded accumulator per device, each running the pass loop of its own
         interleaved rows; the bands' tiles are merged on the first device,
@@ -258,7 +265,7 @@ class MultiRenderer:
                                  "run is not checkpointed")
         return adaptive.render_adaptive_multi(self.renderers, width, height, max_spp, bounces, seed,
                                               rr, rr_depth, tol, megakernel=megakernel,
-                                              denoise=denoise, **rule)
+                                              denoise=denoise, aa=aa, **rule)
 
     def close(self):
         for r in self.renderers:
