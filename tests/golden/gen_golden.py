@@ -19,7 +19,7 @@ What it does (SURVEY.md §8c "Deterministic harness"):
     before min-max normalisation, and also keeps the real make_image output;
   * overrides the SDL `size` (scene_reader.py:153-155) via a Scene subclass.
 
-Usage:  python gen_golden.py [all|scene|kat|mesh|meshkat|k5mini|scenes|render W H SPP B SEED]
+Usage:  python gen_golden.py [all|scene|kat|mesh|meshkat|k5mini|scenes|materials|render W H SPP B SEED]
 """
 import contextlib
 import io
@@ -309,6 +309,63 @@ def gen_scene_goldens():
         print("wrote", name, colors.shape, float(colors.min()), float(colors.max()))
 
 
+# goldens of the material scenes of tests/material_scenes.py (exponents that
+# are no small integer, kd = 0, ks = 0): (case, W, H); all 2 spp, 4 bounces,
+# seed 5.  np.float64 ** float is NaN for a negative base and a fractional
+# exponent (a RuntimeWarning, no error), so these frames hold NaN pixels.
+MATERIAL_GOLDENS = [("frac", 12, 12), ("neg", 12, 12), ("zero", 12, 12), ("mesh", 10, 10)]
+MATERIAL_FRAME = (2, 4, 5)             # spp, bounces, seed
+MATERIAL_NAN = ("frac", "mesh")        # must hold NaN pixels, and finite ones
+
+
+def material_golden_name(case, W, H):
+    spp, B, seed = MATERIAL_FRAME
+    return f"mat_{case}_{W}x{H}_s{spp}_b{B}_seed{seed}.npz"   # (neither render_* nor *_scene_*_render_*)
+
+
+def save_npz_fixed(path, **arrays):
+    """np.savez_compressed with every member's time stamp fixed, so that the
+    same arrays give the same bytes on any day."""
+    import zipfile
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED) as z:
+        for k in sorted(arrays):
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o600 << 16
+            with z.open(info, "w", force_zip64=True) as f:
+                np.lib.format.write_array(f, np.asanyarray(arrays[k]), allow_pickle=False)
+
+
+def gen_materials():
+    """The reference on the material scenes (written into a temporary
+    directory by the writer the tests use)."""
+    import tempfile
+    import warnings
+    sys.path.insert(0, os.path.dirname(HERE))
+    import material_scenes as mats
+    _, _, ref_scene = import_reference()
+    spp, B, seed = MATERIAL_FRAME
+    keys = ["red", "green", "blue", "ka", "kd", "ks", "kt", "n"]
+    for case, W, H in MATERIAL_GOLDENS:
+        d = tempfile.mkdtemp(prefix="pt_mat_")
+        sdl = mats.write_material_scene(d, case, cornell_dir=os.path.join(REF, "objs"))
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)   # invalid value in power
+            colors, _ = render_reference(W, H, spp, B, seed, scene=sdl)
+        with contextlib.redirect_stdout(io.StringIO()):
+            sc = ref_scene.Scene(sdl)
+        table = np.array([[o[k] for k in keys] for o in sc.objects], dtype=np.float64)
+        nan_px = int(np.isnan(colors).any(axis=-1).sum())
+        assert not np.isinf(colors).any()
+        if case in MATERIAL_NAN:
+            assert 0 < nan_px < W * H, (case, nan_px)
+        name = material_golden_name(case, W, H)
+        save_npz_fixed(os.path.join(HERE, name), colors=colors, width=W, height=H, spp=spp,
+                       bounces=B, seed=seed, materials=table)
+        print("wrote", name, colors.shape, "NaN pixels", nan_px, float(np.nanmin(colors)),
+              float(np.nanmax(colors)))
+
+
 def gen_scene():
     """Scene dump: what scene_reader.Scene produces (scene_reader.py:49-188)."""
     _, _, ref_scene = import_reference()
@@ -509,6 +566,8 @@ if __name__ == "__main__":
         gen_k5mini()
     if what in ("all", "scenes"):
         gen_scene_goldens()
+    if what in ("all", "materials"):
+        gen_materials()
     if what == "render":
         gen_render(*[int(x) for x in sys.argv[2:7]])
     if what == "all":
