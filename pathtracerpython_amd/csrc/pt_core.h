@@ -180,11 +180,16 @@ struct SceneK {
     const TriS* tris;
     const int32_t* tri_obj;
     const Mat* mat;
-    const int32_t* light_tri;   // [n_light] global triangle index
-    const double* light_cum;    // [n_light+1] running area sums (utils.py:31-35)
+    const int32_t* light_tri;   // [n_light] global triangle index: n_obj_tri + i (the lane
+                                // code computes it; the table is the host's record)
+    const double* light_cum;    // [n_light+1] running area sums (utils.py:31-35);
+                                // light_cum[n_light] is light_sum (the same additions)
     const int32_t* tri_grp;     // [n_tri] coplanar group of each triangle
     int32_t n_tri, n_obj_tri, n_obj, n_light;
-    int32_t n_unit, n_obj_unit, pad0, pad1;
+    int32_t n_unit, n_obj_unit;
+    int32_t light_mono;         // light_cum is finite and non-decreasing (prepare_scene's
+                                // check): pick_light takes its counting form
+    int32_t pad1;
     double light_sum;
     double eye[3];
     double ortho[4];
@@ -412,12 +417,91 @@ PT_HD int verdict_code(Verdict v) { return v.cand ? kCand : (v.amb ? kAmb : kMis
 
 // ------------------------------------------------------ light sampling --
 // pick_random_triangle, utils.py:28-39: first i with cum[i] <= n < cum[i+1]
-PT_HD int pick_light(const SceneK& S, double u) {
+PT_HD int pick_light_loop(const SceneK& S, double u) {
     const double n = 0.0 + (S.kd[kKdLightSum] - 0.0) * u;
     for (int i = 0; i < S.n_light; ++i)
         if (S.light_cum[i] <= n && n < S.light_cum[i + 1]) return i;
     return 0;   // unreachable for u < 1 (the reference would fail here)
 }
+// The same pick without a lane-dependent loop, for a table that is finite
+// and non-decreasing from cum[0] = 0: the i of the rule above is then the
+// number of i in 1 .. n_light-1 with cum[i] <= n when n < cum[n_light], and 0
+// otherwise (n < 0, n >= the sum, NaN: no interval holds n; a zero-area
+// triangle's empty interval is counted past, as the rule skips it).  The
+// trip count is wave-uniform and no load depends on lane data, so a lane's
+// three picks share scalar loads issued ahead of the Philox rounds instead of
+// load -> wait -> compare chains inside a divergent loop; the sum is the
+// table's last entry (the same additions as light_sum, pt_prepare.h).
+PT_HD int pick_light_pair(double c1, double c2, double u) {   // n_light == 2: cum[1], cum[2]
+    const double n = 0.0 + (c2 - 0.0) * u;
+    return (int)((c1 <= n) & (n < c2));
+}
+PT_HD int pick_light_count(const double* cum, int n_light, double u) {
+    const double sum = cum[n_light];
+    const double n = 0.0 + (sum - 0.0) * u;
+    int c = 0;
+    for (int i = 1; i < n_light; ++i) c += (cum[i] <= n) ? 1 : 0;
+    return n < sum ? c : 0;
+}
+// Which form: SceneK::light_mono, set by prepare_scene when the table passed
+// its check (wave-uniform: a kernel argument).  A table that fails it (an
+// area that is negative, NaN or infinite) keeps the loop.
+PT_HD int pick_light(const SceneK& S, double u) {
+    if (!S.light_mono) return pick_light_loop(S, u);
+    // one 16-B load: the Cornell light and every quad light
+    if (S.n_light == 2) return pick_light_pair(S.light_cum[1], S.light_cum[2], u);
+    return pick_light_count(S.light_cum, S.n_light, u);
+}
+// The pick's table read ahead of its use (the render loop: once per bounce,
+// before the Philox rounds of the three light samples): a two-triangle
+// light's two sums in registers, any other table stays in memory.
+// PT_LIGHT_EARLY=0 (dev) reads it at each pick.  K2: 4.41 ms with the loop,
+// 4.33 with the pair form read at each pick, 4.30 read ahead.
+#ifndef PT_LIGHT_EARLY
+#define PT_LIGHT_EARLY 1
+#endif
+struct LightTab {
+    double c1, c2;   // form 2: cum[1], cum[2]
+    int form;        // 2: the pair here, 1: pick_light_count, 0: pick_light_loop
+};
+PT_HD LightTab light_tab(const SceneK& S) {
+    LightTab t;
+    t.form = S.light_mono ? (S.n_light == 2 ? 2 : 1) : 0;
+    // (branch-free and in bounds for any table: n_light >= 1, and only form 2
+    // reads the pair)
+    t.c1 = S.light_cum[1];
+    t.c2 = S.light_cum[S.n_light < 2 ? 1 : 2];
+#if defined(__HIP_DEVICE_COMPILE__)
+    // opaque scalar copies: the compiler otherwise drops this read and issues
+    // the load again at each of the three picks, waited on at once
+#if !defined(PT_PHASE_CLOCKS)
+    asm("" : "+s"(t.c1), "+s"(t.c2));
+#else
+    // (the phase clocks' build reads the scene with vector loads: the values,
+    // wave-uniform, through readfirstlane first so that "s" is legal.  In the
+    // product's build this form costs registers: 4.37 ms)
+    uint64_t w[2];
+    __builtin_memcpy(w, &t.c1, 16);
+    uint32_t a = __builtin_amdgcn_readfirstlane((uint32_t)w[0]);
+    uint32_t b = __builtin_amdgcn_readfirstlane((uint32_t)(w[0] >> 32));
+    uint32_t c = __builtin_amdgcn_readfirstlane((uint32_t)w[1]);
+    uint32_t d = __builtin_amdgcn_readfirstlane((uint32_t)(w[1] >> 32));
+    asm("" : "+s"(a), "+s"(b), "+s"(c), "+s"(d));
+    w[0] = (uint64_t)b << 32 | a;
+    w[1] = (uint64_t)d << 32 | c;
+    __builtin_memcpy(&t.c1, w, 16);
+#endif
+#endif
+    return t;
+}
+PT_HD int pick_light(const SceneK& S, const LightTab& t, double u) {
+    if (t.form == 2) return pick_light_pair(t.c1, t.c2, u);
+    if (t.form == 1) return pick_light_count(S.light_cum, S.n_light, u);
+    return pick_light_loop(S, u);
+}
+// light i's triangle: the light's triangles follow the objects' in scene order
+// (prepare_scene fills light_tri with n_obj_tri, n_obj_tri + 1, ...)
+PT_HD int light_tri_of(const SceneK& S, int li) { return S.n_obj_tri + li; }
 
 // sample_random_pt with sample_bary_coords, utils.py:21-25, :42-46
 PT_HD D3 light_point(const TriD& T, double u1, double u2, double u3) {

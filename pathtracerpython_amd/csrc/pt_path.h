@@ -270,9 +270,10 @@ struct ShadowSet {
 // light sample k of shadow_setup (u: its 4 uniforms)
 template <bool COUNT, bool STORE_L = true>
 PT_HD void shadow_setup_k(const SceneK& S, D3 P, D3 n, int k, double u0, double u1, double u2,
-                          double u3, ShadowSet* sh, const Spill& sp) {
-    const int li = pick_light(S, u0);
-    const D3 L = light_point(S.trid[S.light_tri[li]], u1, u2, u3);
+                          double u3, ShadowSet* sh, const Spill& sp, const LightTab* lt = nullptr) {
+    // lt: the pick's table when the caller read it ahead (light_tab)
+    const int li = lt ? pick_light(S, *lt, u0) : pick_light(S, u0);
+    const D3 L = light_point(S.trid[light_tri_of(S, li)], u1, u2, u3);
     if (STORE_L) sp.put3(kSpL + 3 * k, L);
 #if PT_SETUP_REUSE
     // |L - P|^2 once: squared_dist(P, L) sums the same squares in the same
@@ -313,7 +314,7 @@ PT_HD D3 light_redraw(const SceneK& S, uint64_t seed, uint32_t pixel, uint32_t s
     uint32_t c[4];
     rng_block(seed, pixel, sample, b, (uint32_t)k, c);
     const int li = pick_light(S, u_of(c[0]));
-    return light_point(S.trid[S.light_tri[li]], u_of(c[1]), u_of(c[2]), u_of(c[3]));
+    return light_point(S.trid[light_tri_of(S, li)], u_of(c[1]), u_of(c[2]), u_of(c[3]));
 }
 // the wavefront record's RNG key in its light-point slots (written once per
 // slot, k_wf_shade step 0): the seed, pixel | sample0 << 32, the sample stride;
@@ -1941,12 +1942,18 @@ PT_HD void render_loop(const SceneK& S, const LaneJob& J, int tri, const Spill& 
         // one Philox block per light sample, drawn where it is used (fewer
         // live registers than the four blocks in lockstep)
         uint32_t w[16];
+#if PT_LIGHT_EARLY
+        const LightTab lt = light_tab(S);
+        const LightTab* ltp = &lt;
+#else
+        const LightTab* ltp = nullptr;
+#endif
 #pragma unroll
         for (int k = 0; k < kLightSamples; ++k) {
             uint32_t c[4];
             rng_block(J.seed, pixel, sample, (uint32_t)b, (uint32_t)k, c);
             shadow_setup_k<COUNT>(S, P, ld3(R.n), k, u_of(c[0]), u_of(c[1]), u_of(c[2]), u_of(c[3]),
-                                  &sh, sp);
+                                  &sh, sp, ltp);
         }
         sh.key2 = COUNT ? S.n_tri : S.n_obj;
         sh.leak = S.n_obj - 1;

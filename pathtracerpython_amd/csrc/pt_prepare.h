@@ -404,6 +404,17 @@ inline void build_unitc(HostScene* H) {
     }
 }
 
+// The condition of pick_light's counting form (pt_core.h): the running sums
+// start at 0, are finite and never decrease
+inline bool light_table_mono(const std::vector<double>& cum) {
+    if (cum.empty() || cum[0] != 0.0) return false;
+    for (size_t i = 0; i < cum.size(); ++i) {
+        if (!std::isfinite(cum[i])) return false;
+        if (i && !(cum[i - 1] <= cum[i])) return false;
+    }
+    return true;
+}
+
 // Returns "" on success, else an error message.
 inline std::string prepare_scene(const pt_scene_desc* d, HostScene* H) {
     if (!d) return "null scene descriptor";
@@ -765,7 +776,8 @@ inline std::string prepare_scene(const pt_scene_desc* d, HostScene* H) {
     K.n_obj_tri = d->n_obj_tri;
     K.n_obj = d->n_obj;
     K.n_light = (int32_t)H->light_tri.size();
-    K.light_sum = acc;
+    K.light_sum = acc;   // == light_cum[n_light]
+    K.light_mono = light_table_mono(H->light_cum) ? 1 : 0;
     for (int i = 0; i < 3; ++i) {
         K.eye[i] = d->eye[i];
         K.light_rgb[i] = d->light_rgb[i];

@@ -1,7 +1,7 @@
 // pt_render.h — the single render kernel (k_render) and its launch records,
 // shared by pt_hip.hip (the library, every other instantiation) and pt_k2.hip
 // (k_render<false, false, false>, the K2 kernel, in a translation unit of its
-// own so that it gets its own code-generation flags, build.py K2_FLAGS).
+// own so that it gets its own code-generation flags, build.py UNITS).
 #pragma once
 #include <hip/hip_runtime.h>
 
