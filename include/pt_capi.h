@@ -88,10 +88,15 @@ extern "C" {
  * whose ortho is (x0', y0', x1', y1'), and it depends on (seed, k, s) only:
  * the same draw in whichever launch, pass, band or resumed run takes it.
  * Allowed beside it: PT_FLAG_RR, PT_FLAG_FORCE_F64, PT_FLAG_OUT_F64,
- * PT_FLAG_MEGAKERNEL; with PT_FLAG_COUNT, PT_FLAG_WALK_COUNT or
- * PT_FLAG_KERNEL_TIMES it is PT_EINVAL.  Scenes with a BVH render through the
- * single kernel (as with PT_FLAG_MEGAKERNEL): the wavefront kernels have no
- * per-sample primary query yet.  An accumulator remembers the bit of its
+ * PT_FLAG_MEGAKERNEL; with PT_FLAG_COUNT it is PT_EINVAL.  Scenes with a BVH
+ * render through the wavefront kernels under the conditions of a launch
+ * without the flag (each path slot starts a closest query from the eye per
+ * sample; the same lanes per pixel, so the frame and S, Q, n are the single
+ * kernel's bit for bit).  PT_FLAG_WALK_COUNT and PT_FLAG_KERNEL_TIMES are
+ * accepted where the launch takes the wavefront kernels and fill pt_stats as
+ * for a launch without the flag; where it takes the single kernel (no BVH,
+ * PT_FLAG_MEGAKERNEL, PT_FLAG_FORCE_F64, a tree deeper than the walk stack,
+ * 2^29 path slots or more) they are PT_EINVAL.  An accumulator remembers the bit of its
  * first pass since pt_accum_reset / pt_accum_create / pt_accum_write / an
  * imported tile and refuses a pass with the other value (PT_EINVAL): mixed
  * passes would mix two definitions of sample s.  Features and the denoiser
@@ -301,8 +306,7 @@ int pt_accum_select(pt_accum* acc, const pt_adapt_params* a, void* stream,
  * see the flag); anything else is PT_EINVAL.  Scenes with a BVH run
  * the pass through the wavefront kernels (shade, sort and walk steps over the
  * slots of the listed pixels) under pt_render_device's conditions, and
- * through the single kernel with PT_FLAG_MEGAKERNEL, PT_FLAG_FORCE_F64 or
- * PT_FLAG_AA;
+ * through the single kernel with PT_FLAG_MEGAKERNEL or PT_FLAG_FORCE_F64;
  * both use the same lanes per pixel, so S, Q and n are the same bit for bit.
  * Asynchronous on `stream` (after the select's read); pt_last_kernel_ms()
  * gives the pass's kernel time. */

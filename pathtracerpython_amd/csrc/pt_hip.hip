@@ -1017,6 +1017,21 @@ int pt_band_rows(const pt_render_params* p, int32_t* rows) {
 constexpr uint32_t kKnownFlags = PT_FLAG_RR | PT_FLAG_FORCE_F64 | PT_FLAG_COUNT | PT_FLAG_OUT_F64 |
                                  PT_FLAG_MEGAKERNEL | PT_FLAG_WALK_COUNT | PT_FLAG_KERNEL_TIMES |
                                  PT_FLAG_AA;
+static const char kAaNoCount[] = "PT_FLAG_AA does not combine with PT_FLAG_COUNT, PT_FLAG_WALK_COUNT or "
+                                 "PT_FLAG_KERNEL_TIMES: the antialiasing kernels do not count";
+// An antialiased launch that takes the single kernel (pt_aa.hip) has nothing
+// to fill pt_stats with; through the wavefront kernels the walk counts and the
+// kernel times are a centre-ray launch's.
+static bool aa_stats_refused(uint32_t flags) {
+    return (flags & PT_FLAG_AA) && (flags & (PT_FLAG_WALK_COUNT | PT_FLAG_KERNEL_TIMES));
+}
+// What the scene and the flags alone say about the path: false — the launch
+// takes the single kernel whatever its size (pt_render_device's condition
+// without the slot count).
+static bool wf_scene_ok(const pt_scene* s, uint32_t flags) {
+    return s->dev.n_bnode > 0 && !(flags & (PT_FLAG_COUNT | PT_FLAG_FORCE_F64 | PT_FLAG_MEGAKERNEL)) &&
+           s->dev.n_qnode > 0 && s->dev.qstack <= kWalkStack;
+}
 static int validate(const pt_render_params* p) {
     if (!p) return fail(PT_EINVAL, "null params");
     if (p->width <= 0 || p->height <= 0) return fail(PT_EINVAL, "width/height must be > 0");
@@ -1029,9 +1044,8 @@ static int validate(const pt_render_params* p) {
         return fail(PT_EINVAL, "need row_step > 0 and 0 <= row_phase < row_step");
     if (p->flags & ~kKnownFlags)
         return fail(PT_EINVAL, "unknown flag bits (bit 7, v4's PT_FLAG_TREE_WALK, is retired)");
-    if ((p->flags & PT_FLAG_AA) && (p->flags & (PT_FLAG_COUNT | PT_FLAG_WALK_COUNT | PT_FLAG_KERNEL_TIMES)))
-        return fail(PT_EINVAL, "PT_FLAG_AA does not combine with PT_FLAG_COUNT, PT_FLAG_WALK_COUNT or "
-                               "PT_FLAG_KERNEL_TIMES: the antialiasing kernels do not count");
+    // (with PT_FLAG_WALK_COUNT / PT_FLAG_KERNEL_TIMES: aa_stats_refused, once the launch's path is known)
+    if ((p->flags & PT_FLAG_AA) && (p->flags & PT_FLAG_COUNT)) return fail(PT_EINVAL, kAaNoCount);
     if (p->out_row_stride != 0 && (int64_t)p->out_row_stride < (int64_t)p->width * 3)
         return fail(PT_EINVAL, "out_row_stride must be 0 or >= width*3");
     if (p->lanes_per_pixel != 0) {
@@ -1135,7 +1149,10 @@ static uint64_t min_lanes_of(int n_cu) {
 // launch over the path slots, then the two persistent walk launches over the
 // queries it appended.  A slot runs at most n_samples x bounces bounces plus
 // the primary ray, so that many steps (+1 to finish the last bounce) drain
-// every slot; steps after that would find no work.
+// every slot; steps after that would find no work.  An antialiased launch
+// (PT_FLAG_AA in `flags`) has no shared primary query: k_wf_shade_aa starts a
+// query per sample, so a sample takes bounces + 1 steps, step 0's closest
+// walk is over the slots' own records, and CQP stays unused.
 //
 // The list form (L, an accumulator pass: pt_accum_render): the same loop over
 // the slots of the active list's entries, with the list kernels for the
@@ -1159,7 +1176,8 @@ static int render_wavefront(pt_scene* s, const RenderK& R, const WfList* L, dim3
     const uint32_t split_log2 = L ? L->R.split_log2 : R.split_log2;
     const int32_t split = (int32_t)(1u << split_log2);
     const int32_t per_slot = ((L ? L->max_k : R.spp) + split - 1) / split;
-    const int32_t steps = per_slot * (L ? L->R.bounces : R.bounces) + 2;
+    const bool aa = (flags & PT_FLAG_AA) != 0;
+    const int32_t steps = per_slot * ((L ? L->R.bounces : R.bounces) + (aa ? 1 : 0)) + 2;
     const size_t sz_w = slots * sizeof(WfPath), sz_s = slots * sizeof(WfShadowQ),
                  sz_c = slots * sizeof(WfClosestQ), sz_l = 4 * slots * sizeof(int32_t);
     const unsigned sh_blocks =
@@ -1255,8 +1273,8 @@ static int render_wavefront(pt_scene* s, const RenderK& R, const WfList* L, dim3
     // step 0 walks the primary queries (CQP, one per pixel), later steps the slots' (CQ)
     auto closest_walk = [&](hipStream_t on, int32_t step) {
         const int32_t* l = lists + 3 * slots;
-        WfClosestQ* q = step == 0 ? CQP : CQ;
-        const uint32_t ws = step == 0 ? split_log2 : 0u;
+        WfClosestQ* q = step == 0 && !aa ? CQP : CQ;
+        const uint32_t ws = step == 0 && !aa ? split_log2 : 0u;
         if (s->dev.bunitc) {
             if (wcount) hipLaunchKernelGGL((k_wf_closest<true, true>), dim3(cl_blocks), dim3(256), 0, on, s->dev, W, q, l, counters + 2, PT_WF_THR_CLOSEST, wc + 3, ovf_cr, ovf_cd, ws);
             else hipLaunchKernelGGL((k_wf_closest<true, false>), dim3(cl_blocks), dim3(256), 0, on, s->dev, W, q, l, counters + 2, PT_WF_THR_CLOSEST, wc + 3, ovf_cr, ovf_cd, ws);
@@ -1280,7 +1298,15 @@ static int render_wavefront(pt_scene* s, const RenderK& R, const WfList* L, dim3
         HIPCHK(hipMemsetAsync(counters, 0, 4 * sizeof(int32_t), st));
         HIPCHK(mark(step, 0, 0, st));
         const dim3 sgrid((unsigned)((slots + kShadeBlock - 1) / kShadeBlock)), pgrid((n_prim + 255) / 256);
-        if (L) {
+        if (aa) {   // (the slots start their own primary queries)
+            if (L)
+                hipLaunchKernelGGL(k_wf_shade_list_aa, sgrid, dim3(kShadeBlock), 0, st, s->dev, L->R, step,
+                                   L->list, (const uint32_t*)L->n, W, SQ, CQ, lists, counters, (uint32_t)slots,
+                                   keys, home);
+            else
+                hipLaunchKernelGGL(k_wf_shade_aa, sgrid, dim3(kShadeBlock), 0, st, s->dev, R, step, W, SQ, CQ,
+                                   lists, counters, (uint32_t)slots, keys);
+        } else if (L) {
             hipLaunchKernelGGL(k_wf_shade_list, sgrid, dim3(kShadeBlock), 0, st, s->dev, L->R, step, L->list,
                                (const uint32_t*)L->n, W, SQ, CQ, (const WfClosestQ*)CQP, lists, counters,
                                (uint32_t)slots, keys, home);
@@ -1374,6 +1400,7 @@ int pt_render_device(pt_scene* s, const pt_render_params* p, void* out_dev, void
     int rc = validate(p);
     if (rc) return rc;
     if (!s) return fail(PT_EINVAL, "null scene");
+    if (aa_stats_refused(p->flags) && !wf_scene_ok(s, p->flags)) return fail(PT_EINVAL, kAaNoCount);
     int32_t first = 0, rows = 0;
     band_layout(p, &first, &rows);
     if (rows == 0) return PT_OK;
@@ -1444,13 +1471,12 @@ int pt_render_device(pt_scene* s, const pt_render_params* p, void* out_dev, void
     // only the single kernel implements; and for launches of 2^29 or more
     // path slots, beyond the shadow lists' (slot << 2) | ray entries — the
     // single kernel's framebuffer is the same bit for bit)
-    // (and for antialiased launches: the wavefront kernels have no per-sample
-    // primary query)
     const bool aa = (p->flags & PT_FLAG_AA) != 0;
-    const bool wavefront = s->dev.n_bnode > 0 && !count && !f64 && !aa &&
+    const bool wavefront = s->dev.n_bnode > 0 && !count && !f64 &&
                            !(p->flags & PT_FLAG_MEGAKERNEL) && s->dev.n_qnode > 0 &&
                            s->dev.qstack <= kWalkStack && (uint64_t)grid.x * 256u < ((uint64_t)1 << 29);
     if (wavefront) return render_wavefront(s, R, nullptr, grid, out_dev, st, p->flags, stats);
+    if (aa_stats_refused(p->flags)) return fail(PT_EINVAL, kAaNoCount);
     if (count) HIPCHK(hipMemsetAsync(s->stats, 0, sizeof(StatsDev), st));
     HIPCHK(hipEventRecord(s->ev0, st));
     if (aa) {   // (validate: never with count)
@@ -1738,6 +1764,7 @@ int pt_accum_render_stats(pt_accum* a, const pt_render_params* p, const pt_adapt
         return fail(PT_EINVAL, "this accumulator's passes so far were made with the other value of PT_FLAG_AA: "
                                "sample s would have two definitions (pt_accum_reset first)");
     pt_scene* s = a->scene;
+    if (aa_stats_refused(p->flags) && !wf_scene_ok(s, p->flags)) return fail(PT_EINVAL, kAaNoCount);
     DeviceGuard g(s->device);
     hipStream_t st = (hipStream_t)stream;
     if (stats) memset(stats, 0, sizeof(*stats));
@@ -1776,12 +1803,12 @@ int pt_accum_render_stats(pt_accum* a, const pt_render_params* p, const pt_adapt
     // list form) under pt_render_device's conditions; the same split, so S, Q
     // and n are the single kernel's bit for bit
     const uint64_t wf_blocks = (threads + 255) / 256;
-    if (bvh && !f64 && !aa && !(p->flags & PT_FLAG_MEGAKERNEL) && s->dev.n_qnode > 0 &&
+    if (bvh && !f64 && !(p->flags & PT_FLAG_MEGAKERNEL) && s->dev.n_qnode > 0 &&
         s->dev.qstack <= kWalkStack && wf_blocks * 256u < ((uint64_t)1 << 29)) {
         rc = accum_begin(a, st);
         if (rc) return rc;
         a->list_valid = false;   // the pass changes n, S, Q
-        a->aa = 0;
+        a->aa = aa ? 1 : 0;
         WfList L;
         L.R = R;
         L.R.lanes = wf_blocks * 256u;
@@ -1790,6 +1817,7 @@ int pt_accum_render_stats(pt_accum* a, const pt_render_params* p, const pt_adapt
         L.max_k = (int32_t)std::min(A.step_spp, A.max_spp);
         return render_wavefront(s, RenderK{}, &L, dim3((unsigned)wf_blocks), nullptr, st, p->flags, stats);
     }
+    if (aa_stats_refused(p->flags)) return fail(PT_EINVAL, kAaNoCount);
 #if PT_MOMENT_HOME
     if (R.lanes > a->home_lanes) {   // (the previous pass may still read the old one: ordered by the free)
         if (a->home) HIPCHK(hipFree(a->home));

@@ -62,6 +62,7 @@ struct SlotJob {
     int32_t row_local, ix;
     uint32_t c;
     bool valid;
+    int32_t iy;   // the pixel's image row (with ix: aa_dir's pixel, the antialiased shade step)
 };
 __device__ __forceinline__ SlotJob slot_job(const SceneK& S, const RenderK& R, uint32_t tid) {
     SlotJob j;
@@ -70,12 +71,14 @@ __device__ __forceinline__ SlotJob slot_job(const SceneK& S, const RenderK& R, u
     j.valid = pl < R.npix;
     j.row_local = 0;
     j.ix = 0;
+    j.iy = 0;
     j.d0 = d3(0, 0, 0);
     j.J = LaneJob{};
     if (j.valid) {
         j.row_local = (int32_t)(pl / (uint32_t)R.W);
         j.ix = (int32_t)pl - j.row_local * R.W;
         const int32_t iy = R.first_row + j.row_local * R.row_step;
+        j.iy = iy;
         const D3 eye = ld3(S.eye);
         const double x = linspace_at(S.ortho[0], S.ortho[2], R.W, j.ix);
         const double y = linspace_at(S.ortho[1], S.ortho[3], R.H, iy);
@@ -111,6 +114,7 @@ struct ListJob {
     D3 d0;
     uint32_t e, k;
     bool valid;
+    int32_t ix, iy;   // the entry's pixel (aa_dir's, the antialiased shade step)
 };
 __device__ __forceinline__ ListJob list_job(const SceneK& S, const ListK& R, const uint32_t* __restrict__ list,
                                             const uint32_t* __restrict__ accN, uint32_t tid) {
@@ -119,6 +123,7 @@ __device__ __forceinline__ ListJob list_job(const SceneK& S, const ListK& R, con
     j.e = entry < R.n_list ? list[entry] : 0xffffffffu;
     j.valid = j.e < R.npix;   // the same for all slots of an entry
     j.k = 0;
+    j.ix = j.iy = 0;
     j.d0 = d3(0, 0, 0);
     j.J = LaneJob{};
     // (the launch's constants outside the branch: they stay wave-uniform, and
@@ -132,6 +137,8 @@ __device__ __forceinline__ ListJob list_job(const SceneK& S, const ListK& R, con
         j.k = adapt_k(n0, R.A);
         const int32_t row = (int32_t)(j.e / (uint32_t)R.W);
         const int32_t ix = (int32_t)j.e - row * R.W, iy = R.H - 1 - row;
+        j.ix = ix;
+        j.iy = iy;
         const D3 eye = ld3(S.eye);
         const double x = linspace_at(S.ortho[0], S.ortho[2], R.W, ix);
         const double y = linspace_at(S.ortho[1], S.ortho[3], R.H, iy);

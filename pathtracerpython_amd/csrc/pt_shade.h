@@ -1,5 +1,6 @@
 // pt_shade.h — the wavefront path's list appends and its shade step
-// (k_wf_shade; k_wf_shade_list, its list form for accumulator passes), shared
+// (k_wf_shade; k_wf_shade_list, its list form for accumulator passes;
+// k_wf_shade_aa / k_wf_shade_list_aa, their antialiased forms), shared
 // by pt_hip.hip and pt_shade.hip: the shade kernels are compiled in a
 // translation unit of their own (pt_shade.hip) so that they get their own
 // code-generation flags (build.py UNITS), as the K2 kernel does (pt_k2.hip).
@@ -203,7 +204,75 @@ __global__ __launch_bounds__(kShadeBlock) void k_wf_shade_list(
     wf_append_block(want, counters, lists, lists + 3 * (size_t)slots, (int32_t)tid);
 #endif
 }
+// The antialiased forms (PT_FLAG_AA; pt_wavefront.h wf_aa_start, wf_shade_aa):
+// no shared primary query — step 0 initialises the slot and starts its first
+// sample's own query, and every later sample of the slot starts in the shade
+// step that ends the one before it.  k_wf_primary is not launched.
+__global__ __launch_bounds__(kShadeBlock) void k_wf_shade_aa(SceneK S, RenderK R, int32_t step,
+                                                     WfPath* __restrict__ W, WfShadowQ* __restrict__ SQ,
+                                                     WfClosestQ* __restrict__ CQ,
+                                                     int32_t* __restrict__ lists, int32_t* counters,
+                                                     uint32_t slots, uint16_t* __restrict__ keys) {
+    const uint32_t tid = blockIdx.x * (uint32_t)kShadeBlock + threadIdx.x;
+    uint32_t want = 0;
+    uint32_t skey = 0;
+    if (tid >= slots) {   // (the last block of a kShadeBlock grid over 256-slot blocks)
+    } else if (step == 0) {
+        SlotJob j = slot_job(S, R, tid);
+        W[tid].acc[0] = W[tid].acc[1] = W[tid].acc[2] = 0.0;
+        W[tid].put_rkey(j.J);
+        W[tid].si = 0;
+        W[tid].set(kWfDone, false, 0);
+        const bool go = j.valid && j.J.n_samples > 0 && j.J.bounces > 0;
+        j.J.seed = R.seed;   // (wave-uniform: aa_jitter's rng_block takes its key in scalar registers)
+        if (go) want = wf_aa_start(S, j.J, AaPixel{R.W, R.H, j.ix, j.iy}, &W[tid], &CQ[tid]);
+    } else if ((tid >> R.split_log2) < R.npix && W[tid].state() != kWfDone) {
+        SlotJob j = slot_job(S, R, tid);
+        j.J.seed = R.seed;   // (as in step 0; the slot is valid)
+        want = wf_shade_aa<PT_WF_BIN != 0>(S, j.J, AaPixel{R.W, R.H, j.ix, j.iy}, &W[tid], &SQ[tid], &CQ[tid]);
+        skey = want >> 16;   // (0 without PT_WF_BIN, and for a primary query)
+        want &= 0xffffu;
+    }
+    wf_append_block(want, counters, lists, lists + 3 * (size_t)slots, (int32_t)tid, keys, skey);
+}
+__global__ __launch_bounds__(kShadeBlock) void k_wf_shade_list_aa(
+    SceneK S, ListK R, int32_t step, const uint32_t* __restrict__ list, const uint32_t* __restrict__ accN,
+    WfPath* __restrict__ W, WfShadowQ* __restrict__ SQ, WfClosestQ* __restrict__ CQ,
+    int32_t* __restrict__ lists, int32_t* counters, uint32_t slots, uint16_t* __restrict__ keys,
+    double* __restrict__ home) {
+    const uint32_t tid = blockIdx.x * (uint32_t)kShadeBlock + threadIdx.x;
+    uint32_t want = 0;
+    uint32_t skey = 0;
+    WfMoments M{{home + tid, (size_t)slots}};
+    if (tid >= slots) {   // (the last block of a kShadeBlock grid over 256-slot blocks)
+    } else if (step == 0) {
+        const ListJob j = list_job(S, R, list, accN, tid);
+        M.clear();
+        W[tid].acc[0] = W[tid].acc[1] = W[tid].acc[2] = 0.0;
+        W[tid].put_rkey(j.J);
+        W[tid].si = 0;
+        W[tid].set(kWfDone, false, 0);
+        if (j.valid && j.J.n_samples > 0 && j.J.bounces > 0)
+            want = wf_aa_start(S, j.J, AaPixel{R.W, R.H, j.ix, j.iy}, &W[tid], &CQ[tid]);
+    } else if ((tid >> R.split_log2) < R.n_list && W[tid].state() != kWfDone) {
+        const ListJob j = list_job(S, R, list, accN, tid);
+        want = wf_shade_aa<PT_WF_BIN != 0>(S, j.J, AaPixel{R.W, R.H, j.ix, j.iy}, &W[tid], &SQ[tid], &CQ[tid], M);
+        skey = want >> 16;
+        want &= 0xffffu;
+    }
+    wf_append_block(want, counters, lists, lists + 3 * (size_t)slots, (int32_t)tid, keys, skey);
+}
 #elif !defined(PT_SHADE_UNIT)
+__global__ __launch_bounds__(kShadeBlock) void k_wf_shade_aa(SceneK S, RenderK R, int32_t step,
+                                                     WfPath* __restrict__ W, WfShadowQ* __restrict__ SQ,
+                                                     WfClosestQ* __restrict__ CQ,
+                                                     int32_t* __restrict__ lists, int32_t* counters,
+                                                     uint32_t slots, uint16_t* __restrict__ keys);
+__global__ __launch_bounds__(kShadeBlock) void k_wf_shade_list_aa(
+    SceneK S, ListK R, int32_t step, const uint32_t* __restrict__ list, const uint32_t* __restrict__ accN,
+    WfPath* __restrict__ W, WfShadowQ* __restrict__ SQ, WfClosestQ* __restrict__ CQ,
+    int32_t* __restrict__ lists, int32_t* counters, uint32_t slots, uint16_t* __restrict__ keys,
+    double* __restrict__ home);
 __global__ __launch_bounds__(kShadeBlock) void k_wf_shade(SceneK S, RenderK R, int32_t step,
                                                   WfPath* __restrict__ W, WfShadowQ* __restrict__ SQ,
                                                   WfClosestQ* __restrict__ CQ, const WfClosestQ* __restrict__ CQP,

@@ -23,6 +23,9 @@
 // order, so the framebuffer is bitwise identical to k_render's (tested).
 // Path state lives in HBM between the kernels: WfPath (256 B per slot, the
 // f64 spill home included) and the query records.
+// With antialiasing (PT_FLAG_AA) a slot has no cached primary hit: every
+// sample starts with its own closest query from the eye (wf_aa_start), issued
+// by the shade step that ends the sample before it (wf_shade_aa).
 #pragma once
 #include <stddef.h>
 
@@ -195,6 +198,47 @@ PT_HD uint32_t wf_start(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, WfC
     return kWfWantClosest;
 }
 
+// Antialiasing (PT_FLAG_AA, pt_path.h AaSched): the slot has no cached primary
+// hit.  Sample W->si starts with its own closest query from the eye along the
+// jittered ray: wf_start's body for that d0, the candidates of the eye-frame
+// units into the slot's own query record (walked like a bounce's query, the
+// slot's spill home holding the eye and d0).  The eye units are tested in
+// aa_closest's unit form (PT_WF_AA_PRIMARY_M: origin_q / closest_unit_m, the
+// ambiguous members decided in f64) or in wf_start's per-triangle form; both
+// are conservative filters in front of the same closest_finish.
+#ifndef PT_WF_AA_PRIMARY_M
+#define PT_WF_AA_PRIMARY_M (PT_AA_PRIMARY_M && PT_LIGHT_QUAD && PT_QUAD && PT_MARGIN)
+#endif
+PT_HD uint32_t wf_aa_start(const SceneK& S, const LaneJob& J, const AaPixel& X, WfPath* W,
+                           WfClosestQ* cq) {
+    const Spill sp{W->sp, 1};
+    double jx, jy;
+    aa_jitter(J.seed, J.pixel, (uint32_t)(J.sample0 + W->si * J.sample_stride), &jx, &jy);
+    const D3 d0 = aa_dir(S, X.W, X.H, X.ix, X.iy, jx, jy);
+    const D3 eye = ld3(S.eye);
+    const D3 dn = unit(d0);
+    sp.put3(kSpP, eye);
+    sp.put3(kSpNd, d0);
+    const F3 o32 = to_f3(eye - ld3(S.center));
+    const F3 d32 = to_f3(dn);
+    ClosestAcc acc = closest_init();
+    for (int u = 0; u < S.n_unit; ++u) {   // from the eye: the unit_eye records
+        const UnitF U = S.unit_eye[u];
+#if PT_WF_AA_PRIMARY_M
+        const OriginU O = origin_q(U, o32);
+        if (closest_unit_m(U, O, U.grp == -1, d32, &acc))   // rare
+            fused_fallback<false, false, true, 2>(S, U, closest_bits_m(U, O, U.grp == -1, d32), nullptr,
+                                                  &acc, sp, nullptr, nullptr);
+#else
+        closest_unit<false>(S, U, origin_u(U, o32), d32, U.grp == -1, sp, kSpP, kSpNd, &acc,
+                            nullptr);
+#endif
+    }
+    wf_put_closest(cq, o32, -1, d32, acc);
+    W->set(kWfPrimary, false, 0);
+    return kWfWantClosest;
+}
+
 // The body of render_lane's loop up to its walks: RNG, light samples, next
 // ray, the fused pass over the uniform units (pt_path.h render_lane).
 // The sort key of a query origin (the BVH frame, PT_WF_BIN, render_wavefront):
@@ -320,10 +364,47 @@ PT_HD uint32_t wf_begin_bounce(const SceneK& S, const LaneJob& J, WfPath* W, WfS
 // constant n_samples times, as render_lane_moments does.
 struct WfSum { static constexpr bool kMoments = false; };
 struct WfMoments : MomentMem { static constexpr bool kMoments = true; };
-template <class Home>
-PT_HD bool wf_finish(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, const WfShadowQ* shq,
-                     const WfClosestQ* cq, const WfClosestQ* pq, Home home) {
+//
+// AA (antialiasing): a primary query per sample, in the slot's own record cq
+// (wf_aa_start), and nothing cached in kSpD0 / kSpP0 / tri0.  A sample whose
+// primary ray escapes or hits the light is complete at once (AaSched /
+// AaMomentSched's order), and a path's end restarts from the eye.  Returns
+// kWfNextPrimary when the slot's next sample is to be started in this shade
+// step (wf_aa_start; d0 and pq are unused).
+enum : int { kWfNextNone = 0, kWfNextBounce = 1, kWfNextPrimary = 2 };
+template <class Home, bool AA = false>
+PT_HD int wf_finish(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, const WfShadowQ* shq,
+                    const WfClosestQ* cq, const WfClosestQ* pq, Home home) {
     const Spill sp{W->sp, 1};
+    if constexpr (AA) {
+        if (W->state() == kWfPrimary) {   // aa_primary: closest(eye, d0 of this sample)
+            const D3 dj = sp.get3(kSpNd);
+            D3 P0 = d3(0, 0, 0);
+            const int tri0 = closest_finish<false, false, true>(S, wf_get_acc(*cq), ld3(S.eye), unit(dj),
+                                                                &P0, nullptr);
+            if (tri0 >= 0 && tri0 < S.n_obj_tri) {
+                W->set(kWfBegin, false, 0);   // (b = 0; begin_bounce sets the state)
+                W->tri = tri0;
+                W->k = 1.0;
+                sp.put3(kSpP, P0);   // (kSpNd holds d0, the incoming direction of bounce 0)
+                return kWfNextBounce;
+            }
+            // the sample is complete: 0, or the light's colour (main.py:214-215)
+            if constexpr (Home::kMoments) {
+                home.add(tri0 < 0 ? d3(0, 0, 0) : ld3(S.kd + kKdLightRgb));
+            } else {
+                if (tri0 >= 0) {
+                    const D3 acc = ld3(W->acc) + ld3(S.kd + kKdLightRgb);
+                    W->acc[0] = acc.x; W->acc[1] = acc.y; W->acc[2] = acc.z;
+                }
+            }
+            const int si = W->si + 1;
+            W->si = si;
+            if (si < J.n_samples) return kWfNextPrimary;
+            W->set(kWfDone, false, 0);
+            return kWfNextNone;
+        }
+    } else
     if (W->state() == kWfPrimary) {   // k_render: closest(eye, d0) then render_lane's prologue
         D3 P0 = d3(0, 0, 0);
         const int tri0 = closest_finish<false, false, true>(S, wf_get_acc(*pq), ld3(S.eye), unit(d0),
@@ -390,6 +471,13 @@ PT_HD bool wf_finish(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, const 
             acc = d3(0, 0, 0);
         }
         ++si;
+        if constexpr (AA) {   // next sample: its own primary query
+            W->acc[0] = acc.x; W->acc[1] = acc.y; W->acc[2] = acc.z;
+            W->si = si;
+            if (si < J.n_samples) return kWfNextPrimary;
+            W->set(kWfDone, false, 0);
+            return kWfNextNone;
+        } else
         if (si < J.n_samples) {   // next sample from the cached primary hit
             b = 0;
             tri = W->tri0;
@@ -422,6 +510,15 @@ template <bool KEY = false, class Home = WfSum>
 PT_HD uint32_t wf_shade(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, WfShadowQ* shq,
                         WfClosestQ* cq, const WfClosestQ* pq, Home home = Home{}) {
     return wf_finish(S, J, d0, W, shq, cq, pq, home) ? wf_begin_bounce<KEY>(S, J, W, shq, cq) : 0u;
+}
+// The antialiased shade step: after wf_finish either the next bounce's start
+// or the next sample's primary query (X: the slot's pixel, for aa_dir).
+template <bool KEY = false, class Home = WfSum>
+PT_HD uint32_t wf_shade_aa(const SceneK& S, const LaneJob& J, const AaPixel& X, WfPath* W, WfShadowQ* shq,
+                           WfClosestQ* cq, Home home = Home{}) {
+    const int next = wf_finish<Home, true>(S, J, d3(0, 0, 0), W, shq, cq, nullptr, home);
+    if (next == kWfNextBounce) return wf_begin_bounce<KEY>(S, J, W, shq, cq);
+    return next == kWfNextPrimary ? wf_aa_start(S, J, X, W, cq) : 0u;
 }
 
 }  // namespace pt

@@ -18,7 +18,7 @@ frame; without --noise the -r samples go through the accumulator),
 --local-devices N (N GPUs of this process, no rank processes: interleaved row
 bands, also for --noise / --denoise; render.MultiRenderer), --aa
 (antialiasing: a jittered primary ray per sample, PT_FLAG_AA; combines with
-every flag above; scenes with a BVH then render through the single kernel).  The
+every flag above; scenes with a BVH keep the wavefront kernels).  The
 reference's interactive 3-D viewer flags (--show-scene, --show-normals,
 --show-screen, --show-inter -> plot.py) are accepted and ignored with a
 notice: the pyqtgraph viewer is out of scope.
@@ -201,9 +201,6 @@ def main(argv=None):
     if args.show_scene or args.show_normals or args.show_screen or args.show_inter:
         print('note: the 3-D scene viewer (plot.py) is not part of this build; ignoring --show-*',
               file=sys.stderr)
-    if args.aa and scene_has_bvh(scene):
-        print('note: --aa renders scenes with a BVH through the single kernel (the wavefront '
-              'kernels have no per-sample primary ray yet)', file=sys.stderr)
     rank, _, world = rank_env()
     if world != args.devices:
         raise SystemExit(f'--devices {args.devices} but WORLD_SIZE={world}')
@@ -261,15 +258,6 @@ def main(argv=None):
         spp = f'up to {args.n_rays}' if args.noise is not None else f'{args.n_rays}'
         print(f'render: {W}x{H}, {spp} spp, {args.n_bounces} bounces, {last}')
     return finish(args, arr, fb)
-
-
-BVH_MIN_TRIS = 64   # pt_prepare.h kBvhMinTris
-
-
-def scene_has_bvh(scene):
-    """Whether the library builds a BVH for this scene: some object has at
-    least the mesh threshold of triangles (pt_prepare.h kBvhMinTris)."""
-    return any(len(o["geometry"].triangles) >= BVH_MIN_TRIS for o in scene.objects)
 
 
 def report_adaptive(args, res, W, H):

@@ -93,7 +93,8 @@ class Renderer:
                aa=False, **band):
         """Framebuffer (rows, W, 3), float32 (float64 with out_f64); rows = H
         for a full render.  stats=True also returns the work counters.
-        aa=True: a jittered primary ray per sample (not with stats)."""
+        aa=True: a jittered primary ray per sample (not with stats; on
+        scenes with a BVH through the wavefront kernels, like any render)."""
         p = self.params(width, height, spp, bounces, seed, rr, rr_depth, force_f64,
                         count=stats, out_f64=out_f64, megakernel=megakernel, aa=aa, **band)
         return self.render_params(p, stats=stats)

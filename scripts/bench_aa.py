@@ -3,6 +3,7 @@
 writes it to --out, default profiles/aa_k2.json, stamped with pt_build_id).
 
     python3 scripts/bench_aa.py [--parts uniform,list,effect,bvh] [--out FILE]
+    python3 scripts/bench_aa.py --parts k5            (writes profiles/aa_k5.json)
     python3 scripts/bench_aa.py --parts parent --parent-root DIR [--rounds 5]
 
 The K2 frame: Cornell 512x512, 64 spp, 4 bounces, seed 9.  Kernel times are
@@ -20,6 +21,12 @@ launches each (default 20), the median of the last --keep (default 10).
   bvh      a scene with a BVH (synth.write_k5_scene, 100k triangles, 512x512,
            16 spp, 4 bounces): the antialiased single kernel beside the
            centre-ray single kernel (megakernel=True) and the wavefront render
+  k5       the same scene and shape, antialiasing through the wavefront kernels
+           (the default on BVH scenes) beside the antialiased single kernel
+           (megakernel=True) and the centre-ray wavefront render; one
+           PT_FLAG_KERNEL_TIMES launch of each wavefront form (the shade /
+           shadow / closest / sort split); the tol-0.05 adaptive run (min 8,
+           step 8, max 64, floor 0.01) with aa=True through both paths
   parent   `python bench.py --gpus 1` on this tree and on the parent commit's
            (DIR: a built checkout of it) in alternating child processes,
            --rounds each: is this tree's K2 line inside the parent's own
@@ -104,9 +111,11 @@ def main():
     ap.add_argument("--steps", type=int, default=20, help="part parent: bench.py --steps")
     ap.add_argument("--warmup", type=int, default=5, help="part parent: bench.py --warmup")
     ap.add_argument("--parent-root", default=None)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "aa_k2.json"))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
     parts = args.parts.split(",")
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "aa_k5.json" if parts == ["k5"] else "aa_k2.json")
     if parts == ["parent"]:
         if not args.parent_root:
             raise SystemExit("--parts parent needs --parent-root")
@@ -215,7 +224,7 @@ def measure(args, parts):
                 fb = torch.empty((Hb, Wb, 3), dtype=torch.float32, device="cuda")
                 p = {"wavefront": rb.params(Wb, Hb, 16, BOUNCES, SEED),
                      "single_kernel": rb.params(Wb, Hb, 16, BOUNCES, SEED, megakernel=True),
-                     "single_kernel_aa": rb.params(Wb, Hb, 16, BOUNCES, SEED, aa=True)}
+                     "single_kernel_aa": rb.params(Wb, Hb, 16, BOUNCES, SEED, aa=True, megakernel=True)}
                 ms = {k: [] for k in p}
                 n = max(4, args.launches // 4)
                 for _ in range(n):
@@ -231,6 +240,8 @@ def measure(args, parts):
                 b["ratio_aa_to_wavefront"] = (b["single_kernel_aa"]["kernel_ms"]["median"] /
                                               b["wavefront"]["kernel_ms"]["median"])
                 res["bvh"] = b
+        if "k5" in parts:
+            res["k5"] = part_k5(args, last)
         if "effect" in parts:
             We = He = 64
             ref = r.render(We, He, 4096, BOUNCES, SEED + 1, out_f64=True, aa=True)
@@ -243,6 +254,74 @@ def measure(args, parts):
                              "rmse_edge": {"aa": rmse(aa, ref, edge), "centre_ray": rmse(centre, ref, edge)},
                              "rmse_other": {"aa": rmse(aa, ref, ~edge), "centre_ray": rmse(centre, ref, ~edge)}}
     return res
+
+
+def part_k5(args, last):
+    """Antialiasing on a BVH scene: the wavefront form of the per-sample
+    primary query beside the single kernel and the centre-ray wavefront."""
+    import tempfile
+    import torch
+    from pathtracerpython_amd import scene_reader
+    from pathtracerpython_amd._abi import make_adapt
+    from pathtracerpython_amd.adaptive import Accumulator
+    from pathtracerpython_amd.render import Renderer
+    from pathtracerpython_amd.synth import write_k5_scene
+    Wb = Hb = 512
+    spp = 16
+    k5 = scene_reader.Scene(write_k5_scene(tempfile.mkdtemp(), n_tris=100_000, seed=0, size=Wb))
+    out = {"shape": {"scene": "K5 synth", "n_tris": 100_000, "width": Wb, "height": Hb, "spp": spp,
+                     "bounces": BOUNCES, "seed": SEED}}
+    with Renderer(k5) as rb:
+        fb = torch.empty((Hb, Wb, 3), dtype=torch.float32, device="cuda")
+        p = {"aa_wavefront": rb.params(Wb, Hb, spp, BOUNCES, SEED, aa=True),
+             "aa_single_kernel": rb.params(Wb, Hb, spp, BOUNCES, SEED, aa=True, megakernel=True),
+             "centre_wavefront": rb.params(Wb, Hb, spp, BOUNCES, SEED)}
+        ms = {k: [] for k in p}
+        for _ in range(args.launches):
+            for k in p:
+                rb.render_device(p[k], fb.data_ptr(), 0)
+                torch.cuda.synchronize()
+                ms[k].append(rb.last_kernel_ms())
+        for k in p:
+            out[k] = {"kernel_ms": last(ms[k])}
+        med = {k: out[k]["kernel_ms"]["median"] for k in p}
+        out["ratio_aa_wavefront_to_aa_single_kernel"] = med["aa_wavefront"] / med["aa_single_kernel"]
+        out["ratio_aa_wavefront_to_centre_wavefront"] = med["aa_wavefront"] / med["centre_wavefront"]
+        out["step_count_floor_of_that_ratio"] = (BOUNCES + 1) / BOUNCES
+        # the per-kernel split (the walks one after the other on one stream)
+        split = {}
+        for k, aa in (("aa_wavefront", True), ("centre_wavefront", False)):
+            _, st = rb.render_params(rb.params(Wb, Hb, spp, BOUNCES, SEED, aa=aa, kernel_times=True), stats=True)
+            split[k] = {f: st[f] for f in ("shade_ms", "shadow_ms", "closest_ms", "sort_ms", "shade_launches",
+                                           "shadow_launches", "closest_launches", "sort_launches")}
+        out["kernel_times"] = split
+        # the adaptive run, antialiased, through both paths
+        with Accumulator(rb, Wb, Hb) as acc:
+            adapt = make_adapt(0.05, 64, 8, 8, 0.01)
+            pa = {"aa_wavefront": rb.params(Wb, Hb, 64, BOUNCES, SEED, aa=True),
+                  "aa_single_kernel": rb.params(Wb, Hb, 64, BOUNCES, SEED, aa=True, megakernel=True)}
+            kern = {k: [] for k in pa}
+            info = {}
+            runs = max(3, args.launches // 5)
+            for _ in range(runs):
+                for k in pa:
+                    acc.reset()
+                    t, passes = 0.0, 0
+                    while acc.select(adapt)[0]:
+                        acc.render(pa[k], adapt)
+                        torch.cuda.synchronize()
+                        t += rb.last_kernel_ms()
+                        passes += 1
+                    kern[k].append(t)
+                    info[k] = (passes, acc.read(n=True)["n"])
+            row = {k: {"pass_kernel_ms_sum": stat(kern[k][-max(2, runs // 2):]), "passes": info[k][0],
+                       "samples": int(info[k][1].sum())} for k in pa}
+            row["same_count_map"] = bool(np.array_equal(info["aa_wavefront"][1], info["aa_single_kernel"][1]))
+            row["kernel_ratio_wavefront_to_single_kernel"] = (
+                row["aa_wavefront"]["pass_kernel_ms_sum"]["median"] /
+                row["aa_single_kernel"]["pass_kernel_ms_sum"]["median"])
+            out["adaptive_tol_0.05"] = row
+    return out
 
 
 if __name__ == "__main__":
