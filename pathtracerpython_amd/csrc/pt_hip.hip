@@ -49,11 +49,16 @@ extern template __global__ void k_render<false, false, false>(SceneK, RenderK, v
 #endif
 
 // ------------------------------------------------- wavefront (BVH scenes) --
-// the list appends and the shade step (k_wf_shade): pt_shade.h
+// the list appends' helpers and the shade kernels (pt_shade.hip): pt_shade.h
 #include "pt_shade.h"
 
-// PT_WF_BIN: the shadow list's counting sort on the 12-bit cell key without
-// the host: the list's length n is read on the device.  nb = bin_cols(n)
+// The shadow walks' query list is sorted by the origin's cell (wf_cell, 12
+// Morton bits) before each walk step (render_wavefront): lanes of a wave then
+// walk from nearby origins toward the light, and the shadow walks run 10%
+// faster.  The closest list stays unsorted (random
+// directions: its walks did not gain).
+// The sort: a counting sort on the 12-bit cell key without the host — the
+// list's length n is read on the device.  nb = bin_cols(n)
 // blocks (at most kBinBlocks, at least kBinMinChunk entries each, so a short
 // list pays a small count matrix) each take a contiguous chunk of the list;
 // k_bin_hist counts its keys per cell (LDS) into the cell-major count matrix
@@ -196,12 +201,7 @@ __global__ __launch_bounds__(256) void k_wf_primary(SceneK S, RenderK R, WfPath*
                                                     WfClosestQ* __restrict__ CQP,
                                                     int32_t* __restrict__ list, int32_t* counters) {
     const uint32_t pix = blockIdx.x * 256u + threadIdx.x;
-    uint32_t want = 0;
-    if (pix < R.npix) {
-        const uint32_t slot = pix << R.split_log2;
-        const SlotJob j = slot_job(S, R, slot);
-        if (j.valid) want = wf_start(S, j.J, j.d0, &W[slot], &CQP[pix]);
-    }
+    const uint32_t want = wf_primary_step(S, WfFrame{R}, pix, W, CQP);
     wf_append((want & kWfWantClosest) != 0, counters, list, (int32_t)pix);
 }
 // Persistent walk kernels over the 4-wide quantised BVH (QNode): a
@@ -424,7 +424,7 @@ __global__ __launch_bounds__(256) void k_wf_final(SceneK S, RenderK R, const WfP
 // A pass renders a LIST of pixels: k_accum_select_* build it (err, the active
 // predicate, an ordered compaction), k_render_list adds k samples to each
 // listed pixel, k_accum_resolve writes S / n as a framebuffer (ListK:
-// pt_render.h).
+// pt_job.h).
 // The lane's home of S and Q across the bounce loop: 0 the lane's registers
 // (MomentRegs), 1 a device buffer [6][lanes], touched only when a path ends
 // (MomentMem).  Both stay at 128 VGPRs / 64 B scratch; the registers are 5%
@@ -738,12 +738,7 @@ __global__ __launch_bounds__(256) void k_wf_primary_list(SceneK S, ListK R, cons
                                                          WfPath* __restrict__ W, WfClosestQ* __restrict__ CQP,
                                                          int32_t* __restrict__ qlist, int32_t* counters) {
     const uint32_t entry = blockIdx.x * 256u + threadIdx.x;
-    uint32_t want = 0;
-    if (entry < R.n_list) {
-        const uint32_t slot = entry << R.split_log2;
-        const ListJob j = list_job(S, R, list, accN, slot);
-        if (j.valid) want = wf_start(S, j.J, j.d0, &W[slot], &CQP[entry]);
-    }
+    const uint32_t want = wf_primary_step(S, WfActive{R, list, accN}, entry, W, CQP);
     wf_append((want & kWfWantClosest) != 0, counters, qlist, (int32_t)entry);
 }
 // k_render_list's epilogue over the slots' sums (home[6][slots], one block of
@@ -778,6 +773,20 @@ __global__ __launch_bounds__(256) void k_wf_final_list(ListK R, const uint32_t* 
         }
     }
 }
+
+// Sections of a scratch buffer, handed out front to back (base null: only the
+// sizes, `at` the bytes needed so far)
+struct Bump {
+    char* base;
+    size_t at = 0;
+    template <class T>
+    T* take(size_t n, size_t align = 256) {
+        at = (at + align - 1) / align * align;
+        T* p = base ? (T*)(base + at) : nullptr;
+        at += n * sizeof(T);
+        return p;
+    }
+};
 
 // ---------------------------------------------------------------- API --
 struct pt_scene {
@@ -1032,6 +1041,14 @@ static bool wf_scene_ok(const pt_scene* s, uint32_t flags) {
     return s->dev.n_bnode > 0 && !(flags & (PT_FLAG_COUNT | PT_FLAG_FORCE_F64 | PT_FLAG_MEGAKERNEL)) &&
            s->dev.n_qnode > 0 && s->dev.qstack <= kWalkStack;
 }
+// This launch takes the wavefront kernels: BVH scenes, unless the caller asks
+// for the single kernel, or for counting / forced f64, which only the single
+// kernel implements (wf_scene_ok), or the launch has 2^29 or more path slots,
+// beyond the shadow lists' (slot << 2) | ray entries.  The single kernel's
+// result is the same bit for bit.
+static bool wf_route(const pt_scene* s, uint32_t flags, uint64_t slots) {
+    return wf_scene_ok(s, flags) && slots < ((uint64_t)1 << 29);
+}
 static int validate(const pt_render_params* p) {
     if (!p) return fail(PT_EINVAL, "null params");
     if (p->width <= 0 || p->height <= 0) return fail(PT_EINVAL, "width/height must be > 0");
@@ -1161,6 +1178,23 @@ static uint64_t min_lanes_of(int n_cu) {
 // come from the largest k the rule allows.  Every pass initialises every slot
 // it launches (k_wf_shade_list's step 0): s->wf holds whatever the previous
 // pass or render left.
+// The walk launches: the <UC, COUNT> instantiation for a scene whose BVH units
+// have the 64-B form (SceneK::bunitc) and for a PT_FLAG_WALK_COUNT launch.
+static void launch_wf_closest(bool uc, bool count, unsigned blocks, hipStream_t on, const SceneK& S, WfPath* W,
+                              WfClosestQ* Q, const int32_t* list, int32_t* counters, unsigned long long* wc,
+                              int* ovf_ref, uint16_t* ovf_dist, uint32_t wshift) {
+    const auto k = uc ? (count ? k_wf_closest<true, true> : k_wf_closest<true, false>)
+                      : (count ? k_wf_closest<false, true> : k_wf_closest<false, false>);
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, on, S, W, Q, list, counters, PT_WF_THR_CLOSEST, wc, ovf_ref,
+                       ovf_dist, wshift);
+}
+static void launch_wf_shadow(bool uc, bool count, unsigned blocks, hipStream_t on, const SceneK& S, WfPath* W,
+                             WfShadowQ* SQ, const int32_t* list, int32_t* counters, unsigned long long* wc,
+                             int* ovf) {
+    const auto k = uc ? (count ? k_wf_shadow<true, true> : k_wf_shadow<true, false>)
+                      : (count ? k_wf_shadow<false, true> : k_wf_shadow<false, false>);
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, on, S, W, SQ, list, counters, PT_WF_THR_SHADOW, wc, ovf);
+}
 struct WfList {
     ListK R;
     const uint32_t* list;
@@ -1178,35 +1212,47 @@ static int render_wavefront(pt_scene* s, const RenderK& R, const WfList* L, dim3
     const int32_t per_slot = ((L ? L->max_k : R.spp) + split - 1) / split;
     const bool aa = (flags & PT_FLAG_AA) != 0;
     const int32_t steps = per_slot * ((L ? L->R.bounces : R.bounces) + (aa ? 1 : 0)) + 2;
-    const size_t sz_w = slots * sizeof(WfPath), sz_s = slots * sizeof(WfShadowQ),
-                 sz_c = slots * sizeof(WfClosestQ), sz_l = 4 * slots * sizeof(int32_t);
     const unsigned sh_blocks =
         std::max(1u, std::min<unsigned>(grid.x, (unsigned)PT_WF_SHADOW_BLOCKS_PER_CU * (unsigned)s->n_cu));
     const unsigned cl_blocks =
         std::max(1u, std::min<unsigned>(grid.x, (unsigned)PT_WF_CLOSEST_BLOCKS_PER_CU * (unsigned)s->n_cu));
-    // walk-stack overflow (entries below the shared-memory part): 4 B per
-    // entry and shadow lane, 4 + 2 B per entry and closest lane
-    const size_t ovf_n = (size_t)kWalkStackGlobal;
-    const size_t sz_os = ovf_n * sh_blocks * 256 * 4, sz_ocr = ovf_n * cl_blocks * 256 * 4,
-                 sz_ocd = ovf_n * cl_blocks * 256 * 2;
-    const size_t off_s = sz_w, off_c = off_s + sz_s, off_l = off_c + sz_c, off_n = off_l + sz_l;
-    const size_t off_os = off_n + 256, off_ocr = off_os + sz_os, off_ocd = off_ocr + sz_ocr;
-    const size_t sz_p = (size_t)n_prim * sizeof(WfClosestQ);   // the primary queries
-    const size_t off_p = (off_ocd + sz_ocd + 255) / 256 * 256;
-    // PT_WF_BIN: the shadow list's keys (3 slots x u16), the sorted list
-    // (3 slots x i32), the sort's count matrix, its scan and scan storage
-    size_t sz_tmp = 0;
-#if PT_WF_BIN
-    // the count matrix (its rows' prefix sums in place), the row totals and their scan
-    sz_tmp = ((size_t)kBins * kBinBlocks + 2 * (size_t)kBins) * sizeof(uint32_t);
-#endif
-    const size_t sz_k = PT_WF_BIN ? 3 * slots * sizeof(uint16_t) : 0,
-                 sz_lo = PT_WF_BIN ? 3 * slots * sizeof(int32_t) : 0;
-    const size_t off_k = (off_p + sz_p + 255) / 256 * 256, off_lo = (off_k + sz_k + 255) / 256 * 256,
-                 off_t = (off_lo + sz_lo + 255) / 256 * 256;
-    // the list form's moment home
-    const size_t off_h = (off_t + sz_tmp + 255) / 256 * 256, sz_h = L ? 6 * slots * sizeof(double) : 0;
-    const size_t need = off_h + sz_h + 256;
+    // the launch's buffers in s->wf, each section on a 256-B boundary
+    struct {
+        WfPath* W;
+        WfShadowQ* SQ;
+        WfClosestQ* CQ;
+        int32_t *lists, *counters;   // [4 slots], [4] (the shade kernels' queue counters)
+        int* ovf_s;                  // walk-stack overflow (entries below the shared-memory part):
+        int* ovf_cr;                 // 4 B per entry and shadow lane, 4 + 2 B per entry and closest lane
+        uint16_t* ovf_cd;
+        WfClosestQ* CQP;             // the primary queries
+        uint16_t* keys;              // the shadow list's sort keys [3 slots]
+        int32_t* lists_o;            // the sorted shadow list [3 slots]
+        uint32_t *bin_hist, *bin_rowsum, *bin_base;   // the sort's count matrix (its rows' prefix sums in
+                                                      // place), the row totals and their scan
+        double* home;                // the list form's moment home [6][slots]
+    } B;
+    auto carve = [&](char* base) -> size_t {   // returns the bytes carved
+        Bump m{base};
+        const size_t ovf_n = (size_t)kWalkStackGlobal;
+        B.W = m.take<WfPath>(slots);
+        B.SQ = m.take<WfShadowQ>(slots);
+        B.CQ = m.take<WfClosestQ>(slots);
+        B.lists = m.take<int32_t>(4 * slots);
+        B.counters = m.take<int32_t>(64);
+        B.ovf_s = m.take<int>(ovf_n * sh_blocks * 256);
+        B.ovf_cr = m.take<int>(ovf_n * cl_blocks * 256);
+        B.ovf_cd = m.take<uint16_t>(ovf_n * cl_blocks * 256);
+        B.CQP = m.take<WfClosestQ>(n_prim);
+        B.keys = m.take<uint16_t>(3 * slots);
+        B.lists_o = m.take<int32_t>(3 * slots);
+        B.bin_hist = m.take<uint32_t>((size_t)kBins * kBinBlocks);
+        B.bin_rowsum = m.take<uint32_t>(kBins);
+        B.bin_base = m.take<uint32_t>(kBins);
+        B.home = m.take<double>(L ? 6 * slots : 0);
+        return m.at;
+    };
+    const size_t need = carve(nullptr) + 256;
     if (need > s->wf_bytes) {
         if (s->wf) (void)hipFree(s->wf);
         s->wf = nullptr;
@@ -1219,39 +1265,21 @@ static int render_wavefront(pt_scene* s, const RenderK& R, const WfList* L, dim3
         HIPCHK(hipEventCreateWithFlags(&s->wf_ev_shade, hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&s->wf_ev_walk, hipEventDisableTiming));
     }
-    char* b = (char*)s->wf;
-    WfPath* W = (WfPath*)b;
-    WfShadowQ* SQ = (WfShadowQ*)(b + off_s);
-    WfClosestQ* CQ = (WfClosestQ*)(b + off_c);
-    int32_t* lists = (int32_t*)(b + off_l);
-    int32_t* counters = (int32_t*)(b + off_n);
-    int* ovf_s = (int*)(b + off_os);
-    int* ovf_cr = (int*)(b + off_ocr);
-    uint16_t* ovf_cd = (uint16_t*)(b + off_ocd);
-    WfClosestQ* CQP = (WfClosestQ*)(b + off_p);
-    uint16_t* keys = PT_WF_BIN ? (uint16_t*)(b + off_k) : nullptr;
-    int32_t* lists_o = (int32_t*)(b + off_lo);
-    double* home = (double*)(b + off_h);
-#if PT_WF_BIN
-    uint32_t* bin_hist = (uint32_t*)(b + off_t);
-    uint32_t* bin_rowsum = bin_hist + (size_t)kBins * kBinBlocks;
-    uint32_t* bin_base = bin_rowsum + kBins;
-#endif
-    bool sorted = false;   // this step's lists are in lists_o
-#if PT_WF_BIN
+    carve((char*)s->wf);
+    int32_t* const closest_list = B.lists + 3 * slots;
+    bool sorted = false;   // this step's shadow list is in lists_o
     auto bin_sort = [&]() -> hipError_t {   // (the device reads the list's length: no host wait)
-        hipLaunchKernelGGL(k_bin_hist, dim3(kBinBlocks), dim3(256), 0, st, (const uint16_t*)keys,
-                           (const int32_t*)counters, bin_hist);
-        hipLaunchKernelGGL(k_bin_rows, dim3(kBins / 4), dim3(256), 0, st, bin_hist, (const int32_t*)counters,
-                           bin_rowsum);
-        hipLaunchKernelGGL(k_bin_base, dim3(1), dim3(1024), 0, st, (const uint32_t*)bin_rowsum, bin_base);
-        hipLaunchKernelGGL(k_bin_scatter, dim3(kBinBlocks), dim3(256), 0, st, (const uint16_t*)keys,
-                           (const int32_t*)lists, (const int32_t*)counters, (const uint32_t*)bin_hist,
-                           (const uint32_t*)bin_base, lists_o);
+        hipLaunchKernelGGL(k_bin_hist, dim3(kBinBlocks), dim3(256), 0, st, (const uint16_t*)B.keys,
+                           (const int32_t*)B.counters, B.bin_hist);
+        hipLaunchKernelGGL(k_bin_rows, dim3(kBins / 4), dim3(256), 0, st, B.bin_hist, (const int32_t*)B.counters,
+                           B.bin_rowsum);
+        hipLaunchKernelGGL(k_bin_base, dim3(1), dim3(1024), 0, st, (const uint32_t*)B.bin_rowsum, B.bin_base);
+        hipLaunchKernelGGL(k_bin_scatter, dim3(kBinBlocks), dim3(256), 0, st, (const uint16_t*)B.keys,
+                           (const int32_t*)B.lists, (const int32_t*)B.counters, (const uint32_t*)B.bin_hist,
+                           (const uint32_t*)B.bin_base, B.lists_o);
         sorted = true;
         return hipGetLastError();
     };
-#endif
     const bool wcount = (flags & PT_FLAG_WALK_COUNT) != 0 && stats;
     const bool times = (flags & PT_FLAG_KERNEL_TIMES) != 0 && stats;
     unsigned long long* wc = (unsigned long long*)s->stats;   // [0..2] shadow, [3..5] closest
@@ -1270,55 +1298,32 @@ static int render_wavefront(pt_scene* s, const RenderK& R, const WfList* L, dim3
     auto mark = [&](int32_t step, int k, int end, hipStream_t on) -> hipError_t {
         return times ? hipEventRecord(s->prof_ev[(size_t)step * kEv + k * 2 + end], on) : hipSuccess;
     };
-    // step 0 walks the primary queries (CQP, one per pixel), later steps the slots' (CQ)
-    auto closest_walk = [&](hipStream_t on, int32_t step) {
-        const int32_t* l = lists + 3 * slots;
-        WfClosestQ* q = step == 0 && !aa ? CQP : CQ;
-        const uint32_t ws = step == 0 && !aa ? split_log2 : 0u;
-        if (s->dev.bunitc) {
-            if (wcount) hipLaunchKernelGGL((k_wf_closest<true, true>), dim3(cl_blocks), dim3(256), 0, on, s->dev, W, q, l, counters + 2, PT_WF_THR_CLOSEST, wc + 3, ovf_cr, ovf_cd, ws);
-            else hipLaunchKernelGGL((k_wf_closest<true, false>), dim3(cl_blocks), dim3(256), 0, on, s->dev, W, q, l, counters + 2, PT_WF_THR_CLOSEST, wc + 3, ovf_cr, ovf_cd, ws);
-        } else {
-            if (wcount) hipLaunchKernelGGL((k_wf_closest<false, true>), dim3(cl_blocks), dim3(256), 0, on, s->dev, W, q, l, counters + 2, PT_WF_THR_CLOSEST, wc + 3, ovf_cr, ovf_cd, ws);
-            else hipLaunchKernelGGL((k_wf_closest<false, false>), dim3(cl_blocks), dim3(256), 0, on, s->dev, W, q, l, counters + 2, PT_WF_THR_CLOSEST, wc + 3, ovf_cr, ovf_cd, ws);
-        }
-    };
-    auto shadow_walk = [&](hipStream_t on) {
-        const int32_t* l = sorted ? lists_o : lists;
-        if (s->dev.bunitc) {
-            if (wcount) hipLaunchKernelGGL((k_wf_shadow<true, true>), dim3(sh_blocks), dim3(256), 0, on, s->dev, W, SQ, l, counters, PT_WF_THR_SHADOW, wc, ovf_s);
-            else hipLaunchKernelGGL((k_wf_shadow<true, false>), dim3(sh_blocks), dim3(256), 0, on, s->dev, W, SQ, l, counters, PT_WF_THR_SHADOW, wc, ovf_s);
-        } else {
-            if (wcount) hipLaunchKernelGGL((k_wf_shadow<false, true>), dim3(sh_blocks), dim3(256), 0, on, s->dev, W, SQ, l, counters, PT_WF_THR_SHADOW, wc, ovf_s);
-            else hipLaunchKernelGGL((k_wf_shadow<false, false>), dim3(sh_blocks), dim3(256), 0, on, s->dev, W, SQ, l, counters, PT_WF_THR_SHADOW, wc, ovf_s);
-        }
-    };
     HIPCHK(hipEventRecord(s->ev0, st));
     for (int32_t step = 0; step < steps; ++step) {
-        HIPCHK(hipMemsetAsync(counters, 0, 4 * sizeof(int32_t), st));
+        HIPCHK(hipMemsetAsync(B.counters, 0, 4 * sizeof(int32_t), st));
         HIPCHK(mark(step, 0, 0, st));
         const dim3 sgrid((unsigned)((slots + kShadeBlock - 1) / kShadeBlock)), pgrid((n_prim + 255) / 256);
         if (aa) {   // (the slots start their own primary queries)
             if (L)
                 hipLaunchKernelGGL(k_wf_shade_list_aa, sgrid, dim3(kShadeBlock), 0, st, s->dev, L->R, step,
-                                   L->list, (const uint32_t*)L->n, W, SQ, CQ, lists, counters, (uint32_t)slots,
-                                   keys, home);
+                                   L->list, (const uint32_t*)L->n, B.W, B.SQ, B.CQ, B.lists, B.counters,
+                                   (uint32_t)slots, B.keys, B.home);
             else
-                hipLaunchKernelGGL(k_wf_shade_aa, sgrid, dim3(kShadeBlock), 0, st, s->dev, R, step, W, SQ, CQ,
-                                   lists, counters, (uint32_t)slots, keys);
+                hipLaunchKernelGGL(k_wf_shade_aa, sgrid, dim3(kShadeBlock), 0, st, s->dev, R, step, B.W, B.SQ,
+                                   B.CQ, B.lists, B.counters, (uint32_t)slots, B.keys);
         } else if (L) {
             hipLaunchKernelGGL(k_wf_shade_list, sgrid, dim3(kShadeBlock), 0, st, s->dev, L->R, step, L->list,
-                               (const uint32_t*)L->n, W, SQ, CQ, (const WfClosestQ*)CQP, lists, counters,
-                               (uint32_t)slots, keys, home);
+                               (const uint32_t*)L->n, B.W, B.SQ, B.CQ, (const WfClosestQ*)B.CQP, B.lists,
+                               B.counters, (uint32_t)slots, B.keys, B.home);
             if (step == 0)
                 hipLaunchKernelGGL(k_wf_primary_list, pgrid, dim3(256), 0, st, s->dev, L->R, L->list,
-                                   (const uint32_t*)L->n, W, CQP, lists + 3 * slots, counters + 2);
+                                   (const uint32_t*)L->n, B.W, B.CQP, closest_list, B.counters + 2);
         } else {
-            hipLaunchKernelGGL(k_wf_shade, sgrid, dim3(kShadeBlock), 0, st, s->dev, R, step, W, SQ, CQ,
-                               (const WfClosestQ*)CQP, lists, counters, (uint32_t)slots, keys);
+            hipLaunchKernelGGL(k_wf_shade, sgrid, dim3(kShadeBlock), 0, st, s->dev, R, step, B.W, B.SQ, B.CQ,
+                               (const WfClosestQ*)B.CQP, B.lists, B.counters, (uint32_t)slots, B.keys);
             if (step == 0)
-                hipLaunchKernelGGL(k_wf_primary, pgrid, dim3(256), 0, st, s->dev, R, W, CQP,
-                                   lists + 3 * slots, counters + 2);
+                hipLaunchKernelGGL(k_wf_primary, pgrid, dim3(256), 0, st, s->dev, R, B.W, B.CQP, closest_list,
+                                   B.counters + 2);
         }
         HIPCHK(mark(step, 0, 1, st));
         sorted = false;
@@ -1335,10 +1340,13 @@ static int render_wavefront(pt_scene* s, const RenderK& R, const WfList* L, dim3
                 HIPCHK(hipStreamWaitEvent(s->wf_side, s->wf_ev_shade, 0));
             }
             HIPCHK(mark(step, 2, 0, cs));
-            closest_walk(cs, step);
+            // step 0 walks the primary queries (CQP, one per pixel / entry, the
+            // spill home in its first slot), later steps the slots' (CQ)
+            const bool prim = step == 0 && !aa;
+            launch_wf_closest(s->dev.bunitc != nullptr, wcount, cl_blocks, cs, s->dev, B.W, prim ? B.CQP : B.CQ,
+                              closest_list, B.counters + 2, wc + 3, B.ovf_cr, B.ovf_cd, prim ? split_log2 : 0u);
             HIPCHK(mark(step, 2, 1, cs));
             if (side) HIPCHK(hipEventRecord(s->wf_ev_walk, s->wf_side));
-#if PT_WF_BIN
             // the shadow list sorted by the origin's cell (the device reads
             // its length) while the closest walks, unsorted, already run
             if (step > 0) {   // (step 0: the primary rays)
@@ -1346,18 +1354,18 @@ static int render_wavefront(pt_scene* s, const RenderK& R, const WfList* L, dim3
                 HIPCHK(bin_sort());
                 HIPCHK(mark(step, 3, 1, st));
             }
-#endif
             HIPCHK(mark(step, 1, 0, st));
-            shadow_walk(st);
+            launch_wf_shadow(s->dev.bunitc != nullptr, wcount, sh_blocks, st, s->dev, B.W, B.SQ,
+                             sorted ? B.lists_o : B.lists, B.counters, wc, B.ovf_s);
             HIPCHK(mark(step, 1, 1, st));
             if (side) HIPCHK(hipStreamWaitEvent(st, s->wf_ev_walk, 0));
         }
     }
     if (L)
-        hipLaunchKernelGGL(k_wf_final_list, grid, dim3(256), 0, st, L->R, L->list, (const double*)home,
+        hipLaunchKernelGGL(k_wf_final_list, grid, dim3(256), 0, st, L->R, L->list, (const double*)B.home,
                            (uint32_t)slots, L->S, L->Q, L->n);
     else
-        hipLaunchKernelGGL(k_wf_final, grid, dim3(256), 0, st, s->dev, R, (const WfPath*)W, out_dev);
+        hipLaunchKernelGGL(k_wf_final, grid, dim3(256), 0, st, s->dev, R, (const WfPath*)B.W, out_dev);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s->ev1, st));
     s->timed = true;
@@ -1380,7 +1388,7 @@ static int render_wavefront(pt_scene* s, const RenderK& R, const WfList* L, dim3
             for (int32_t step = 0; step < steps; ++step)
                 for (int k = 0; k < 4; ++k) {
                     if (k > 0 && step + 1 >= steps) continue;
-                    if (k == 3 && (!PT_WF_BIN || step == 0)) continue;
+                    if (k == 3 && step == 0) continue;   // (no sort before the primary walks)
                     float ms = 0.f;
                     HIPCHK(hipEventElapsedTime(&ms, s->prof_ev[(size_t)step * kEv + k * 2],
                                                s->prof_ev[(size_t)step * kEv + k * 2 + 1]));
@@ -1420,8 +1428,7 @@ int pt_render_device(pt_scene* s, const pt_render_params* p, void* out_dev, void
                   ? (uint32_t)p->lanes_per_pixel
                   : choose_split((uint64_t)p->width * (uint64_t)p->height, (uint64_t)R.npix, p->spp,
                                  s->dev.n_bnode > 0, min_lanes_of(s->n_cu));
-    R.split_log2 = 0;
-    while ((1u << R.split_log2) < R.split) ++R.split_log2;
+    R.split_log2 = log2_ceil(R.split);
     R.tail_pix = R.npix;
     R.tail_lane = R.npix * R.split;
     R.tail_log2 = R.split_log2;
@@ -1466,16 +1473,9 @@ int pt_render_device(pt_scene* s, const pt_render_params* p, void* out_dev, void
     const dim3 rgrid((unsigned)((threads + kRenderBlock - 1) / kRenderBlock)), rblock(kRenderBlock);
     const bool count = (p->flags & PT_FLAG_COUNT) != 0;
     const bool f64 = (p->flags & PT_FLAG_FORCE_F64) != 0;
-    // BVH scenes render through the wavefront kernels unless the caller asks
-    // for the single kernel (and for counting / forced-f64 launches, which
-    // only the single kernel implements; and for launches of 2^29 or more
-    // path slots, beyond the shadow lists' (slot << 2) | ray entries — the
-    // single kernel's framebuffer is the same bit for bit)
     const bool aa = (p->flags & PT_FLAG_AA) != 0;
-    const bool wavefront = s->dev.n_bnode > 0 && !count && !f64 &&
-                           !(p->flags & PT_FLAG_MEGAKERNEL) && s->dev.n_qnode > 0 &&
-                           s->dev.qstack <= kWalkStack && (uint64_t)grid.x * 256u < ((uint64_t)1 << 29);
-    if (wavefront) return render_wavefront(s, R, nullptr, grid, out_dev, st, p->flags, stats);
+    if (wf_route(s, p->flags, (uint64_t)grid.x * 256u))
+        return render_wavefront(s, R, nullptr, grid, out_dev, st, p->flags, stats);
     if (aa_stats_refused(p->flags)) return fail(PT_EINVAL, kAaNoCount);
     if (count) HIPCHK(hipMemsetAsync(s->stats, 0, sizeof(StatsDev), st));
     HIPCHK(hipEventRecord(s->ev0, st));
@@ -1789,8 +1789,7 @@ int pt_accum_render_stats(pt_accum* a, const pt_render_params* p, const pt_adapt
         while (cap * 2u <= std::min(kmin, 64u)) cap *= 2u;
         R.split = std::min(a->lanes_per_pixel, cap);
     }
-    R.split_log2 = 0;
-    while ((1u << R.split_log2) < R.split) ++R.split_log2;
+    R.split_log2 = log2_ceil(R.split);
     R.n_list = m.count;
     R.npix = a->npix;
     R.A = A;
@@ -1800,11 +1799,10 @@ int pt_accum_render_stats(pt_accum* a, const pt_render_params* p, const pt_adapt
     if (R.lanes >= ((uint64_t)1 << 32)) return fail(PT_EINVAL, "launch needs 2^32 or more work-items (32-bit lane index)");
     const bool f64 = (p->flags & PT_FLAG_FORCE_F64) != 0;
     // BVH scenes take the pass through the wavefront kernels (render_wavefront's
-    // list form) under pt_render_device's conditions; the same split, so S, Q
+    // list form) under pt_render_device's condition; the same split, so S, Q
     // and n are the single kernel's bit for bit
     const uint64_t wf_blocks = (threads + 255) / 256;
-    if (bvh && !f64 && !(p->flags & PT_FLAG_MEGAKERNEL) && s->dev.n_qnode > 0 &&
-        s->dev.qstack <= kWalkStack && wf_blocks * 256u < ((uint64_t)1 << 29)) {
+    if (wf_route(s, p->flags, wf_blocks * 256u)) {
         rc = accum_begin(a, st);
         if (rc) return rc;
         a->list_valid = false;   // the pass changes n, S, Q

@@ -1,13 +1,11 @@
-// pt_render.h — the single render kernel (k_render) and its launch records,
+// pt_render.h — the single render kernel (k_render; its launch records: pt_job.h),
 // shared by pt_hip.hip (the library, every other instantiation) and pt_k2.hip
 // (k_render<false, false, false>, the K2 kernel, in a translation unit of its
 // own so that it gets its own code-generation flags, build.py UNITS).
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "pt_path.h"
-
-using namespace pt;
+#include "pt_job.h"   // RenderK, ListK, slot_job, list_job
 
 // PT_K2_OWN_TU: k_render<false, false, false> is compiled in pt_k2.hip
 // (pt_hip.hip declares the instantiation extern).  The phase-clock dev build
@@ -21,22 +19,6 @@ using namespace pt;
 #endif
 
 // ------------------------------------------------------------- kernels --
-struct RenderK {
-    int32_t W, H, spp, bounces;
-    uint64_t seed;
-    int32_t rr_depth;   // -1: off
-    int32_t first_row, row_step, n_rows;
-    int32_t sample_begin;
-    uint32_t split, split_log2;
-    uint32_t npix;
-    int32_t out_f64;
-    uint32_t out_stride;   // elements between output rows (pt_render_params.out_row_stride)
-    // single kernel, launch drain: the pixels from tail_pix on (the image's
-    // top rows, dispatched last) get 2^tail_log2 lanes each, from lane
-    // tail_lane (a multiple of 64) on; tail_pix = npix: none
-    uint32_t tail_pix, tail_lane, tail_log2;
-};
-
 struct StatsDev { unsigned long long v[8]; };
 
 template <bool COUNT>
@@ -51,103 +33,6 @@ __device__ __forceinline__ void flush_counters(const Counters& c, StatsDev* st) 
         for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m);
         if ((threadIdx.x & 63) == 0 && x) atomicAdd(&st->v[i], (unsigned long long)x);
     }
-}
-
-// Work-item -> (pixel, sample slice) of a launch: `split` adjacent work-items
-// share a pixel and stride its samples; the primary ray of main.py:191
-// (make_screen_pts / make_rays, utils.py:55-69).
-struct SlotJob {
-    LaneJob J;
-    D3 d0;
-    int32_t row_local, ix;
-    uint32_t c;
-    bool valid;
-    int32_t iy;   // the pixel's image row (with ix: aa_dir's pixel, the antialiased shade step)
-};
-__device__ __forceinline__ SlotJob slot_job(const SceneK& S, const RenderK& R, uint32_t tid) {
-    SlotJob j;
-    const uint32_t pl = tid >> R.split_log2;
-    j.c = tid & (R.split - 1u);
-    j.valid = pl < R.npix;
-    j.row_local = 0;
-    j.ix = 0;
-    j.iy = 0;
-    j.d0 = d3(0, 0, 0);
-    j.J = LaneJob{};
-    if (j.valid) {
-        j.row_local = (int32_t)(pl / (uint32_t)R.W);
-        j.ix = (int32_t)pl - j.row_local * R.W;
-        const int32_t iy = R.first_row + j.row_local * R.row_step;
-        j.iy = iy;
-        const D3 eye = ld3(S.eye);
-        const double x = linspace_at(S.ortho[0], S.ortho[2], R.W, j.ix);
-        const double y = linspace_at(S.ortho[1], S.ortho[3], R.H, iy);
-        j.d0 = d3(x - eye.x, y - eye.y, 0.0 - eye.z);
-        const int32_t c = (int32_t)j.c, sp = (int32_t)R.split;
-        j.J.seed = R.seed;
-        j.J.pixel = (uint32_t)j.ix * (uint32_t)R.H + (uint32_t)iy;
-        j.J.sample0 = R.sample_begin + c;
-        j.J.sample_stride = sp;
-        j.J.n_samples = (c < R.spp) ? (R.spp - c + sp - 1) / sp : 0;
-        j.J.bounces = R.bounces;
-        j.J.rr_depth = R.rr_depth;
-    }
-    return j;
-}
-
-// An accumulator pass (pt_accum, pt_hip.hip "adaptive sampling"): the launch
-// renders a LIST of pixels.
-struct ListK {
-    int32_t W, H, bounces, rr_depth;   // rr_depth -1: off
-    uint64_t seed;
-    uint32_t split, split_log2;
-    uint32_t n_list, npix;
-    uint64_t lanes;   // work-items of the launch (a multiple of 64): the moment home's stride
-    AdaptK A;
-};
-// Work-item -> (list entry, sample slice) of a pass through the wavefront
-// kernels, k_render_list's mapping: `split` adjacent slots share the entry's
-// pixel e and stride the k = adapt_k(n[e]) samples the pass adds, from sample
-// n[e] on.  An entry that is no pixel of the frame is never dereferenced.
-struct ListJob {
-    LaneJob J;
-    D3 d0;
-    uint32_t e, k;
-    bool valid;
-    int32_t ix, iy;   // the entry's pixel (aa_dir's, the antialiased shade step)
-};
-__device__ __forceinline__ ListJob list_job(const SceneK& S, const ListK& R, const uint32_t* __restrict__ list,
-                                            const uint32_t* __restrict__ accN, uint32_t tid) {
-    ListJob j;
-    const uint32_t entry = tid >> R.split_log2, c = tid & (R.split - 1u);
-    j.e = entry < R.n_list ? list[entry] : 0xffffffffu;
-    j.valid = j.e < R.npix;   // the same for all slots of an entry
-    j.k = 0;
-    j.ix = j.iy = 0;
-    j.d0 = d3(0, 0, 0);
-    j.J = LaneJob{};
-    // (the launch's constants outside the branch: they stay wave-uniform, and
-    // rng_block takes its key in scalar registers)
-    j.J.seed = R.seed;
-    j.J.sample_stride = (int32_t)R.split;
-    j.J.bounces = R.bounces;
-    j.J.rr_depth = R.rr_depth;
-    if (j.valid) {
-        const uint32_t n0 = accN[j.e];
-        j.k = adapt_k(n0, R.A);
-        const int32_t row = (int32_t)(j.e / (uint32_t)R.W);
-        const int32_t ix = (int32_t)j.e - row * R.W, iy = R.H - 1 - row;
-        j.ix = ix;
-        j.iy = iy;
-        const D3 eye = ld3(S.eye);
-        const double x = linspace_at(S.ortho[0], S.ortho[2], R.W, ix);
-        const double y = linspace_at(S.ortho[1], S.ortho[3], R.H, iy);
-        j.d0 = d3(x - eye.x, y - eye.y, 0.0 - eye.z);
-        j.J.pixel = (uint32_t)ix * (uint32_t)R.H + (uint32_t)iy;
-        j.J.sample0 = (int32_t)(n0 + c);
-        j.J.n_samples = c < j.k ? (int32_t)((j.k - c + R.split - 1u) >> R.split_log2) : 0;
-    }
-    return j;
 }
 
 // Sum of a pixel's sample colours over its `split` work-items (fixed xor

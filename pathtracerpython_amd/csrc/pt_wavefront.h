@@ -29,7 +29,7 @@
 #pragma once
 #include <stddef.h>
 
-#include "pt_path.h"
+#include "pt_job.h"   // (and pt_path.h)
 
 namespace pt {
 
@@ -241,7 +241,7 @@ PT_HD uint32_t wf_aa_start(const SceneK& S, const LaneJob& J, const AaPixel& X, 
 
 // The body of render_lane's loop up to its walks: RNG, light samples, next
 // ray, the fused pass over the uniform units (pt_path.h render_lane).
-// The sort key of a query origin (the BVH frame, PT_WF_BIN, render_wavefront):
+// The sort key of a query origin (the BVH frame; render_wavefront's sort):
 // 4 bits per axis over the root node's grid, in Morton order (neighbouring
 // cells get neighbouring keys)
 PT_HD uint32_t wf_cell(const SceneK& S, F3 o) {
@@ -262,7 +262,7 @@ PT_HD uint32_t wf_cell(const SceneK& S, F3 o) {
         for (int a = 0; a < 3; ++a) m |= ((c[a] >> b) & 1u) << (3 * b + a);
     return m;
 }
-// KEY: the origin's cell in bits 16..27 of the result (k_wf_shade takes it off)
+// KEY: the origin's cell in bits 16..27 of the result (the shade kernels take it off, pt_shade.hip)
 template <bool KEY = false>
 PT_HD uint32_t wf_begin_bounce(const SceneK& S, const LaneJob& J, WfPath* W, WfShadowQ* shq,
                                WfClosestQ* cq) {
@@ -352,9 +352,9 @@ PT_HD uint32_t wf_begin_bounce(const SceneK& S, const LaneJob& J, WfPath* W, WfS
 
 // Shade step >= 1, first half: finish the pending work of the slot with the
 // walks' results (the colour, the next hit, path end / next sample).  Returns
-// true when the slot's next bounce is to be started (state kWfBegin; the
-// second half is wf_begin_bounce).  pq: the slot's primary query (the GPU
-// shares one per pixel, k_wf_primary; the host emulation has one per slot, cq)
+// kWfNextBounce when the slot's next bounce is to be started (state kWfBegin;
+// the second half is wf_begin_bounce), else kWfNextNone.  pq: the slot's
+// primary query (one per pixel / entry, wf_primary_step)
 //
 // Home: where a path's colour goes when the path ends.  WfSum (the uniform
 // render): nowhere, W->acc runs on over the slot's samples.  WfMoments (the
@@ -419,7 +419,7 @@ PT_HD int wf_finish(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, const W
             }
             W->acc[0] = acc.x; W->acc[1] = acc.y; W->acc[2] = acc.z;
             W->set(kWfDone, false, 0);
-            return false;
+            return kWfNextNone;
         }
         W->si = 0;
         W->set(kWfBegin, false, 0);   // (b = 0; begin_bounce sets the state)
@@ -431,9 +431,9 @@ PT_HD int wf_finish(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, const W
         sp.put3(kSpP0, P0);
         sp.put3(kSpP, P0);
         sp.put3(kSpNd, d0);   // incoming direction of bounce 0 (main.py:191)
-        return true;
+        return kWfNextBounce;
     }
-    if (W->state() != kWfBounce) return false;
+    if (W->state() != kWfBounce) return kWfNextNone;
     // the colour of the pending bounce (main.py:208-231)
     ShadowSet sh;
 #pragma unroll
@@ -492,14 +492,10 @@ PT_HD int wf_finish(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, const W
     W->si = si;
     if (si >= J.n_samples) {
         W->set(kWfDone, false, 0);
-        return false;
+        return kWfNextNone;
     }
     W->set(kWfBegin, false, b);   // (begin_bounce sets the state and trace)
-    return true;
-}
-PT_HD bool wf_finish(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, const WfShadowQ* shq,
-                     const WfClosestQ* cq, const WfClosestQ* pq) {
-    return wf_finish(S, J, d0, W, shq, cq, pq, WfSum{});
+    return kWfNextBounce;
 }
 
 // Shade step >= 1: wf_finish, then the next bounce's start.  Returns the
@@ -509,7 +505,7 @@ PT_HD bool wf_finish(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, const 
 template <bool KEY = false, class Home = WfSum>
 PT_HD uint32_t wf_shade(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, WfShadowQ* shq,
                         WfClosestQ* cq, const WfClosestQ* pq, Home home = Home{}) {
-    return wf_finish(S, J, d0, W, shq, cq, pq, home) ? wf_begin_bounce<KEY>(S, J, W, shq, cq) : 0u;
+    return wf_finish(S, J, d0, W, shq, cq, pq, home) == kWfNextBounce ? wf_begin_bounce<KEY>(S, J, W, shq, cq) : 0u;
 }
 // The antialiased shade step: after wf_finish either the next bounce's start
 // or the next sample's primary query (X: the slot's pixel, for aa_dir).
@@ -519,6 +515,75 @@ PT_HD uint32_t wf_shade_aa(const SceneK& S, const LaneJob& J, const AaPixel& X, 
     const int next = wf_finish<Home, true>(S, J, d3(0, 0, 0), W, shq, cq, nullptr, home);
     if (next == kWfNextBounce) return wf_begin_bounce<KEY>(S, J, W, shq, cq);
     return next == kWfNextPrimary ? wf_aa_start(S, J, X, W, cq) : 0u;
+}
+
+// Where the slots of a launch get their jobs (pt_job.h): the pixels of a
+// frame, `split` slots each, or the entries of an accumulator pass's active
+// list.  n_prim(): the launch's primary queries, one per pixel / entry.
+struct WfFrame {
+    const RenderK& R;
+    PT_HD SlotJob job(const SceneK& S, uint32_t tid) const { return slot_job(S, R, tid); }
+    PT_HD uint32_t n_prim() const { return R.npix; }
+};
+struct WfActive {
+    const ListK& R;
+    const uint32_t* list;
+    const uint32_t* accN;
+    PT_HD ListJob job(const SceneK& S, uint32_t tid) const { return list_job(S, R, list, accN, tid); }
+    PT_HD uint32_t n_prim() const { return R.n_list; }
+};
+
+// The primary query of pixel / entry `entry` (centre rays: its `split` slots
+// share it, main.py:191): the uniform part of the eye ray into CQP[entry],
+// the spill home in the entry's first slot.  Returns the queries wanted.
+template <class Src>
+PT_HD uint32_t wf_primary_step(const SceneK& S, const Src& src, uint32_t entry, WfPath* W, WfClosestQ* CQP) {
+    if (entry >= src.n_prim()) return 0u;
+    const uint32_t slot = entry << src.R.split_log2;
+    const auto j = src.job(S, slot);
+    return j.valid ? wf_start(S, j.J, j.d0, &W[slot], &CQP[entry]) : 0u;
+}
+
+// One shade step of slot tid < slots (the four shade kernels' body, and the
+// host checks').  Returns the queries wanted, the shadow list's sort key
+// (wf_cell) in bits 16..27.
+// Step 0 initialises the slot, and its sums where the home has some: the
+// buffers hold the state of an earlier pass or render.  Centre rays: the
+// primary queries are wf_primary_step's, one per pixel / entry.  AA: no shared
+// primary query — step 0 starts the slot's first sample's own, and every
+// later sample starts in the step that ends the one before it.
+// Later steps: a finished slot costs one load, its job is only built when it
+// runs.
+template <bool AA, class Src, class Home>
+PT_HD uint32_t wf_slot_step(const SceneK& S, const Src& src, int32_t step, uint32_t tid, WfPath* W,
+                            WfShadowQ* SQ, WfClosestQ* CQ, const WfClosestQ* CQP, Home home) {
+    const uint32_t entry = tid >> src.R.split_log2;
+    uint32_t want = 0;
+    if (step == 0) {
+        auto j = src.job(S, tid);
+        if constexpr (Home::kMoments) home.clear();
+        W[tid].acc[0] = W[tid].acc[1] = W[tid].acc[2] = 0.0;
+        W[tid].put_rkey(j.J);
+        const bool go = j.valid && j.J.n_samples > 0 && j.J.bounces > 0;
+        if constexpr (AA) {
+            W[tid].si = 0;
+            W[tid].set(kWfDone, false, 0);
+            j.J.seed = src.R.seed;   // (wave-uniform: aa_jitter's rng_block takes its key in scalar registers)
+            if (go) want = wf_aa_start(S, j.J, AaPixel{src.R.W, src.R.H, j.ix, j.iy}, &W[tid], &CQ[tid]);
+        } else {
+            W[tid].set(go ? kWfPrimary : kWfDone, false, 0);
+        }
+    } else if (entry < src.n_prim() && W[tid].state() != kWfDone) {
+        auto j = src.job(S, tid);
+        if constexpr (AA) {
+            j.J.seed = src.R.seed;   // (as in step 0; the slot is valid)
+            want = wf_shade_aa<true>(S, j.J, AaPixel{src.R.W, src.R.H, j.ix, j.iy}, &W[tid], &SQ[tid], &CQ[tid],
+                                     home);
+        } else {
+            want = wf_shade<true>(S, j.J, j.d0, &W[tid], &SQ[tid], &CQ[tid], &CQP[entry], home);
+        }
+    }
+    return want;
 }
 
 }  // namespace pt

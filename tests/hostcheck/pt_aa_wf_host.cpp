@@ -1,6 +1,6 @@
 // pt_aa_wf_host.cpp — TEST INFRASTRUCTURE.  The antialiased wavefront state
-// machine (pt_wavefront.h wf_aa_start / wf_shade_aa; pt_shade.h k_wf_shade_aa,
-// k_wf_shade_list_aa) run on the host, in its uniform form (a whole frame,
+// machine (pt_wavefront.h wf_slot_step<true>, the text k_wf_shade_aa and
+// k_wf_shade_list_aa run) run on the host, in its uniform form (a whole frame,
 // `split` slots per pixel) and its list form (one accumulator pass), with the
 // walk primitives of hc_accum_wf_pass (pt_accum_wf_host.cpp), so the CPU suite
 // can check it against the single kernel's lane code (pt_aa_host.cpp
@@ -21,14 +21,15 @@ struct AaWfBuffers {
 };
 AaWfBuffers g_aa;
 
-// The shade / walk loop over `slots` slots until a shade step finds no work.
-// home_stride > 0: the list form (the slots' six sums in g_aa.home
-// [6][home_stride]).  busy[s] (s < busy_cap): the slots that are not kWfDone
-// after shade step s.  Returns the shade steps that found work.
-int32_t aa_wf_loop(const SceneK& K, const std::vector<LaneJob>& J, const std::vector<AaPixel>& X,
-                   const std::vector<char>& valid, size_t home_stride, int fresh, int32_t* busy,
+// The shade / walk loop over the `slots` slots of src (a WfFrame or a
+// WfActive: the antialiased shade kernels' step, pt_wavefront.h wf_slot_step)
+// until a shade step finds no work.  home_stride > 0: the list form (the
+// slots' six sums in g_aa.home [6][home_stride]).  busy[s] (s < busy_cap): the
+// slots that are not kWfDone after shade step s.  Returns the shade steps that
+// found work.
+template <class Src>
+int32_t aa_wf_loop(const SceneK& K, const Src& src, size_t slots, size_t home_stride, int fresh, int32_t* busy,
                    int32_t busy_cap) {
-    const size_t slots = J.size();
     if (g_aa.W.size() < slots) {
         g_aa.W.resize(slots);
         g_aa.SQ.resize(slots);
@@ -47,33 +48,18 @@ int32_t aa_wf_loop(const SceneK& K, const std::vector<LaneJob>& J, const std::ve
     std::vector<uint32_t> want(slots);
     int32_t worked = 0;
     for (int32_t step = 0;; ++step) {
-        bool any = false;
-        std::fill(want.begin(), want.end(), 0u);
+        bool any = step == 0 && slots > 0;
         for (size_t t = 0; t < slots; ++t) {
-            WfMoments M{{home_stride ? &g_aa.home[t] : nullptr, home_stride}};
-            if (step == 0) {   // k_wf_shade_aa's step 0: the slot, then its first sample's query
-                if (home_stride) M.clear();
-                W[t].acc[0] = W[t].acc[1] = W[t].acc[2] = 0.0;
-                W[t].put_rkey(J[t]);
-                W[t].si = 0;
-                W[t].set(kWfDone, false, 0);
-                if (valid[t] && J[t].n_samples > 0 && J[t].bounces > 0)
-                    want[t] = wf_aa_start(K, J[t], X[t], &W[t], &CQ[t]);
-                any = true;
-            } else if (W[t].state() != kWfDone) {
-                want[t] = home_stride ? wf_shade_aa<false>(K, J[t], X[t], &W[t], &SQ[t], &CQ[t], M)
-                                      : wf_shade_aa<false>(K, J[t], X[t], &W[t], &SQ[t], &CQ[t]);
-                any = true;
-            }
+            any |= W[t].state() != kWfDone;
+            const uint32_t w =
+                home_stride ? wf_slot_step<true>(K, src, step, (uint32_t)t, W, SQ, CQ, nullptr,
+                                                 WfMoments{{&g_aa.home[t], home_stride}})
+                            : wf_slot_step<true>(K, src, step, (uint32_t)t, W, SQ, CQ, nullptr, WfSum{});
+            want[t] = w & 0xffffu;
         }
         if (!any) break;
         ++worked;
-        for (size_t t = 0; t < slots; ++t) {
-            const Spill sp{W[t].sp, 1};
-            for (int k = 0; k < kLightSamples; ++k)
-                if ((want[t] >> k) & 1u) walk_shadow(K, &SQ[t], k, sp);
-            if (want[t] & kWfWantClosest) walk_closest(K, &CQ[t], sp);
-        }
+        run_walks(K, want, W, SQ, CQ);
         if (step < busy_cap) {
             int32_t b = 0;
             for (size_t t = 0; t < slots; ++t) b += W[t].state() != kWfDone;
@@ -99,28 +85,9 @@ int hc_aa_wf_render(const pt_scene_desc* d, const pt_render_params* p, uint32_t 
     if (!prepare_scene(d, &H).empty()) return -1;
     bind_host(&H);
     if (H.k.n_bnode == 0 || H.k.n_qnode == 0 || H.k.qstack > kBvhStack) return -3;
-    uint32_t slog = 0;
-    while ((1u << slog) < split) ++slog;
-    const uint32_t npix = (uint32_t)p->width * (uint32_t)p->height;
-    const size_t slots = (size_t)npix << slog;
-    std::vector<LaneJob> J(slots);
-    std::vector<AaPixel> X(slots);
-    std::vector<char> valid(slots, 1);
-    for (size_t t = 0; t < slots; ++t) {   // slot_job
-        const uint32_t pl = (uint32_t)(t >> slog);
-        const int32_t c = (int32_t)(t & (split - 1u)), sp = (int32_t)split;
-        const int32_t iy = (int32_t)(pl / (uint32_t)p->width), ix = (int32_t)pl - iy * p->width;
-        X[t] = AaPixel{p->width, p->height, ix, iy};
-        J[t] = LaneJob{};
-        J[t].seed = p->seed;
-        J[t].pixel = (uint32_t)ix * (uint32_t)p->height + (uint32_t)iy;
-        J[t].sample0 = p->sample_begin + c;
-        J[t].sample_stride = sp;
-        J[t].n_samples = c < p->spp ? (p->spp - c + sp - 1) / sp : 0;
-        J[t].bounces = p->bounces;
-        J[t].rr_depth = rr_of(p);
-    }
-    const int32_t worked = aa_wf_loop(H.k, J, X, valid, 0, fresh, busy, busy_cap);
+    const RenderK R = host_frame(p, 0, 1, p->height, split, rr_of(p));
+    const uint32_t npix = R.npix, slog = R.split_log2;
+    const int32_t worked = aa_wf_loop(H.k, WfFrame{R}, (size_t)npix << slog, 0, fresh, busy, busy_cap);
     for (uint32_t pl = 0; pl < npix; ++pl) {   // k_wf_final
         D3 v[64];
         for (uint32_t c = 0; c < split; ++c) v[c] = ld3(g_aa.W[((size_t)pl << slog) + c].acc);
@@ -137,9 +104,9 @@ int hc_aa_wf_render(const pt_scene_desc* d, const pt_render_params* p, uint32_t 
     return 0;
 }
 
-// hc_accum_wf_pass with antialiased samples (k_wf_shade_list_aa, list_job's
-// mapping, k_wf_final_list): one pass over list[0..n_list) under the rule,
-// `split` slots per entry; S, Q, n read and updated in place.
+// hc_accum_wf_pass with antialiased samples (k_wf_shade_list_aa's step over
+// the active list, k_wf_final_list): one pass over list[0..n_list) under the
+// rule, `split` slots per entry; S, Q, n read and updated in place.
 int hc_aa_wf_pass(const pt_scene_desc* d, const pt_render_params* p, const uint32_t* list, uint32_t n_list,
                   uint32_t min_spp, uint32_t max_spp, uint32_t step_spp, uint32_t split, int fresh,
                   double* accS, double* accQ, uint32_t* accN, int32_t* steps_out, int32_t* busy,
@@ -149,56 +116,11 @@ int hc_aa_wf_pass(const pt_scene_desc* d, const pt_render_params* p, const uint3
     if (!prepare_scene(d, &H).empty()) return -1;
     bind_host(&H);
     if (H.k.n_bnode == 0 || H.k.n_qnode == 0 || H.k.qstack > kBvhStack) return -3;
-    const AdaptK A{0.0, 1.0, min_spp, max_spp, step_spp};
-    uint32_t slog = 0;
-    while ((1u << slog) < split) ++slog;
-    const uint32_t npix = (uint32_t)p->width * (uint32_t)p->height;
-    const size_t slots = (size_t)n_list << slog;
-    std::vector<LaneJob> J(slots);
-    std::vector<AaPixel> X(slots, AaPixel{p->width, p->height, 0, 0});
-    std::vector<char> valid(slots, 0);
-    std::vector<uint32_t> kk(n_list, 0);
-    for (size_t t = 0; t < slots; ++t) {   // list_job
-        const uint32_t entry = (uint32_t)(t >> slog), c = (uint32_t)t & (split - 1u);
-        const uint32_t e = list[entry];
-        J[t] = LaneJob{};
-        J[t].seed = p->seed;
-        J[t].sample_stride = (int32_t)split;
-        J[t].bounces = p->bounces;
-        J[t].rr_depth = rr_of(p);
-        if (e >= npix) continue;
-        valid[t] = 1;
-        const uint32_t n0 = accN[e], k = adapt_k(n0, A);
-        kk[entry] = k;
-        const int32_t row = (int32_t)(e / (uint32_t)p->width);
-        const int32_t ix = (int32_t)e - row * p->width, iy = p->height - 1 - row;
-        X[t].ix = ix;
-        X[t].iy = iy;
-        J[t].pixel = (uint32_t)ix * (uint32_t)p->height + (uint32_t)iy;
-        J[t].sample0 = (int32_t)(n0 + c);
-        J[t].n_samples = c < k ? (int32_t)((k - c + split - 1u) >> slog) : 0;
-    }
-    const int32_t worked = aa_wf_loop(H.k, J, X, valid, slots, fresh, busy, busy_cap);
-    const std::vector<double>& home = g_aa.home;
-    for (uint32_t en = 0; en < n_list; ++en) {   // k_wf_final_list
-        const uint32_t e = list[en];
-        if (e >= npix) continue;
-        double v[6][64];
-        for (uint32_t c = 0; c < split; ++c)
-            for (int i = 0; i < 6; ++i) v[i][c] = home[(size_t)i * slots + ((size_t)en << slog) + c];
-        for (uint32_t m = 1; m < split; m <<= 1)
-            for (int i = 0; i < 6; ++i) {
-                double nv[64];
-                for (uint32_t c = 0; c < split; ++c) nv[c] = v[i][c] + v[i][c ^ m];
-                memcpy(v[i], nv, split * sizeof(double));
-            }
-        if (kk[en] == 0) continue;
-        for (int i = 0; i < 3; ++i) {
-            accS[3 * (size_t)e + i] += v[i][0];
-            accQ[3 * (size_t)e + i] += v[3 + i][0];
-        }
-        accN[e] += kk[en];
-    }
+    const ListK R = host_list(p, n_list, AdaptK{0.0, 1.0, min_spp, max_spp, step_spp}, split);
+    const WfActive src{R, list, accN};
+    const size_t slots = (size_t)R.lanes;
+    const int32_t worked = aa_wf_loop(H.k, src, slots, slots, fresh, busy, busy_cap);
+    final_list(H.k, src, g_aa.home.data(), accS, accQ, accN);
     if (steps_out) *steps_out = worked;
     return 0;
 }

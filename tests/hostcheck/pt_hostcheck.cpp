@@ -21,6 +21,23 @@
 
 using namespace pt;
 
+// The launch record of the rows first, first + row_step, ... (n_rows of them)
+// of p's frame with `split` slots per pixel, as pt_render_device fills it
+// (the fields the wavefront kernels read).
+static RenderK host_frame(const pt_render_params* p, int32_t first, int32_t row_step, int32_t n_rows,
+                          uint32_t split, int32_t rr_depth) {
+    RenderK R{};
+    R.W = p->width; R.H = p->height; R.spp = p->spp; R.bounces = p->bounces;
+    R.seed = p->seed;
+    R.rr_depth = rr_depth;
+    R.first_row = first; R.row_step = row_step; R.n_rows = n_rows;
+    R.sample_begin = p->sample_begin;
+    R.split = split;
+    R.split_log2 = log2_ceil(split);
+    R.npix = (uint32_t)n_rows * (uint32_t)p->width;
+    return R;
+}
+
 extern "C" {
 
 // sizes and field offsets of the C-ABI structs as the C++ compiler lays
@@ -179,42 +196,21 @@ int hc_render_wavefront3(const pt_scene_desc* d, const pt_render_params* p, doub
     int32_t first, rows;
     if (!band_layout(p, &first, &rows)) return -2;
     const size_t n = (size_t)rows * p->width;
+    const RenderK R = host_frame(p, first, p->row_step, rows, 1, (p->flags & PT_FLAG_RR) ? p->rr_depth : -1);
+    const WfFrame src{R};
+    // (split = 1: a pixel's primary query is its one slot's own, CQP = CQ)
     std::vector<WfPath> W(n);
     std::vector<WfShadowQ> SQ(n);
     std::vector<WfClosestQ> CQ(n);
-    std::vector<LaneJob> J(n);
-    std::vector<D3> D0(n);
-    for (int r = 0; r < rows; ++r) {
-        const int iy = first + r * p->row_step;
-        for (int ix = 0; ix < p->width; ++ix) {
-            const size_t i = (size_t)r * p->width + ix;
-            const D3 eye = ld3(H.k.eye);
-            const double x = linspace_at(H.k.ortho[0], H.k.ortho[2], p->width, ix);
-            const double y = linspace_at(H.k.ortho[1], H.k.ortho[3], p->height, iy);
-            D0[i] = d3(x - eye.x, y - eye.y, 0.0 - eye.z);
-            J[i].seed = p->seed;
-            J[i].pixel = (uint32_t)ix * (uint32_t)p->height + (uint32_t)iy;
-            J[i].sample0 = p->sample_begin;
-            J[i].sample_stride = 1;
-            J[i].n_samples = p->spp;
-            J[i].bounces = p->bounces;
-            J[i].rr_depth = (p->flags & PT_FLAG_RR) ? p->rr_depth : -1;
-        }
-    }
     std::vector<uint32_t> want(n);
     int32_t busy = 0;
     for (int step = 0;; ++step) {
         bool any = false;
-        for (size_t i = 0; i < n; ++i) {
-            want[i] = 0;
-            if (step == 0) {   // (k_wf_shade's step 0: the slot's RNG key, then k_wf_primary)
-                W[i].put_rkey(J[i]);
-                want[i] = wf_start(H.k, J[i], D0[i], &W[i], &CQ[i]);
-            }
-            else if (W[i].state() != kWfDone) {
-                want[i] = wf_shade(H.k, J[i], D0[i], &W[i], &SQ[i], &CQ[i], &CQ[i]);
-                any = true;
-            }
+        for (size_t i = 0; i < n; ++i) {   // the shade kernel's step, then (step 0) the primary kernel's
+            any |= step > 0 && W[i].state() != kWfDone;
+            want[i] = wf_slot_step<false>(H.k, src, step, (uint32_t)i, W.data(), SQ.data(), CQ.data(), CQ.data(),
+                                          WfSum{}) & 0xffffu;
+            if (step == 0) want[i] = wf_primary_step(H.k, src, (uint32_t)i, W.data(), CQ.data());
         }
         if (step > 0 && !any) break;
         ++busy;
