@@ -18,6 +18,7 @@
 #include "../../pathtracerpython_amd/csrc/pt_path.h"
 #include "../../pathtracerpython_amd/csrc/pt_wavefront.h"
 #include "../../pathtracerpython_amd/csrc/pt_prepare.h"
+#include "../devcheck/filter_eval.h"
 
 using namespace pt;
 
@@ -305,13 +306,36 @@ int hc_bvh_info(const pt_scene_desc* d, int32_t* out) {
     return 0;
 }
 
-// Filter self-test: random lines (origins at the eye or on triangles,
-// directions random) against every triangle; compares classify() with the
-// f64 evaluation.  out[0] = wrong certain verdicts (must be 0), out[1] =
-// ambiguous verdicts, out[2] = tests, out[3] = certain candidates, out[4] =
-// shadow tests where the margin form (margin_plane/margin_tri) differs from
-// classify_tri other than by "ambiguous" for a certain miss (must be 0).
-int hc_filter_selftest(const pt_scene_desc* d, int64_t n_rays, uint64_t seed, int64_t* out) {
+}   // extern "C"
+struct FilterArrays {   // hc_filter_cases' arrays: [n] lines, results as ptcheck::FilterOut
+    double* o; double* dn; double* lim;
+    float* hlo; float* hhi;
+    int32_t* at_eye;
+    ptcheck::FilterOut out;
+    int8_t* near;   // [n][nu][2] eval64_near, or null
+};
+// eval64's decisions of this line and triangle within `rel` (relative) of
+// their thresholds: |n.d| against 1e-5, the two weight products against 0
+// (relative to their factors' lengths), sqd against 1e-5 and against lim —
+// a build whose reciprocal differs in the last place may decide these the
+// other way, so the device check compares its eval64 on the others.
+static bool eval64_near(const TriD& T, D3 o, D3 dn, double lim, double rel) {
+    const D3 vp = ld3(T.vp);
+    const double den = fabs(dot(dn, vp));
+    if (fabs(den - kZero) <= rel * kZero) return true;
+    if (!(den > kZero)) return false;
+    const D3 p = plane_point(T, o, dn);
+    const D3 c1 = cross(ld3(T.e12), p - ld3(T.v2));
+    const D3 c2 = cross(ld3(T.e23), p - ld3(T.v3));
+    const D3 c3 = cross(ld3(T.e31), p - ld3(T.v1));
+    const double n1 = sqrt(dot(c1, c1)), n2 = sqrt(dot(c2, c2)), n3 = sqrt(dot(c3, c3));
+    if (fabs(dot(c1, c2)) <= rel * n1 * n2 || fabs(dot(c1, c3)) <= rel * n1 * n3) return true;
+    const double sqd = squared_dist(p, o);
+    return fabs(sqd - kZero) <= rel * kZero || fabs(sqd - lim) <= rel * lim;
+}
+// the self-test's loop: the lines, filter_line on each, the tally (X: hc_filter_cases' arrays, or null)
+static int filter_run(const pt_scene_desc* d, int64_t n_rays, uint64_t seed, int64_t* out,
+                      const FilterArrays* X) {
     HostScene H;
     if (!prepare_scene(d, &H).empty()) return -1;
     bind_host(&H);
@@ -319,7 +343,19 @@ int hc_filter_selftest(const pt_scene_desc* d, int64_t n_rays, uint64_t seed, in
     std::uniform_real_distribution<double> U(0.0, 1.0);
     std::normal_distribution<double> N(0.0, 1.0);
     int64_t wrong = 0, amb = 0, tests = 0, cand = 0, mdiff = 0;
-    const D3 C = ld3(H.k.center), Cs = ld3(H.k.center_s);
+    const int nu = H.k.n_unit + H.k.n_bunit;
+    const int kKinds = ptcheck::kKinds;
+    // without arrays from the caller: one line's worth, reused
+    std::vector<double> s_d(7), s_sqd((size_t)nu * 2);
+    std::vector<float> s_f(2), s_atdt((size_t)nu * 4), s_sum((size_t)H.k.n_obj_unit * ptcheck::kSumN + 1);
+    std::vector<int8_t> s_code((size_t)nu * 2 * kKinds), s_hit((size_t)nu * 2), s_mflag(nu);
+    int32_t s_eye = 0;
+    FilterArrays L = X ? *X : FilterArrays{s_d.data(), s_d.data() + 3, s_d.data() + 6, s_f.data(),
+                                           s_f.data() + 1, &s_eye,
+                                           {s_code.data(), s_hit.data(), s_sqd.data(), s_atdt.data(),
+                                            s_mflag.data(), s_sum.data()}, nullptr};
+    const ptcheck::FilterLines LC = {L.o, L.dn, L.lim, L.hlo, L.hhi, L.at_eye};
+    const ptcheck::FilterOut& F = L.out;
     for (int64_t i = 0; i < n_rays; ++i) {
         D3 o;
         if (i % 4 == 0) {
@@ -345,89 +381,129 @@ int hc_filter_selftest(const pt_scene_desc* d, int64_t n_rays, uint64_t seed, in
         }
         const D3 dn = unit(dir);
         const bool at_eye = i % 4 == 0;
-        // frames: the eye's origins test unit_eye, surface origins `unit`
-        // (surface frame); the BVH units are in the frame with the eye
-        const F3 o32 = to_f3(o - C), o32s = to_f3(o - Cs), d32 = to_f3(dn);
         const double lim = 0.5 + 40.0 * U(rng);   // a shadow range
         const float hlo = (float)(sqrt(lim) * (1 - 1e-6)), hhi = (float)(sqrt(lim) * (1 + 1e-6));
-        for (int u = 0; u < H.k.n_unit + H.k.n_bunit; ++u) {   // uniform and BVH units
-            const bool uni = u < H.k.n_unit;
-            const UnitF& U = uni ? (at_eye ? H.unit_eye[u] : H.unit[u]) : H.bunit[u - H.k.n_unit];
-            const OriginU O = origin_u(U, (uni && !at_eye) ? o32s : o32);
-            const RayPlane pc = ray_plane(U, O.h, d32, INFINITY, INFINITY);
-            const RayPlane ps = ray_plane(U, O.h, d32, hlo, hhi);
-            for (int i = 0; i < U.count; ++i) {
-                const TriB& B = U.tri[i];
-                const float bo = i ? O.bo1 : O.bo0, co = i ? O.co1 : O.co0;
-                D3 Q; double sqd;
-                const bool h = eval64(H.trid[U.t[i]], o, dn, &Q, &sqd);
-                // closest semantics
-                int st = verdict_code(classify_tri(B, pc, bo, co, d32));
-                const bool ref_c = h && sqd > kZero;
-                ++tests;
-                if (st == kAmb) ++amb;
-                else if ((st == kCand) != ref_c) ++wrong;
-                else if (st == kCand) {
-                    ++cand;
-                    const double sq = sqrt(sqd);   // the |t| interval must cover the truth
-                    if (sq < (double)pc.at - pc.dt || sq > (double)pc.at + pc.dt) ++wrong;
-                }
-                // shadow semantics
-                st = verdict_code(classify_tri(B, ps, bo, co, d32));
-                const bool ref_s = h && !(sqd < kZero) && sqd < lim;
-                ++tests;
-                if (st == kAmb) ++amb;
-                else if ((st == kCand) != ref_s) ++wrong;
-                // the render loop's margin form (shadow_unit_m) of the same test
-                float cm, nm, mc, ma;
-                margin_plane(U, ps, hlo, hhi, INFINITY, &cm, &nm);
-                margin_tri(B, ps, bo, co, d32, cm, nm, &mc, &ma);
-                const int ms = mc > 0.0f ? kCand : (ma >= 0.0f ? kAmb : kMiss);
-                if (ms != kAmb && (ms == kCand) != ref_s) ++wrong;
-                if (ms != st && !(st == kMiss && ms == kAmb)) ++mdiff;
+        // the line's slots: the caller's arrays, or one line's scratch
+        const int64_t at = X ? i : 0;
+        const double od[3] = {o.x, o.y, o.z}, dd[3] = {dn.x, dn.y, dn.z};
+        memcpy(L.o + 3 * at, od, sizeof od);
+        memcpy(L.dn + 3 * at, dd, sizeof dd);
+        L.lim[at] = lim;
+        L.hlo[at] = hlo;
+        L.hhi[at] = hhi;
+        L.at_eye[at] = at_eye ? 1 : 0;
+        // frames: the eye's origins test unit_eye, surface origins `unit`
+        // (surface frame); the BVH units are in the frame with the eye
+        ptcheck::filter_line(H.k, LC, at, F, true);
+        if (X && X->near)   // which f64 decisions another arithmetic may take the other way
+            for (int u = 0; u < nu; ++u) {
+                const bool uni = u < H.k.n_unit;
+                const UnitF& Un = uni ? H.unit[u] : H.bunit[u - H.k.n_unit];
+                for (int m = 0; m < 2; ++m)
+                    X->near[(at * nu + u) * 2 + m] =
+                        m < Un.count && eval64_near(H.trid[Un.t[m]], o, dn, lim, 1e-12) ? 1 : 0;
             }
-            if (uni) {   // the render loop's unit form (quad_m): both members' tests
-                float cm, nm;
-                margin_plane(U, ps, hlo, hhi, INFINITY, &cm, &nm);
-                const OriginU Oq = origin_q(U, at_eye ? o32 : o32s);
-                const QuadM qs = quad_m(U, ps, Oq, d32), qc = quad_m(U, pc, Oq, d32);
-                {   // the merged unit margins (PT_MMERGE, margin_unit) against the members'
-                    float c0, a0, c1, a1, cu, au;
-                    margin_m(qs.m0, ps, cm, nm, &c0, &a0);
-                    margin_m(qs.m1, ps, cm, nm, &c1, &a1);
-                    margin_unit(cm, nm, fmaxf(qs.m0, qs.m1), ps.del, &cu, &au);
-                    const bool occ = c0 > 0.0f || c1 > 0.0f;
-                    if ((cu > 0.0f) != occ) ++mdiff;                           // occlusion: same verdict
-                    if (!occ && (a0 >= 0.0f || a1 >= 0.0f) && !(au >= 0.0f)) ++mdiff;   // no lost f64 test
+        // the tally: this build's verdicts against its own eval64
+        for (int u = 0; u < nu; ++u) {
+            const bool uni = u < H.k.n_unit;
+            const int64_t lu = at * nu + u;
+            for (int m = 0; m < 2; ++m) {
+                const int8_t* c = F.code + (lu * 2 + m) * kKinds;
+                const bool h = F.hit[lu * 2 + m] != 0;
+                const double sqd = F.sqd[lu * 2 + m];
+                const bool ref_c = h && sqd > kZero;                       // closest semantics
+                const bool ref_s = h && !(sqd < kZero) && sqd < lim;      // shadow semantics
+                if (c[ptcheck::kClosest] >= 0) {   // a member triangle: the single-triangle forms
+                    int st = c[ptcheck::kClosest];
+                    ++tests;
+                    if (st == kAmb) ++amb;
+                    else if ((st == kCand) != ref_c) ++wrong;
+                    else if (st == kCand) {
+                        ++cand;
+                        const double sq = sqrt(sqd);   // the |t| interval must cover the truth
+                        const float pat = F.atdt[lu * 4], pdt = F.atdt[lu * 4 + 1];
+                        if (sq < (double)pat - pdt || sq > (double)pat + pdt) ++wrong;
+                    }
+                    st = c[ptcheck::kShadow];
+                    ++tests;
+                    if (st == kAmb) ++amb;
+                    else if ((st == kCand) != ref_s) ++wrong;
+                    // the render loop's margin form (shadow_unit_m) of the same test
+                    const int ms = c[ptcheck::kMarginF];
+                    if (ms != kAmb && (ms == kCand) != ref_s) ++wrong;
+                    if (ms != st && !(st == kMiss && ms == kAmb)) ++mdiff;
                 }
-                for (int i = 0; i < 2; ++i) {
-                    D3 Q; double sqd;
-                    const bool h = i < U.count && eval64(H.trid[U.t[i]], o, dn, &Q, &sqd);
-                    float mc, ma;
-                    margin_m(i ? qs.m1 : qs.m0, ps, cm, nm, &mc, &ma);
-                    const int ms = mc > 0.0f ? kCand : (ma >= 0.0f ? kAmb : kMiss);
-                    const bool ref_s = h && !(sqd < kZero) && sqd < lim;
+                if (uni) {   // the render loop's unit form (quad_m): both members' tests
+                    const int ms = c[ptcheck::kQuadShadow];
                     ++tests;
                     if (ms == kAmb) ++amb;
                     else if ((ms == kCand) != ref_s) ++wrong;
-                    const int vc = verdict_code(verdict_m(i ? qc.m1 : qc.m0, pc));
-                    const bool ref_c = h && sqd > kZero;
+                    const int vc = c[ptcheck::kQuadClosest];
                     ++tests;
                     if (vc == kAmb) ++amb;
                     else if ((vc == kCand) != ref_c) ++wrong;
-                    {   // the render loop's lean closest range (PT_CLOSEST_LEAN): no wrong certain verdict
-                        RayPlane pl = pc;
-                        pl.rcand = (fabsf(pl.q) > U.qhi) & (pl.at - pl.dt > kTzHi);
-                        pl.rmiss = pl.at + pl.dt < kTzLo;
-                        const int vl = verdict_code(verdict_m(i ? qc.m1 : qc.m0, pl));
-                        if (vl != kAmb && (vl == kCand) != ref_c) ++wrong;
-                        if (vl != vc && !(vc == kMiss && vl == kAmb)) ++mdiff;
-                    }
+                    // the render loop's lean closest range (PT_CLOSEST_LEAN): no wrong certain verdict
+                    const int vl = c[ptcheck::kLean];
+                    if (vl != kAmb && (vl == kCand) != ref_c) ++wrong;
+                    if (vl != vc && !(vc == kMiss && vl == kAmb)) ++mdiff;
                 }
             }
+            // the merged unit margins (PT_MMERGE, margin_unit) against the members'
+            if (F.mflag[lu] & ptcheck::kMfOcc) ++mdiff;
+            if (F.mflag[lu] & ptcheck::kMfLost) ++mdiff;
         }
     }
     out[0] = wrong; out[1] = amb; out[2] = tests; out[3] = cand; out[4] = mdiff;
+    return 0;
+}
+
+extern "C" {
+// Filter self-test: random lines (origins at the eye or on triangles,
+// directions random) against every triangle; compares classify() with the
+// f64 evaluation.  out[0] = wrong certain verdicts (must be 0), out[1] =
+// ambiguous verdicts, out[2] = tests, out[3] = certain candidates, out[4] =
+// shadow tests where the margin form (margin_plane/margin_tri) differs from
+// classify_tri other than by "ambiguous" for a certain miss (must be 0).
+// The tests of a line are filter_eval.h's filter_line (the code the device
+// check compiles for gfx950), tallied here; hc_filter_cases also hands out
+// the lines and the per-test results.
+int hc_filter_selftest(const pt_scene_desc* d, int64_t n_rays, uint64_t seed, int64_t* out) {
+    return filter_run(d, n_rays, seed, out, nullptr);
+}
+
+// The self-test's lines and this build's results of them, for the device
+// check (tests/devcheck dc_filter runs the same lines on the GPU; the host's
+// eval64 here is the truth both builds' verdicts are judged by).  The lines
+// and the tally are hc_filter_selftest's own (one generator, one loop): out[5]
+// as there.  Arrays as in filter_eval.h, n = n_rays, nu = n_unit + n_bunit
+// (hc_filter_dims); near[n][nu][2] = eval64_near at 1e-12.
+int hc_filter_cases(const pt_scene_desc* d, int64_t n_rays, uint64_t seed, double* o, double* dn,
+                    double* lim, float* hlo, float* hhi, int32_t* at_eye, int8_t* code, int8_t* hit,
+                    double* sqd, float* atdt, int8_t* mflag, float* sum, int8_t* near, int64_t* out) {
+    FilterArrays X = {o, dn, lim, hlo, hhi, at_eye, {code, hit, sqd, atdt, mflag, sum}, near};
+    return filter_run(d, n_rays, seed, out, &X);
+}
+
+// out[4] = {n_unit, n_bunit, n_obj_unit, 1 if the BVH units have the 64-B form}
+int hc_filter_dims(const pt_scene_desc* d, int32_t* out) {
+    HostScene H;
+    if (!prepare_scene(d, &H).empty()) return -1;
+    out[0] = H.k.n_unit;
+    out[1] = H.k.n_bunit;
+    out[2] = H.k.n_obj_unit;
+    out[3] = H.bunitc.empty() ? 0 : 1;
+    return 0;
+}
+
+// The host twins of the min / max family (pt_path.h, pt_core.h), raw bits
+// out: out[i][6] = nan_min(a,b), nan_min3(a,b,c), fmax_q(a,b), min3f(a,b,c),
+// med3_q(a,b,c), pt_canon(a) — the layout of devcheck's dc_minmax.
+int hc_minmax(const float* a, const float* b, const float* c, int64_t n, uint32_t* out) {
+    for (int64_t i = 0; i < n; ++i) {
+        const float r[6] = {nan_min(a[i], b[i]), nan_min3(a[i], b[i], c[i]), fmax_q(a[i], b[i]),
+                            min3f(a[i], b[i], c[i]), med3_q(a[i], b[i], c[i]), pt_canon(a[i])};
+        memcpy(out + 6 * i, r, sizeof r);
+    }
     return 0;
 }
 

@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import frames
 from conftest import (golden_renders, hc_render, multi_mesh_scene, quad_scene, random_scene,
                       scene_golden_ids, scene_goldens, scene_of_golden)
 from oracle import oracle
@@ -126,13 +127,18 @@ def test_sample_split_is_linear(hostcheck, packed):
 # Objects with >= 64 triangles are traversed through the BVH (pt_prepare.h
 # build_bvh, pt_path.h bvh_pass): results and the reference's work counters
 # must not depend on it.
-def _bvh_case(hostcheck, pk, W, H, spp, B, seed, flags=0):
+def _bvh_case(hostcheck, pk, W, H, spp, B, seed, flags=0, rel_tol=None):
+    """rel_tol: the oracle comparison relative to the frame's maximum, within
+    rel_tol (the scenes off the Cornell frame, frames.py); else 1e-12."""
     p = make_params(W, H, spp, B, seed, flags)
     a, sa = hc_render(hostcheck, pk, p, False)
     b, sb = hc_render(hostcheck, pk, p, True)
     assert np.array_equal(a, b)
     ref, ost = oracle.render(pk, W, H, spp, B, seed, flags)
-    assert np.abs(to_list_order(a) - ref).max() <= 1e-12
+    if rel_tol is None:
+        assert np.abs(to_list_order(a) - ref).max() <= 1e-12
+    else:
+        assert frames.rel_err(to_list_order(a), ref) <= rel_tol
     for k in ("closest_tests", "shadow_tests", "ray_bounces", "shading_points", "light_hits",
               "escapes"):
         assert sa[k] == ost[k] == sb[k], k
@@ -324,3 +330,52 @@ def test_two_meshes_first_in_scene_order(hostcheck, tmp_path, seed):
     _bvh_case(hostcheck, pk, 20, 20, 2, 4, seed)
     _wavefront_case(hostcheck, pk, 20, 20, 2, 4, seed)
     _wavefront_case(hostcheck, pk, 16, 16, 2, 5, seed + 7, PT_FLAG_RR)
+
+
+# ------------------------------------------- off the Cornell frame --
+# Every other scene here lives in the Cornell room's coordinates (extent ~19
+# about a centre near the origin), and all of the filter's bounds and the
+# boxes' inflation scale with the extent: the same checks on the scene scaled
+# and shifted (frames.py).  The bitwise assertions and the counter equalities
+# are the ones above; the oracle comparison is relative to the frame's
+# maximum, with the tolerances of frames.MEASURED (conditioning: a shift by
+# 1e6 leaves ~1e-11 of the room's size to a double).
+@pytest.fixture(scope="module")
+def off_frame_base(packed, tmp_path_factory):
+    return {"cornell": packed,
+            "mesh": pack_scene(random_scene(tmp_path_factory.mktemp("offframe"), 300, 21))}
+
+
+@pytest.mark.parametrize("fname", [f[0] for f in frames.FRAMES])
+@pytest.mark.parametrize("scene", ["cornell", "mesh"])
+def test_host_checks_off_the_cornell_frame(hostcheck, off_frame_base, scene, fname):
+    _, s, tx, ty = frames.frame(fname)
+    pk = frames.transformed(off_frame_base[scene], s, tx, ty)
+    W, H, spp, B, seed = frames.FRAME
+    _bvh_case(hostcheck, pk, W, H, spp, B, seed, rel_tol=frames.oracle_tol(scene, fname))
+    wrong, amb, tests, cand = selftest(hostcheck, pk, 1000, 3)
+    assert wrong == 0 and cand > 0
+    if scene != "mesh":
+        return
+    _wavefront_case(hostcheck, pk, W, H, spp, B, seed)
+    out = (C.c_int64 * 4)()
+    assert hostcheck.hc_bvh_check(C.byref(pk.desc), C.c_int64(100), C.c_uint64(3), out) == 0
+    bad, missed, checked, nodes = list(out)
+    assert nodes > 1 and bad == 0
+    assert checked > 100 and missed == 0
+    out = (C.c_int64 * 5)()
+    assert hostcheck.hc_qbvh_check(C.byref(pk.desc), C.c_int64(100), C.c_uint64(3), out) == 0
+    missed, checked, nq, slab_diff, slab_n = list(out)
+    assert nq > 1 and checked > 100 and missed == 0
+    assert slab_n > 1000 and slab_diff == 0
+
+
+def test_transformed_scene_is_the_scene_moved(packed):
+    """frames.transformed: vertices, eye and window scaled then shifted in x
+    and y, areas by s^2, normals and the screen plane (z = 0) untouched."""
+    q = frames.transformed(packed, 1e-2, 1e4, -3.0)
+    assert np.array_equal(q.tri_v, packed.tri_v * 1e-2 + np.array([1e4, -3.0, 0.0]))
+    assert np.array_equal(q.tri_n, packed.tri_n) and np.array_equal(q.tri_area, packed.tri_area * 1e-4)
+    assert list(q.desc.eye) == list(packed.eye * 1e-2 + np.array([1e4, -3.0, 0.0]))
+    assert list(q.desc.ortho) == list(packed.ortho * 1e-2 + np.array([1e4, -3.0, 1e4, -3.0]))
+    assert q.tri_v is not packed.tri_v and q.desc.n_tri == packed.desc.n_tri
