@@ -102,6 +102,43 @@ extern "C" {
  * passes would mix two definitions of sample s.  Features and the denoiser
  * keep the centre ray.                                                    */
 #define PT_FLAG_AA (1u << 8)
+/* Thin-lens camera (build extension; v7, additive): depth of
+ * field, a lens point per sample.  The scene is created with a lens
+ * (pt_scene_create_lens): a radius R >= 0 and the z of the focal plane zf.
+ * ez = eye[2]; the screen is the plane z = 0.  Sample s (absolute, as for
+ * PT_FLAG_AA) of pixel k = ix*H + iy:
+ *  1. Block: (w0, w1, w2, w3) = Philox4x32-10(key = seed,
+ *     ctr = (k, s, 0xFFFFFFFF, 0)) — PT_FLAG_AA's jitter block; words 2 and 3
+ *     are the lens's.
+ *  2. Jitter: with PT_FLAG_AA (jx, jy) as in its rule; without it jx = jy = 0.
+ *  3. Lens point: r = R * sqrt_d(u_of(w2)); phi = 6.283185307179586 * u_of(w3);
+ *     (sn, cs) = sincos_small(phi); lx = r*cs; ly = r*sn;
+ *     ex' = eye.x + lx; ey' = eye.y + ly; ez' = ez.  (sqrt_d, sincos_small:
+ *     csrc/pt_math.h — within 3 ulp and 2^-52 absolute of the exact values.)
+ *  4. Window: kappa = (0 - zf)/(ez - zf) (the lens offset scaled from the
+ *     lens plane to z = 0, the focal plane being the fixed point);
+ *     bx = jx*dx + lx*kappa; by = jy*dy + ly*kappa (dx, dy: PT_FLAG_AA's pixel
+ *     spacing); x0' = x0 + bx; x1' = x1 + bx; the same for y.
+ *  5. Primary ray: x = linspace_at(x0', x1', W, ix), y likewise,
+ *     d0 = (x - ex', y - ey', 0 - ez), origin eye'.
+ *  6. The rest of sample s is unchanged, except that eye' stands wherever the
+ *     sample reads the eye (the specular term of the bounce included).  An
+ *     escape contributes 0, a light hit light_rgb, per sample; bounces <= 0
+ *     gives 0.
+ * Every f64 operation is rounded on its own.  So sample s of pixel k is the
+ * reference's sample on a descriptor with eye = eye' and ortho = (x0', y0',
+ * x1', y1'); it depends on (seed, k, s, R, zf) only.  R = 0 is the pinhole
+ * (with PT_FLAG_AA: the antialiased render, bit for bit); zf = 0 moves only the
+ * eye.  The aperture is a uniform disc by the polar map.
+ * The flag on a scene without a lens is PT_EINVAL; a lens scene rendered
+ * without the flag is the pinhole render.  Allowed beside it: PT_FLAG_AA,
+ * PT_FLAG_RR, PT_FLAG_FORCE_F64, PT_FLAG_OUT_F64, PT_FLAG_MEGAKERNEL; with
+ * PT_FLAG_COUNT, PT_FLAG_WALK_COUNT or PT_FLAG_KERNEL_TIMES it is PT_EINVAL.
+ * Every launch with the flag takes the single kernel (scenes with a BVH
+ * included; the wavefront form is not built).  An accumulator remembers the
+ * bit as it remembers PT_FLAG_AA and refuses a mixed pass.  Features and the
+ * denoiser keep the centre ray from the eye.                               */
+#define PT_FLAG_LENS (1u << 9)
 
 /*
  * Flattened scene, as produced by scene_reader.Scene
@@ -202,6 +239,19 @@ int pt_device_count(int32_t* count);
 int pt_scene_create(const pt_scene_desc* desc, pt_scene** out);
 /* Same, on HIP device `device` (the current device is left unchanged). */
 int pt_scene_create_on(const pt_scene_desc* desc, int32_t device, pt_scene** out);
+/* Same, with a thin lens (PT_FLAG_LENS; v7, additive).  The f32 filter's
+ * "all" frame — the box every primary ray's origin lies in — is extended by
+ * eye.x +- radius, eye.y +- radius before its centre, half extent and the
+ * error bounds that grow with them are derived; the surface frame is
+ * untouched.  Requires radius and focus_z finite, radius >= 0, eye[2] != 0 and
+ * tau = (eye[2] - focus_z)/eye[2] finite and > 0 (the focal plane on the
+ * screen's side of the eye), PT_EINVAL otherwise.  device -1: the current
+ * device, as pt_scene_create.  lens == NULL: exactly pt_scene_create_on. */
+typedef struct pt_lens {
+    double radius, focus_z;
+} pt_lens;
+int pt_scene_create_lens(const pt_scene_desc* desc, int32_t device, const pt_lens* lens,
+                         pt_scene** out);
 void pt_scene_destroy(pt_scene* scene);
 
 /* Number of rows a launch with these params renders. */
@@ -302,8 +352,9 @@ int pt_accum_select(pt_accum* acc, const pt_adapt_params* a, void* stream,
  * row_begin 0, row_end height, row_step 1, row_phase 0, sample_begin 0,
  * out_row_stride 0, lanes_per_pixel 0, flags within PT_FLAG_RR |
  * PT_FLAG_FORCE_F64 | PT_FLAG_MEGAKERNEL | PT_FLAG_WALK_COUNT |
- * PT_FLAG_KERNEL_TIMES | PT_FLAG_AA (one value of PT_FLAG_AA between resets,
- * see the flag); anything else is PT_EINVAL.  Scenes with a BVH run
+ * PT_FLAG_KERNEL_TIMES | PT_FLAG_AA | PT_FLAG_LENS (one value of PT_FLAG_AA
+ * and one of PT_FLAG_LENS between resets, see the flags; a PT_FLAG_LENS pass
+ * takes the single kernel); anything else is PT_EINVAL.  Scenes with a BVH run
  * the pass through the wavefront kernels (shade, sort and walk steps over the
  * slots of the listed pixels) under pt_render_device's conditions, and
  * through the single kernel with PT_FLAG_MEGAKERNEL or PT_FLAG_FORCE_F64;

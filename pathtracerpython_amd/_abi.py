@@ -20,6 +20,7 @@ PT_FLAG_WALK_COUNT = 1 << 5
 PT_FLAG_KERNEL_TIMES = 1 << 6
 # bit 7: reserved (v4's PT_FLAG_TREE_WALK, retired in v5)
 PT_FLAG_AA = 1 << 8   # antialiasing: a jittered primary ray per sample
+PT_FLAG_LENS = 1 << 9   # thin lens: a lens point per sample (a scene created with a lens)
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -34,6 +35,19 @@ class PtSceneDesc(C.Structure):
         ("eye", C.c_double * 3), ("ortho", C.c_double * 4),
         ("ambient", C.c_double), ("light_rgb", C.c_double * 3),
     ]
+
+
+class PtLens(C.Structure):
+    """pt_lens (include/pt_capi.h): the aperture radius and the focal plane's z."""
+    _fields_ = [("radius", C.c_double), ("focus_z", C.c_double)]
+
+
+def make_lens(lens):
+    """pt_lens of (R, zf)."""
+    R, zf = lens
+    L = PtLens()
+    L.radius, L.focus_z = float(R), float(zf)
+    return L
 
 
 class PtRenderParams(C.Structure):

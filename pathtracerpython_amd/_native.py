@@ -7,7 +7,7 @@ raise `NativeError` — loudly, never silently.
 import ctypes as C
 import os
 
-from ._abi import PtAccumBand, PtAdaptParams, PtDenoiseParams, PtMesh, PtRenderParams, PtSceneDesc, PtStats  # noqa: F401 (PtMesh re-exported)
+from ._abi import PtAccumBand, PtAdaptParams, PtDenoiseParams, PtLens, PtMesh, PtRenderParams, PtSceneDesc, PtStats  # noqa: F401 (PtMesh re-exported)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PT_HIP_LIB", os.path.join(HERE, "_lib", "libpt_hip.so"))
@@ -31,6 +31,7 @@ def _bind(lib):
         "pt_device_count": ([ip], C.c_int),
         "pt_scene_create": ([C.POINTER(PtSceneDesc), C.POINTER(vp)], C.c_int),
         "pt_scene_create_on": ([C.POINTER(PtSceneDesc), C.c_int32, C.POINTER(vp)], C.c_int),
+        "pt_scene_create_lens": ([C.POINTER(PtSceneDesc), C.c_int32, C.POINTER(PtLens), C.POINTER(vp)], C.c_int),
         "pt_render_multi": ([C.POINTER(vp), C.c_int32, C.POINTER(PtRenderParams), vp,
                              C.POINTER(PtStats)], C.c_int),
         "pt_scene_destroy": ([vp], None),
@@ -87,7 +88,7 @@ def _bind(lib):
 
 EXPORTS = ("pt_api_version", "pt_last_error", "pt_build_id", "pt_test_fault_inject",
            "pt_device_count", "pt_scene_create",
-           "pt_scene_create_on", "pt_render_multi", "pt_scene_destroy", "pt_band_rows",
+           "pt_scene_create_on", "pt_scene_create_lens", "pt_render_multi", "pt_scene_destroy", "pt_band_rows",
            "pt_render_device", "pt_render", "pt_last_kernel_ms", "pt_intersect_objects", "pt_compute_color",
            "pt_image_u8_device", "pt_image_u8", "pt_assemble_bands_device", "pt_host_map",
            "pt_host_unmap", "pt_signal", "pt_wait_flags", "pt_obj_load", "pt_mesh_free",

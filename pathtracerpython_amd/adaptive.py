@@ -35,9 +35,9 @@ import weakref
 import numpy as np
 
 from . import _native
-from ._abi import (PT_FLAG_AA, PT_FLAG_FORCE_F64, PT_FLAG_MEGAKERNEL, PT_FLAG_OUT_F64, PT_FLAG_RR, PtAccumBand,
+from ._abi import (PT_FLAG_AA, PT_FLAG_FORCE_F64, PT_FLAG_LENS, PT_FLAG_MEGAKERNEL, PT_FLAG_OUT_F64, PT_FLAG_RR, PtAccumBand,
                    PtStats, band_pixels, make_adapt, make_band, make_denoise, make_params)
-from .progressive import scene_fingerprint
+from .progressive import lens_of, scene_fingerprint
 
 
 class AdaptiveResult:
@@ -373,22 +373,25 @@ class AccumCheckpoint:
             os.remove(self.path)
 
 
-def accum_key(packed, width, height, bounces, seed, rr, rr_depth, lanes_per_pixel, aa=False):
+def accum_key(packed, width, height, bounces, seed, rr, rr_depth, lanes_per_pixel, aa=False, lens=None):
     """AccumCheckpoint's key: what defines sample s of a pixel and the sum
-    order of the moments.  "aa" is present only when antialiasing is on, so
-    the keys and files from before it stay valid."""
+    order of the moments.  "aa" is present only when antialiasing is on and
+    "lens": [R, zf] only when the samples go through a lens, so the keys and
+    files from before them stay valid."""
     key = {"scene": scene_fingerprint(packed), "width": int(width), "height": int(height),
            "bounces": int(bounces), "seed": int(seed), "rr": bool(rr),
            "rr_depth": int(rr_depth), "lanes_per_pixel": int(lanes_per_pixel)}
     if aa:
         key["aa"] = True
+    if lens is not None:
+        key["lens"] = [float(lens[0]), float(lens[1])]
     return key
 
 
 def render_adaptive(renderer, width=None, height=None, max_spp=64, bounces=1, seed=None, rr=False,
                     rr_depth=3, tol=0.05, min_spp=8, step_spp=8, floor=0.01, force_f64=False,
                     on_pass=None, megakernel=False, denoise=None, lanes_per_pixel=0, checkpoint=None,
-                    checkpoint_every=1, max_passes=None, moments=False, aa=False):
+                    checkpoint_every=1, max_passes=None, moments=False, aa=False, lens=None):
     """Render until err <= tol everywhere or a pixel has max_spp samples.
 
     renderer: a render.Renderer.  on_pass(i, n_active, samples_added) after
@@ -406,6 +409,8 @@ def render_adaptive(renderer, width=None, height=None, max_spp=64, bounces=1, se
     checkpoint written).  moments=True: the result also holds S and Q.
     aa=True: antialiasing, every sample has its own jittered primary ray
     (PT_FLAG_AA); the features and the denoiser keep the centre ray.
+    lens: the samples go through the renderer's lens (PT_FLAG_LENS; None: iff
+    it has one); the features and the denoiser keep the pinhole's centre ray.
     Returns an AdaptiveResult."""
     check_rule(tol, max_spp, min_spp, step_spp, floor)
     if denoise is not None and denoise is not True and not isinstance(denoise, dict):
@@ -416,8 +421,10 @@ def render_adaptive(renderer, width=None, height=None, max_spp=64, bounces=1, se
     height = int(renderer.scene.height if height is None else height)
     seed = renderer.scene.seed if seed is None else seed
     seed = 0 if seed is None else int(seed)
+    through = lens_of(renderer, lens)
     flags = (PT_FLAG_RR if rr else 0) | (PT_FLAG_FORCE_F64 if force_f64 else 0) | \
-        (PT_FLAG_MEGAKERNEL if megakernel else 0) | (PT_FLAG_AA if aa else 0)
+        (PT_FLAG_MEGAKERNEL if megakernel else 0) | (PT_FLAG_AA if aa else 0) | \
+        (PT_FLAG_LENS if through is not None else 0)
     params = make_params(width, height, max_spp, bounces, seed, flags, rr_depth)
     adapt = make_adapt(tol, max_spp, min_spp, step_spp, floor)
     ck = checkpoint if isinstance(checkpoint, AccumCheckpoint) or checkpoint is None \
@@ -425,7 +432,7 @@ def render_adaptive(renderer, width=None, height=None, max_spp=64, bounces=1, se
     key = rule = state = None
     if ck is not None:
         key = accum_key(renderer.packed, width, height, bounces, params.seed, rr, rr_depth,
-                        lanes_per_pixel, aa)
+                        lanes_per_pixel, aa, through)
         rule = {"tol": float(tol), "min_spp": int(min_spp), "max_spp": int(max_spp),
                 "step_spp": int(step_spp), "floor": float(floor)}
         state = ck.load(key)
@@ -500,7 +507,7 @@ def _drain(accs):
 def render_adaptive_multi(renderers, width=None, height=None, max_spp=64, bounces=1, seed=None, rr=False,
                           rr_depth=3, tol=0.05, min_spp=8, step_spp=8, floor=0.01, force_f64=False,
                           on_pass=None, megakernel=False, denoise=None, lanes_per_pixel=0,
-                          moments=False, timings=None, aa=False):
+                          moments=False, timings=None, aa=False, lens=None):
     """render_adaptive on the renderers of a render.MultiRenderer (one scene
     on N devices): device d gets a banded accumulator of the rows
     distributed.rank_band(H, d, N) and runs its own pass loop — a round-robin
@@ -524,7 +531,8 @@ def render_adaptive_multi(renderers, width=None, height=None, max_spp=64, bounce
     seed = r0.scene.seed if seed is None else seed
     seed = 0 if seed is None else int(seed)
     flags = (PT_FLAG_RR if rr else 0) | (PT_FLAG_FORCE_F64 if force_f64 else 0) | \
-        (PT_FLAG_MEGAKERNEL if megakernel else 0) | (PT_FLAG_AA if aa else 0)
+        (PT_FLAG_MEGAKERNEL if megakernel else 0) | (PT_FLAG_AA if aa else 0) | \
+        (PT_FLAG_LENS if lens_of(r0, lens) is not None else 0)   # (every renderer of a MultiRenderer has the lens)
     params = make_params(width, height, max_spp, bounces, seed, flags, rr_depth)
     adapt = make_adapt(tol, max_spp, min_spp, step_spp, floor)
     bands = [make_band(height, *rank_band(height, d, N), lanes_per_pixel=lanes_per_pixel)

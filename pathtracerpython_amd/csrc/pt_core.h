@@ -224,7 +224,10 @@ struct SceneK {
     // readlanes with this table)
     const double* kd;            // [kKd*] below
 };
-enum : int { kKdEye = 0, kKdCenterS = 3, kKdLightSum = 6, kKdCenter = 7, kKdLightRgb = 10, kKdCount = 13 };
+// (kKdLens*: the thin lens of pt_scene_create_lens — radius, focal plane z and
+// kappa = (0 - zf)/(ez - zf); zeros on a scene without a lens)
+enum : int { kKdEye = 0, kKdCenterS = 3, kKdLightSum = 6, kKdCenter = 7, kKdLightRgb = 10,
+             kKdLensR = 13, kKdLensZf = 14, kKdLensKappa = 15, kKdCount = 16 };
 
 // ------------------------------------------------------------------ RNG --
 // Philox4x32-10 (Salmon et al., SC'11), key = seed, counter =

@@ -44,6 +44,7 @@ static int fail(int code, const std::string& msg) {
 // k_render and its launch records: pt_render.h
 #include "pt_render.h"
 #include "pt_aa.h"   // the antialiasing kernels' launchers (pt_aa.hip)
+#include "pt_lens.h" // the thin-lens kernels' launchers (pt_lens.hip)
 #if PT_K2_OWN_TU
 extern template __global__ void k_render<false, false, false>(SceneK, RenderK, void*, StatsDev*);
 #endif
@@ -792,6 +793,7 @@ struct Bump {
 struct pt_scene {
     int device = 0;
     uint64_t fingerprint = 0;   // of the scene descriptor (pt_render_multi: one scene on every handle)
+    bool has_lens = false;      // created by pt_scene_create_lens with a lens (PT_FLAG_LENS is allowed)
     int n_cu = 256;   // compute units of the device (MI355X: 256 in 8 XCDs)
     HostScene host;
     SceneK dev{};
@@ -928,6 +930,22 @@ int pt_scene_create_on(const pt_scene_desc* desc, int32_t device, pt_scene** out
     return pt_scene_create(desc, out);
 }
 
+static int scene_create(const pt_scene_desc* desc, const pt_lens* lens, pt_scene** out);
+int pt_scene_create_lens(const pt_scene_desc* desc, int32_t device, const pt_lens* lens, pt_scene** out) {
+    if (!lens) return pt_scene_create_on(desc, device, out);
+    if (!out) return fail(PT_EINVAL, "null output handle");
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(PT_ENODEV, "no HIP device visible (the MI355X path needs a gfx950 GPU)");
+    if (device == -1) return scene_create(desc, lens, out);   // the current device
+    if (device < 0 || device >= ndev)
+        return fail(PT_EINVAL, "device " + std::to_string(device) + " out of range (" +
+                                   std::to_string(ndev) + " visible)");
+    DeviceGuard g(device);
+    return scene_create(desc, lens, out);
+}
+
 // FNV-1a over the descriptor's arrays and constants
 static void fnv(uint64_t* h, const void* p, size_t n) {
     const unsigned char* b = (const unsigned char*)p;
@@ -946,17 +964,21 @@ static uint64_t scene_fingerprint(const pt_scene_desc* d) {
     return h;
 }
 
-int pt_scene_create(const pt_scene_desc* desc, pt_scene** out) {
+int pt_scene_create(const pt_scene_desc* desc, pt_scene** out) { return scene_create(desc, nullptr, out); }
+
+static int scene_create(const pt_scene_desc* desc, const pt_lens* lens, pt_scene** out) {
     if (!out) return fail(PT_EINVAL, "null output handle");
     *out = nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(PT_ENODEV, "no HIP device visible (the MI355X path needs a gfx950 GPU)");
     pt_scene* s = new pt_scene();
-    std::string err = prepare_scene(desc, &s->host);
+    std::string err = prepare_scene(desc, &s->host, lens);
     if (!err.empty()) { delete s; return fail(PT_EINVAL, err); }
+    s->has_lens = lens != nullptr;
     if (hipGetDevice(&s->device) != hipSuccess) { delete s; return fail(PT_EHIP, "hipGetDevice failed"); }
     s->fingerprint = scene_fingerprint(desc);   // (prepare_scene checked the arrays)
+    if (lens) fnv(&s->fingerprint, lens, sizeof(*lens));   // (another frame: no mixing with lens-free handles)
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, s->device) == hipSuccess) {
         if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos) {
@@ -1025,7 +1047,10 @@ int pt_band_rows(const pt_render_params* p, int32_t* rows) {
 
 constexpr uint32_t kKnownFlags = PT_FLAG_RR | PT_FLAG_FORCE_F64 | PT_FLAG_COUNT | PT_FLAG_OUT_F64 |
                                  PT_FLAG_MEGAKERNEL | PT_FLAG_WALK_COUNT | PT_FLAG_KERNEL_TIMES |
-                                 PT_FLAG_AA;
+                                 PT_FLAG_AA | PT_FLAG_LENS;
+static const char kLensNoCount[] = "PT_FLAG_LENS does not combine with PT_FLAG_COUNT, PT_FLAG_WALK_COUNT or "
+                                   "PT_FLAG_KERNEL_TIMES: the lens kernels do not count";
+static const char kLensNoScene[] = "PT_FLAG_LENS needs a scene created with a lens (pt_scene_create_lens)";
 static const char kAaNoCount[] = "PT_FLAG_AA does not combine with PT_FLAG_COUNT, PT_FLAG_WALK_COUNT or "
                                  "PT_FLAG_KERNEL_TIMES: the antialiasing kernels do not count";
 // An antialiased launch that takes the single kernel (pt_aa.hip) has nothing
@@ -1038,7 +1063,8 @@ static bool aa_stats_refused(uint32_t flags) {
 // takes the single kernel whatever its size (pt_render_device's condition
 // without the slot count).
 static bool wf_scene_ok(const pt_scene* s, uint32_t flags) {
-    return s->dev.n_bnode > 0 && !(flags & (PT_FLAG_COUNT | PT_FLAG_FORCE_F64 | PT_FLAG_MEGAKERNEL)) &&
+    return s->dev.n_bnode > 0 &&
+           !(flags & (PT_FLAG_COUNT | PT_FLAG_FORCE_F64 | PT_FLAG_MEGAKERNEL | PT_FLAG_LENS)) &&
            s->dev.n_qnode > 0 && s->dev.qstack <= kWalkStack;
 }
 // This launch takes the wavefront kernels: BVH scenes, unless the caller asks
@@ -1062,6 +1088,8 @@ static int validate(const pt_render_params* p) {
     if (p->flags & ~kKnownFlags)
         return fail(PT_EINVAL, "unknown flag bits (bit 7, v4's PT_FLAG_TREE_WALK, is retired)");
     // (with PT_FLAG_WALK_COUNT / PT_FLAG_KERNEL_TIMES: aa_stats_refused, once the launch's path is known)
+    if ((p->flags & PT_FLAG_LENS) && (p->flags & (PT_FLAG_COUNT | PT_FLAG_WALK_COUNT | PT_FLAG_KERNEL_TIMES)))
+        return fail(PT_EINVAL, kLensNoCount);
     if ((p->flags & PT_FLAG_AA) && (p->flags & PT_FLAG_COUNT)) return fail(PT_EINVAL, kAaNoCount);
     if (p->out_row_stride != 0 && (int64_t)p->out_row_stride < (int64_t)p->width * 3)
         return fail(PT_EINVAL, "out_row_stride must be 0 or >= width*3");
@@ -1408,6 +1436,7 @@ int pt_render_device(pt_scene* s, const pt_render_params* p, void* out_dev, void
     int rc = validate(p);
     if (rc) return rc;
     if (!s) return fail(PT_EINVAL, "null scene");
+    if ((p->flags & PT_FLAG_LENS) && !s->has_lens) return fail(PT_EINVAL, kLensNoScene);
     if (aa_stats_refused(p->flags) && !wf_scene_ok(s, p->flags)) return fail(PT_EINVAL, kAaNoCount);
     int32_t first = 0, rows = 0;
     band_layout(p, &first, &rows);
@@ -1479,7 +1508,9 @@ int pt_render_device(pt_scene* s, const pt_render_params* p, void* out_dev, void
     if (aa_stats_refused(p->flags)) return fail(PT_EINVAL, kAaNoCount);
     if (count) HIPCHK(hipMemsetAsync(s->stats, 0, sizeof(StatsDev), st));
     HIPCHK(hipEventRecord(s->ev0, st));
-    if (aa) {   // (validate: never with count)
+    if (p->flags & PT_FLAG_LENS) {   // (validate: never with count; wf_scene_ok: never the wavefront kernels)
+        pt_lens_render(f64, s->dev.n_bnode > 0, aa, rgrid, st, s->dev, R, out_dev);
+    } else if (aa) {   // (validate: never with count)
         pt_aa_render(f64, s->dev.n_bnode > 0, rgrid, st, s->dev, R, out_dev);
     } else if (f64) {
         if (count) hipLaunchKernelGGL((k_render<true, true, true>), rgrid, rblock, 0, st, s->dev, R, out_dev, s->stats);
@@ -1577,6 +1608,7 @@ struct pt_accum {
     // PT_FLAG_AA of the passes since the last reset, write or import (-1: none
     // yet): a pass with the other value is refused
     int aa = -1;
+    int lens = -1;   // PT_FLAG_LENS likewise
 };
 
 // pt_accum_band -> BandK, or PT_EINVAL
@@ -1652,6 +1684,7 @@ int pt_accum_reset(pt_accum* a, void* stream) {
     a->list_valid = false;
     a->list_meta = AccumMeta{};
     a->aa = -1;
+    a->lens = -1;
     HIPCHK(hipMemsetAsync(a->S, 0, (size_t)a->npix * 3 * sizeof(double), st));
     HIPCHK(hipMemsetAsync(a->Q, 0, (size_t)a->npix * 3 * sizeof(double), st));
     HIPCHK(hipMemsetAsync(a->n, 0, (size_t)a->npix * sizeof(uint32_t), st));
@@ -1755,15 +1788,21 @@ int pt_accum_render_stats(pt_accum* a, const pt_render_params* p, const pt_adapt
         return fail(PT_EINVAL, "an accumulator pass renders the whole frame: row_begin 0, row_end height, "
                                "row_step 1, sample_begin 0, out_row_stride 0, lanes_per_pixel 0");
     if (p->flags & ~(uint32_t)(PT_FLAG_RR | PT_FLAG_FORCE_F64 | PT_FLAG_MEGAKERNEL | PT_FLAG_WALK_COUNT |
-                               PT_FLAG_KERNEL_TIMES | PT_FLAG_AA))
+                               PT_FLAG_KERNEL_TIMES | PT_FLAG_AA | PT_FLAG_LENS))
         return fail(PT_EINVAL, "unsupported flag bits: an accumulator pass takes PT_FLAG_RR, PT_FLAG_FORCE_F64, "
-                               "PT_FLAG_MEGAKERNEL, PT_FLAG_WALK_COUNT, PT_FLAG_KERNEL_TIMES and PT_FLAG_AA only");
+                               "PT_FLAG_MEGAKERNEL, PT_FLAG_WALK_COUNT, PT_FLAG_KERNEL_TIMES, PT_FLAG_AA and "
+                               "PT_FLAG_LENS only");
     if (p->spp != ap->max_spp) return fail(PT_EINVAL, "spp must be the budget max_spp");
     const bool aa = (p->flags & PT_FLAG_AA) != 0;
     if (a->aa >= 0 && a->aa != (aa ? 1 : 0))
         return fail(PT_EINVAL, "this accumulator's passes so far were made with the other value of PT_FLAG_AA: "
                                "sample s would have two definitions (pt_accum_reset first)");
+    const bool lens = (p->flags & PT_FLAG_LENS) != 0;
+    if (a->lens >= 0 && a->lens != (lens ? 1 : 0))
+        return fail(PT_EINVAL, "this accumulator's passes so far were made with the other value of PT_FLAG_LENS: "
+                               "sample s would have two definitions (pt_accum_reset first)");
     pt_scene* s = a->scene;
+    if (lens && !s->has_lens) return fail(PT_EINVAL, kLensNoScene);
     if (aa_stats_refused(p->flags) && !wf_scene_ok(s, p->flags)) return fail(PT_EINVAL, kAaNoCount);
     DeviceGuard g(s->device);
     hipStream_t st = (hipStream_t)stream;
@@ -1807,6 +1846,7 @@ int pt_accum_render_stats(pt_accum* a, const pt_render_params* p, const pt_adapt
         if (rc) return rc;
         a->list_valid = false;   // the pass changes n, S, Q
         a->aa = aa ? 1 : 0;
+        a->lens = 0;   // (wf_scene_ok: a lens pass never comes here)
         WfList L;
         L.R = R;
         L.R.lanes = wf_blocks * 256u;
@@ -1830,8 +1870,11 @@ int pt_accum_render_stats(pt_accum* a, const pt_render_params* p, const pt_adapt
     if (rc) return rc;
     a->list_valid = false;   // the pass changes n, S, Q
     a->aa = aa ? 1 : 0;
+    a->lens = lens ? 1 : 0;
     const dim3 grid((unsigned)blocks), block(kRenderBlock);
-    if (aa) {
+    if (lens) {
+        pt_lens_render_list(f64, bvh, aa, grid, st, s->dev, R, a->list, a->S, a->Q, a->n);
+    } else if (aa) {
         pt_aa_render_list(f64, bvh, grid, st, s->dev, R, a->list, a->S, a->Q, a->n);
     } else if (f64) {
         hipLaunchKernelGGL((k_render_list<true, true>), grid, block, 0, st, s->dev, R, a->list, a->S, a->Q, a->n, a->home);
@@ -1945,6 +1988,7 @@ int pt_accum_import_band_device(pt_accum* a, const pt_accum_band* band, const vo
     a->list_valid = false;   // n, S, Q change
     a->list_meta = AccumMeta{};
     a->aa = -1;              // (the caller vouches for the tile's samples)
+    a->lens = -1;
     double *tS, *tQ, *tE;
     uint32_t* tN;
     tile_sections(const_cast<void*>(tile_dev), B.npix, &tS, &tQ, &tE, &tN);
@@ -1964,6 +2008,7 @@ int pt_accum_write(pt_accum* a, const double* S, const double* Q, const uint32_t
     a->list_valid = false;
     a->list_meta = AccumMeta{};
     a->aa = -1;   // (the caller vouches for the state it writes)
+    a->lens = -1;
     const size_t np = a->npix;
     HIPCHK(hipMemcpyAsync(a->S, S, np * 3 * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(a->Q, Q, np * 3 * sizeof(double), hipMemcpyHostToDevice, st));

@@ -75,6 +75,9 @@ constexpr int kSpillSlots = 20;
 // in the same 128-B line as the per-step fields; the light points and the
 // primary hit follow in the other line
 constexpr int kSpP = 0, kSpNd = 3, kSpL = 6, kSpD0 = 15, kSpP0 = 17;
+// the lens kernels (PT_FLAG_LENS) cache no primary hit: kSpD0's two rows hold
+// the sample's lens point eye'.x, eye'.y
+constexpr int kSpLens = kSpD0;
 
 // ----------------------------------------------------------- closest hit --
 // intersect_objects (main.py:83-122): the triangle whose intersection has the
@@ -1790,8 +1793,11 @@ PT_HD D3 nee(const SceneK& S, D3 P, D3 n, int obj, int ogrp, const double u[12],
 // Next-ray generation, main.py:236-268.  d_old is the incoming direction as
 // the reference holds it (unnormalised for primary rays).  Returns the new
 // direction and the throughput factor (accumulated_k update).
+// LENS (PT_FLAG_LENS): the specular term's eye is the sample's lens point
+// eye', which the sample's start left in the lane's home rows kSpLens.
+template <bool LENS = false>
 PT_HD D3 bounce(const SceneK& S, const TriS& R, const Mat& m, D3 P, D3 d_old,
-                double u_sel, double u_phi, double u_theta, double* kf) {
+                double u_sel, double u_phi, double u_theta, double* kf, const Spill* sp = nullptr) {
     const D3 n = ld3(R.n);
     const double xi = 0.0 + (m.kdks - 0.0) * u_sel;
     if (xi <= m.kd) {   // diffuse: phi = arccos(sqrt(u)), theta = 6.28 u
@@ -1807,7 +1813,10 @@ PT_HD D3 bounce(const SceneK& S, const TriS& R, const Mat& m, D3 P, D3 d_old,
     // "specular": r = 2 (n.d) n - d, normalised, rotated; k *= ks (e.r)^n
     const double nd2 = dot(n, d_old) * 2;
     const D3 r = unit(d3(nd2 * n.x - d_old.x, nd2 * n.y - d_old.y, nd2 * n.z - d_old.z));
-    const D3 e = unit(ld3(S.kd + kKdEye) - P);
+    D3 eye;
+    if constexpr (LENS) eye = d3(sp->get(kSpLens), sp->get(kSpLens + 1), S.kd[kKdEye + 2]);
+    else eye = ld3(S.kd + kKdEye);
+    const D3 e = unit(eye - P);
     const D3 nd = rotate_y(R, r);
     *kf = m.ks * pow_ref(dot(e, nd), m);
     return nd;
@@ -1912,6 +1921,13 @@ struct LaneSched {
     }
 };
 
+// A scheduler of the lens kernels declares kLens: its samples read their own
+// eye' (bounce<true>); every other scheduler's loop is as it was.
+template <class Sched, class = void>
+struct sched_lens { static constexpr bool value = false; };
+template <class Sched>
+struct sched_lens<Sched, decltype((void)Sched::kLens)> { static constexpr bool value = Sched::kLens; };
+
 // The bounce loop: paths are regenerated in place (Sched::advance), so a
 // wave keeps tracing until all its lanes are out of samples.  The lane's
 // first path starts at tri, origin and direction in the homes kSpP / kSpNd;
@@ -1970,8 +1986,8 @@ PT_HD void render_loop(const SceneK& S, const LaneJob& J, int tri, const Spill& 
 #endif
         // next ray (main.py:236-268): it does not depend on the colour
         double kf;
-        const D3 nd = bounce(S, R, m, P, sp.get3(kSpNd), u_of(w[12]), u_of(w[13]), u_of(w[14]),
-                             &kf);
+        const D3 nd = bounce<sched_lens<Sched>::value>(S, R, m, P, sp.get3(kSpNd), u_of(w[12]),
+                                                       u_of(w[13]), u_of(w[14]), &kf, &sp);
         const double kn = k * kf;
         bool trace = (b + 1 < J.bounces);
         double kk = kn;
@@ -2466,6 +2482,191 @@ PT_HD void render_lane_moments_aa(const SceneK& S, const LaneJob& J, const AaPix
         return;
     }
     AaMomentSched<FORCE64, BVH, Home> q{J, X, E, 0, home};
+    int tri = -1;
+    D3 acc = d3(0, 0, 0);
+    if (q.start(S, sp, &tri, cnt)) render_loop<FORCE64, false, BVH>(S, J, tri, sp, cnt, q, &acc);
+}
+
+// ---------------------------------------------------------- thin lens --
+// PT_FLAG_LENS (build extension, include/pt_capi.h): sample s
+// of pixel k starts at its own point eye' of the lens disc and aims through
+// its own screen window, the reference's ray on a descriptor with eye = eye'
+// and the shifted ortho.  lens_point, lens_window and lens_dir are steps 1-3,
+// 4 and 5 of the rule; every f64 operation rounds on its own.  The scene's
+// (R, zf, kappa) are kd[kKdLens*].
+// AA (PT_FLAG_AA beside the lens) is a template parameter down to the kernels:
+// as a kernel argument, a wave-uniform bool carried through the divergent
+// restart loops, it was compiled to a lane mask written under one exec mask
+// and tested under another, and restarted samples of a launch without
+// PT_FLAG_AA were jittered (gfx950, ROCm's clang; tests/test_gpu_lens.py
+// test_radius_zero_and_the_flag_off found it).
+template <bool AA>
+PT_HD void lens_point(uint64_t seed, uint32_t pixel, uint32_t sample, double R, double* jx, double* jy,
+                      double* lx, double* ly) {
+    uint32_t c[4];
+    rng_block(seed, pixel, sample, 0xFFFFFFFFu, 0u, c);   // PT_FLAG_AA's block: words 2, 3 are the lens's
+    *jx = AA ? u_of(c[0]) - 0.5 : 0.0;
+    *jy = AA ? u_of(c[1]) - 0.5 : 0.0;
+    const double r = R * sqrt_d(u_of(c[2]));
+    const double phi = 6.283185307179586 * u_of(c[3]);   // < 6.2832: inside sincos_small's [0, 8)
+    double sn, cs;
+    sincos_small(phi, &sn, &cs);
+    *lx = r * cs;
+    *ly = r * sn;
+}
+// the window (x0', y0', x1', y1') of jitter (jx, jy) and lens offset (lx, ly)
+PT_HD void lens_window(const SceneK& S, int W, int H, double jx, double jy, double lx, double ly,
+                       double o[4]) {
+    const double dx = W > 1 ? (S.ortho[2] - S.ortho[0]) / (double)(W - 1) : 0.0;
+    const double dy = H > 1 ? (S.ortho[3] - S.ortho[1]) / (double)(H - 1) : 0.0;
+    const double kappa = S.kd[kKdLensKappa];
+    const double bx = jx * dx + lx * kappa, by = jy * dy + ly * kappa;
+    o[0] = S.ortho[0] + bx; o[1] = S.ortho[1] + by;
+    o[2] = S.ortho[2] + bx; o[3] = S.ortho[3] + by;
+}
+// d0 from eye' = (ex, ey, the eye's z)
+PT_HD D3 lens_dir(const SceneK& S, int W, int H, int ix, int iy, double jx, double jy, double lx,
+                  double ly, double ex, double ey) {
+    double o[4];
+    lens_window(S, W, H, jx, jy, lx, ly, o);
+    const double x = linspace_at(o[0], o[2], W, ix);
+    const double y = linspace_at(o[1], o[3], H, iy);
+    return d3(x - ex, y - ey, 0.0 - S.kd[kKdEye + 2]);
+}
+
+// aa_closest from a lens point `eye`: the same unit form over unit_eye, whose
+// bounds hold on the whole disc (prepare_scene's "all" box holds it), but no
+// wave-shared table of origin terms — every lane has its own origin and
+// computes origin_q for it.  (A copy rather than a parameter of aa_closest:
+// the antialiasing kernels' code stays as it was.)
+template <bool FORCE64, bool BVH>
+PT_HD int lens_closest(const SceneK& S, D3 eye, D3 d0, const Spill& sp, D3* P, Counters* cnt) {
+#if PT_AA_PRIMARY_M && PT_LIGHT_QUAD && PT_QUAD && PT_MARGIN
+    if (!FORCE64) {
+        const D3 dn = unit(d0);
+        sp.put3(kSpP, eye);
+        sp.put3(kSpNd, d0);
+        const F3 o32 = to_f3(eye - ld3(S.kd + kKdCenter));
+        const F3 d32 = to_f3(dn);
+        ClosestAcc acc = closest_init();
+        for (int u = 0; u < S.n_unit; ++u) {
+            const UnitF U = S.unit_eye[u];
+            const OriginU O = origin_q(U, o32);
+            if (closest_unit_m(U, O, U.grp == -1, d32, &acc))   // rare
+                fused_fallback<false, false, true, 2>(S, U, closest_bits_m(U, O, U.grp == -1, d32),
+                                                      nullptr, &acc, sp, cnt, nullptr);
+        }
+        if (BVH && S.n_bnode) {   // the meshes, as closest()
+            if (S.bvh_depth < kBvhStack) {
+                bvh_closest<false>(S, o32, -1, d32, &acc, sp, cnt);
+            } else {
+                ShadowSet none = {};
+                bvh_pass<false, false>(S, o32, -1, false, true, &none, d32, &acc, sp, cnt);
+            }
+        }
+        return closest_finish<false, false, BVH>(S, acc, eye, dn, P, cnt);
+    }
+#endif
+    return closest<FORCE64, false, BVH>(S, eye, d0, -1, sp, P, cnt, true);
+}
+
+// aa_primary's form: the primary ray of sample `sample` from its lens point,
+// which stays in the home rows kSpLens for the sample's bounces (bounce<true>).
+template <bool FORCE64, bool BVH, bool AA>
+PT_HD int lens_primary(const SceneK& S, const LaneJob& J, const AaPixel& X, uint32_t sample, const Spill& sp,
+                       Counters* cnt) {
+    double jx, jy, lx, ly;
+    lens_point<AA>(J.seed, J.pixel, sample, S.kd[kKdLensR], &jx, &jy, &lx, &ly);
+    const D3 eye = d3(S.kd[kKdEye] + lx, S.kd[kKdEye + 1] + ly, S.kd[kKdEye + 2]);
+    const D3 d0 = lens_dir(S, X.W, X.H, X.ix, X.iy, jx, jy, lx, ly, eye.x, eye.y);
+    sp.put(kSpLens, eye.x);
+    sp.put(kSpLens + 1, eye.y);
+    D3 P;
+    const int t = lens_closest<FORCE64, BVH>(S, eye, d0, sp, &P, cnt);
+    if (t >= 0 && t < S.n_obj_tri) {
+        sp.put3(kSpP, P);
+        sp.put3(kSpNd, d0);
+    }
+    return t;
+}
+
+// AaSched / AaMomentSched with lens_primary; AA: PT_FLAG_AA beside the lens.
+template <bool FORCE64, bool BVH, bool AA>
+struct LensSched {
+    static constexpr bool kLens = true;
+    const LaneJob& J;
+    AaPixel X;
+    int si;
+    PT_HD uint32_t sample() const { return (uint32_t)(J.sample0 + si * J.sample_stride); }
+    PT_HD uint32_t pixel() const { return J.pixel; }
+    PT_HD bool start(const SceneK& S, const Spill& sp, int* tri, D3* acc, Counters* cnt) {
+        for (; si < J.n_samples; ++si) {
+            const int t = lens_primary<FORCE64, BVH, AA>(S, J, X, sample(), sp, cnt);
+            if (t >= 0 && t < S.n_obj_tri) {
+                *tri = t;
+                return true;
+            }
+            if (t >= 0) *acc = *acc + ld3(S.kd + kKdLightRgb);
+        }
+        return false;
+    }
+    template <bool COUNT>
+    PT_HD bool advance(const SceneK& S, bool done, const Spill& sp, int* tri, D3* acc, Counters* cnt) {
+        if (!done) return true;
+        ++si;
+        return start(S, sp, tri, acc, cnt);
+    }
+};
+template <bool FORCE64, bool BVH, bool AA, class Home>
+struct LensMomentSched {
+    static constexpr bool kLens = true;
+    const LaneJob& J;
+    AaPixel X;
+    int si;
+    Home& home;
+    PT_HD uint32_t sample() const { return (uint32_t)(J.sample0 + si * J.sample_stride); }
+    PT_HD uint32_t pixel() const { return J.pixel; }
+    PT_HD bool start(const SceneK& S, const Spill& sp, int* tri, Counters* cnt) {
+        for (; si < J.n_samples; ++si) {
+            const int t = lens_primary<FORCE64, BVH, AA>(S, J, X, sample(), sp, cnt);
+            if (t >= 0 && t < S.n_obj_tri) {
+                *tri = t;
+                return true;
+            }
+            home.add(t < 0 ? d3(0, 0, 0) : ld3(S.kd + kKdLightRgb));
+        }
+        return false;
+    }
+    template <bool COUNT>
+    PT_HD bool advance(const SceneK& S, bool done, const Spill& sp, int* tri, D3* acc, Counters* cnt) {
+        if (!done) return true;
+        home.add(*acc);
+        *acc = d3(0, 0, 0);
+        ++si;
+        return start(S, sp, tri, cnt);
+    }
+};
+
+// render_lane_aa / render_lane_moments_aa through the lens
+template <bool FORCE64, bool BVH, bool AA>
+PT_HD D3 render_lane_lens(const SceneK& S, const LaneJob& J, const AaPixel& X, const Spill& sp,
+                          Counters* cnt) {
+    D3 acc = d3(0, 0, 0);
+    if (J.n_samples <= 0 || J.bounces <= 0) return acc;
+    LensSched<FORCE64, BVH, AA> q{J, X, 0};
+    int tri = -1;
+    if (q.start(S, sp, &tri, &acc, cnt)) render_loop<FORCE64, false, BVH>(S, J, tri, sp, cnt, q, &acc);
+    return acc;
+}
+template <bool FORCE64, bool BVH, bool AA, class Home>
+PT_HD void render_lane_moments_lens(const SceneK& S, const LaneJob& J, const AaPixel& X, const Spill& sp,
+                                    Counters* cnt, Home& home) {
+    if (J.n_samples <= 0) return;
+    if (J.bounces <= 0) {
+        for (int i = 0; i < J.n_samples; ++i) home.add(d3(0, 0, 0));
+        return;
+    }
+    LensMomentSched<FORCE64, BVH, AA, Home> q{J, X, 0, home};
     int tri = -1;
     D3 acc = d3(0, 0, 0);
     if (q.start(S, sp, &tri, cnt)) render_loop<FORCE64, false, BVH>(S, J, tri, sp, cnt, q, &acc);

@@ -415,8 +415,22 @@ inline bool light_table_mono(const std::vector<double>& cum) {
     return true;
 }
 
-// Returns "" on success, else an error message.
-inline std::string prepare_scene(const pt_scene_desc* d, HostScene* H) {
+// A valid thin lens for this eye (include/pt_capi.h pt_scene_create_lens), or
+// the reason it is not ("" when valid).
+inline std::string lens_check(const double eye[3], const pt_lens& L) {
+    if (!std::isfinite(L.radius) || !std::isfinite(L.focus_z) || !(L.radius >= 0.0))
+        return "lens: radius and focus_z must be finite, radius >= 0";
+    if (!std::isfinite(eye[2]) || eye[2] == 0.0) return "lens: eye z must be finite and non-zero";
+    const double tau = (eye[2] - L.focus_z) / eye[2];
+    if (!std::isfinite(tau) || !(tau > 0.0))
+        return "lens: (eye.z - focus_z)/eye.z must be finite and > 0 (the focal plane lies on the "
+               "screen's side of the eye)";
+    return "";
+}
+
+// Returns "" on success, else an error message.  lens (may be null): the
+// thin lens of PT_FLAG_LENS — primary rays start anywhere on its disc.
+inline std::string prepare_scene(const pt_scene_desc* d, HostScene* H, const pt_lens* lens = nullptr) {
     if (!d) return "null scene descriptor";
     if (d->n_tri <= 0 || d->n_obj_tri < 0 || d->n_obj_tri >= d->n_tri)
         return "need 0 <= n_obj_tri < n_tri (the light must have triangles)";
@@ -449,6 +463,10 @@ inline std::string prepare_scene(const pt_scene_desc* d, HostScene* H) {
             }
     for (int i = 0; i < 3; ++i)
         if (!isfinite(d->eye[i])) return "non-finite eye";
+    if (lens) {
+        const std::string e = lens_check(d->eye, *lens);
+        if (!e.empty()) return e;
+    }
     double Cs[3], Xs = 0.0;
     for (int i = 0; i < 3; ++i) {
         Cs[i] = 0.5 * (lo[i] + hi[i]);
@@ -456,8 +474,10 @@ inline std::string prepare_scene(const pt_scene_desc* d, HostScene* H) {
     }
     Xs = Xs * 1.001 + 1e-6;
     for (int i = 0; i < 3; ++i) {
-        lo[i] = std::min(lo[i], d->eye[i]);
-        hi[i] = std::max(hi[i], d->eye[i]);
+        // (the lens disc lies in the eye's z plane: x and y grow by its radius)
+        const double r = lens && i < 2 ? lens->radius : 0.0;
+        lo[i] = std::min(lo[i], d->eye[i] - r);
+        hi[i] = std::max(hi[i], d->eye[i] + r);
     }
     double C[3], X = 0.0;
     for (int i = 0; i < 3; ++i) {
@@ -794,6 +814,11 @@ inline std::string prepare_scene(const pt_scene_desc* d, HostScene* H) {
         H->kd[kKdLightRgb + i] = K.light_rgb[i];
     }
     H->kd[kKdLightSum] = K.light_sum;
+    if (lens) {
+        H->kd[kKdLensR] = lens->radius;
+        H->kd[kKdLensZf] = lens->focus_z;
+        H->kd[kKdLensKappa] = (0.0 - lens->focus_z) / (d->eye[2] - lens->focus_z);
+    }
     // leaf codes (unit offset << 3 | count) travel in stack entries as
     // (~code << 3 | ray mask) in 32 bits
     if (H->bunit.size() >= (size_t(1) << 24)) return "mesh too large: at most 2^24 BVH units";

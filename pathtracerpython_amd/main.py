@@ -18,7 +18,11 @@ frame; without --noise the -r samples go through the accumulator),
 --local-devices N (N GPUs of this process, no rank processes: interleaved row
 bands, also for --noise / --denoise; render.MultiRenderer), --aa
 (antialiasing: a jittered primary ray per sample, PT_FLAG_AA; combines with
-every flag above; scenes with a BVH keep the wavefront kernels).  The
+every flag above; scenes with a BVH keep the wavefront kernels), --aperture R
+--focus-z Z (a thin-lens camera: a lens point per sample on a disc of radius R
+around the eye, focused on the plane z = Z, PT_FLAG_LENS; the two go together;
+with --aa, --noise, --denoise, --checkpoint, --chunk-spp and --local-devices,
+not with --devices N > 1; always the single kernel).  The
 reference's interactive 3-D viewer flags (--show-scene, --show-normals,
 --show-screen, --show-inter -> plot.py) are accepted and ignored with a
 notice: the pyqtgraph viewer is out of scope.
@@ -45,6 +49,11 @@ def setup(argv=None):
     parser.add_argument('--aa', default=False, action='store_true',
                         help='antialiasing: a jittered primary ray per sample (box filter one '
                              'pixel wide); the features and --denoise keep the centre ray')
+    parser.add_argument('--aperture', type=float, default=None, metavar='R',
+                        help='thin-lens camera: the radius of the lens disc around the eye '
+                             '(with --focus-z); the features and --denoise keep the pinhole')
+    parser.add_argument('--focus-z', type=float, default=None, metavar='Z',
+                        help='with --aperture: the z of the plane in focus (the screen is z = 0)')
     parser.add_argument('--size', type=int, nargs=2, metavar=('W', 'H'), default=None)
     parser.add_argument('--save-raw', default=None,
                         help='also save the float framebuffer (.npy, before normalisation)')
@@ -128,6 +137,10 @@ def render_ranks(scene, args, W, H):
 
 def check_args(args):
     """Reject flag combinations before any rank process starts."""
+    if (args.aperture is None) != (args.focus_z is None):
+        raise SystemExit('--aperture and --focus-z go together')
+    if args.aperture is not None and args.devices > 1:
+        raise SystemExit('--aperture runs in one process (--devices 1; --local-devices N for more GPUs)')
     if args.local_devices is not None:
         if args.local_devices < 1:
             raise SystemExit('--local-devices must be >= 1')
@@ -174,6 +187,11 @@ def local_device_ids(n):
     return list(range(n))
 
 
+def lens_arg(args):
+    """Renderer's lens of --aperture / --focus-z, or None."""
+    return None if args.aperture is None else (args.aperture, args.focus_z)
+
+
 def adaptive_args(args):
     """The render_adaptive arguments of --noise / --denoise."""
     dn = dict(iters=args.denoise_iters, sigma_l=args.denoise_sigma) if args.denoise else None
@@ -212,7 +230,7 @@ def main(argv=None):
     through_accum = args.noise is not None or args.denoise   # (adaptive.py)
     if args.local_devices is not None:   # N GPUs of this process (render.MultiRenderer)
         from .render import MultiRenderer, image_u8
-        with MultiRenderer(scene, local_device_ids(args.local_devices)) as m:
+        with MultiRenderer(scene, local_device_ids(args.local_devices), lens=lens_arg(args)) as m:
             if through_accum:
                 res = m.render_adaptive(W, H, args.n_rays, args.n_bounces, args.seed, args.rr,
                                         **adaptive_args(args))
@@ -225,7 +243,7 @@ def main(argv=None):
         print(f'render: {W}x{H}, {spp} spp, {args.n_bounces} bounces on {args.local_devices} '
               f'local GPUs')
         return finish(args, arr, fb)
-    with Renderer(scene) as r:
+    with Renderer(scene, lens=lens_arg(args)) as r:   # (with a lens every render below goes through it)
         chunks = []
         if through_accum:
             from .render import image_u8

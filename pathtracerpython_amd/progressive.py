@@ -66,21 +66,32 @@ class Checkpoint:
             os.remove(self.path)
 
 
-def run_key(packed, width, height, spp, bounces, seed, rr, rr_depth, chunk_spp, aa=False):
+def lens_of(renderer, lens=None):
+    """The (R, zf) a render of `renderer` with this `lens` argument goes
+    through, or None: Renderer.lens_on's rule (None: iff the renderer has a
+    lens; a renderer without one never does)."""
+    on = getattr(renderer, "lens_on", None)
+    return renderer.lens if on is not None and on(lens) else None
+
+
+def run_key(packed, width, height, spp, bounces, seed, rr, rr_depth, chunk_spp, aa=False, lens=None):
     """What defines a chunked run's samples and their sum order: a checkpoint
     holds it, and a file with another key is refused.  "aa" is present only
-    when antialiasing is on, so the keys and files from before it stay valid."""
+    when antialiasing is on, and "lens": [R, zf] only when the samples go
+    through a lens, so the keys and files from before them stay valid."""
     key = {"scene": scene_fingerprint(packed), "width": int(width), "height": int(height),
            "spp": int(spp), "bounces": int(bounces), "seed": int(seed), "rr": bool(rr),
            "rr_depth": int(rr_depth), "chunk_spp": int(chunk_spp)}
     if aa:
         key["aa"] = True
+    if lens is not None:
+        key["lens"] = [float(lens[0]), float(lens[1])]
     return key
 
 
 def render_progressive(renderer, width=None, height=None, spp=1, bounces=1, seed=None, rr=False,
                        rr_depth=3, chunk_spp=16, checkpoint=None, max_chunks=None,
-                       on_chunk=None, aa=False):
+                       on_chunk=None, aa=False, lens=None):
     """Render `spp` samples per pixel in launches of `chunk_spp`.
 
     renderer: a render.Renderer.  checkpoint: a path (or Checkpoint) to
@@ -89,6 +100,7 @@ def render_progressive(renderer, width=None, height=None, spp=1, bounces=1, seed
     on_chunk(done, spp): progress callback after each chunk.  aa=True:
     antialiasing (a jittered primary ray per sample, keyed by the absolute
     sample index: chunks and resumed runs draw the same rays as one launch).
+    lens: through the renderer's lens (None: iff it has one), keyed likewise.
     Returns the framebuffer (H, W, 3) float64 — the mean over all samples —
     once every sample is done."""
     spp, chunk_spp = int(spp), int(chunk_spp)
@@ -96,7 +108,8 @@ def render_progressive(renderer, width=None, height=None, spp=1, bounces=1, seed
         raise ValueError("spp and chunk_spp must be >= 1")
     p0 = renderer.params(width, height, spp, bounces, seed, rr, rr_depth, out_f64=True)
     W, H = p0.width, p0.height
-    key = run_key(renderer.packed, W, H, spp, bounces, p0.seed, rr, rr_depth, chunk_spp, aa)
+    through = lens_of(renderer, lens)
+    key = run_key(renderer.packed, W, H, spp, bounces, p0.seed, rr, rr_depth, chunk_spp, aa, through)
     ck = checkpoint if isinstance(checkpoint, Checkpoint) or checkpoint is None \
         else Checkpoint(checkpoint)
     state = ck.load(key) if ck is not None else None
@@ -109,7 +122,8 @@ def render_progressive(renderer, width=None, height=None, spp=1, bounces=1, seed
             return None
         n = min(chunk_spp, spp - done)
         fb = renderer.render(W, H, n, bounces, seed, rr, rr_depth, out_f64=True,
-                             sample_begin=done, **({"aa": True} if aa else {}))
+                             sample_begin=done, **({"aa": True} if aa else {}),
+                             **({"lens": through is not None} if hasattr(renderer, "lens_on") else {}))
         acc += fb * n
         done += n
         chunks += 1

@@ -18,9 +18,9 @@ import numbers
 import numpy as np
 
 from . import _native
-from ._abi import (PT_FLAG_AA, PT_FLAG_COUNT, PT_FLAG_FORCE_F64, PT_FLAG_KERNEL_TIMES, PT_FLAG_MEGAKERNEL,
+from ._abi import (PT_FLAG_AA, PT_FLAG_COUNT, PT_FLAG_LENS, PT_FLAG_FORCE_F64, PT_FLAG_KERNEL_TIMES, PT_FLAG_MEGAKERNEL,
                    PT_FLAG_OUT_F64, PT_FLAG_RR, PT_FLAG_WALK_COUNT, PtStats, band_rows, make_denoise,
-                   make_params)
+                   make_lens, make_params)
 from .pack import pack_scene
 
 _dp = C.POINTER(C.c_double)
@@ -29,14 +29,22 @@ _ip = C.POINTER(C.c_int32)
 
 class Renderer:
     """A scene uploaded to a HIP device (one `pt_scene` handle): the current
-    device, or `device`."""
+    device, or `device`.  lens=(R, zf): a thin-lens camera of aperture radius
+    R focused on the plane z = zf (pt_scene_create_lens); renders of this
+    handle then use it unless told otherwise (lens=False)."""
 
-    def __init__(self, scene, device=None, packed=None):
+    def __init__(self, scene, device=None, packed=None, lens=None):
         self.scene = scene
         self.packed = packed if packed is not None else pack_scene(scene)
         self._lib = _native.lib()
+        self.lens = None if lens is None else (float(lens[0]), float(lens[1]))
         h = C.c_void_p()
-        if device is None:
+        if self.lens is not None:
+            L = make_lens(self.lens)
+            _native.check(self._lib.pt_scene_create_lens(C.byref(self.packed.desc),
+                                                         -1 if device is None else int(device),
+                                                         C.byref(L), C.byref(h)), "pt_scene_create_lens")
+        elif device is None:
             _native.check(self._lib.pt_scene_create(C.byref(self.packed.desc), C.byref(h)),
                           "pt_scene_create")
         else:
@@ -49,7 +57,8 @@ class Renderer:
     def params(self, width=None, height=None, spp=1, bounces=1, seed=None, rr=False,
                rr_depth=3, force_f64=False, count=False, out_f64=False, row_begin=0,
                row_end=None, row_step=1, row_phase=0, sample_begin=0, megakernel=False,
-               walk_count=False, kernel_times=False, out_row_stride=0, lanes_per_pixel=0, aa=False):
+               walk_count=False, kernel_times=False, out_row_stride=0, lanes_per_pixel=0, aa=False,
+               lens=None):
         """megakernel=True: scenes with a BVH render with the single kernel
         instead of the wavefront kernels (the same framebuffer, bit for bit).
         walk_count / kernel_times (wavefront renders): the walks' work counts /
@@ -57,7 +66,8 @@ class Renderer:
         between output rows (0: packed).  lanes_per_pixel: 0 lets the
         library choose per launch; a fixed power of two makes any band split
         bit-identical (include/pt_capi.h).  aa=True: antialiasing, a jittered
-        primary ray per sample (PT_FLAG_AA)."""
+        primary ray per sample (PT_FLAG_AA).  lens: a lens point per sample
+        (PT_FLAG_LENS); None means on iff the renderer has a lens."""
         width = int(self.scene.width if width is None else width)
         height = int(self.scene.height if height is None else height)
         seed = self.scene.seed if seed is None else seed
@@ -66,10 +76,17 @@ class Renderer:
             (PT_FLAG_COUNT if count else 0) | (PT_FLAG_OUT_F64 if out_f64 else 0) | \
             (PT_FLAG_MEGAKERNEL if megakernel else 0) | \
             (PT_FLAG_WALK_COUNT if walk_count else 0) | (PT_FLAG_KERNEL_TIMES if kernel_times else 0) | \
-            (PT_FLAG_AA if aa else 0)
+            (PT_FLAG_AA if aa else 0) | (PT_FLAG_LENS if self.lens_on(lens) else 0)
         return make_params(width, height, spp, bounces, seed, flags, rr_depth, row_begin,
                            row_end, row_step, row_phase, sample_begin, out_row_stride,
                            lanes_per_pixel)
+
+    def lens_on(self, lens=None):
+        """Whether a render with this `lens` argument goes through the lens:
+        None means "iff the renderer has one"."""
+        if lens and self.lens is None:
+            raise ValueError("lens=True needs a renderer created with a lens: Renderer(scene, lens=(R, zf))")
+        return self.lens is not None if lens is None else bool(lens)
 
     def band_rows(self, p):
         n = C.c_int32(0)
@@ -90,13 +107,15 @@ class Renderer:
 
     def render(self, width=None, height=None, spp=1, bounces=1, seed=None, rr=False,
                rr_depth=3, force_f64=False, stats=False, out_f64=False, megakernel=False,
-               aa=False, **band):
+               aa=False, lens=None, **band):
         """Framebuffer (rows, W, 3), float32 (float64 with out_f64); rows = H
         for a full render.  stats=True also returns the work counters.
         aa=True: a jittered primary ray per sample (not with stats; on
-        scenes with a BVH through the wavefront kernels, like any render)."""
+        scenes with a BVH through the wavefront kernels, like any render).
+        lens: through the renderer's lens (None: iff it has one; not with
+        stats; always the single kernel)."""
         p = self.params(width, height, spp, bounces, seed, rr, rr_depth, force_f64,
-                        count=stats, out_f64=out_f64, megakernel=megakernel, aa=aa, **band)
+                        count=stats, out_f64=out_f64, megakernel=megakernel, aa=aa, lens=lens, **band)
         return self.render_params(p, stats=stats)
 
     def render_device(self, p, out_ptr, stream=None):
@@ -107,13 +126,13 @@ class Renderer:
                       "pt_render_device")
 
     def render_image(self, width=None, height=None, spp=1, bounces=1, seed=None, rr=False,
-                     rr_depth=3, return_fb=False, aa=False):
+                     rr_depth=3, return_fb=False, aa=False, lens=None):
         """make_image's uint8 array (H, W, 3) of a full render, finalised on
         the device (pt_image_u8_device) from the float64 framebuffer; with
         return_fb also that framebuffer.  Square images are exactly what
         make_image (utils.py:150-161) returns for the same colours."""
         import torch
-        p = self.params(width, height, spp, bounces, seed, rr, rr_depth, out_f64=True, aa=aa)
+        p = self.params(width, height, spp, bounces, seed, rr, rr_depth, out_f64=True, aa=aa, lens=lens)
         W, H = p.width, p.height
         fb = torch.empty((H, W, 3), dtype=torch.float64, device="cuda")
         img = torch.empty((H, W, 3), dtype=torch.uint8, device="cuda")
@@ -125,7 +144,7 @@ class Renderer:
 
     def render_adaptive(self, width=None, height=None, max_spp=64, bounces=1, seed=None,
                         rr=False, rr_depth=3, tol=0.05, megakernel=False, denoise=None, aa=False,
-                        **rule):
+                        lens=None, **rule):
         """Render to the noise target `tol` within max_spp samples per pixel
         (adaptive.render_adaptive: fb, counts, err, passes, samples).
         megakernel=True: a BVH scene's passes run the single kernel instead of
@@ -135,10 +154,10 @@ class Renderer:
         force_f64, on_pass, and lanes_per_pixel, checkpoint, checkpoint_every,
         max_passes (a fixed lane count; a resumable run).  aa=True: every
         sample has its own jittered primary ray (the features and the denoiser
-        keep the centre ray)."""
+        keep the centre ray).  lens: as for render."""
         from .adaptive import render_adaptive
         return render_adaptive(self, width, height, max_spp, bounces, seed, rr, rr_depth, tol,
-                               megakernel=megakernel, denoise=denoise, aa=aa, **rule)
+                               megakernel=megakernel, denoise=denoise, aa=aa, lens=lens, **rule)
 
     def last_kernel_ms(self):
         ms = C.c_float(0)
@@ -224,24 +243,26 @@ class MultiRenderer:
     same lanes_per_pixel; with the default 0 each band's launch picks its own
     lanes per pixel and the values agree to ~1e-15 relative (the sum order
     of a pixel's samples follows its lane count).  (The multi-process path is
-    distributed.py.)"""
+    distributed.py.)  lens=(R, zf): every device's scene is created with the
+    lens."""
 
-    def __init__(self, scene, devices):
+    def __init__(self, scene, devices, lens=None):
         self.devices = [int(d) for d in devices]
         if not self.devices:
             raise ValueError("need at least one device")
-        first = Renderer(scene, device=self.devices[0])
-        self.renderers = [first] + [Renderer(scene, device=d, packed=first.packed)
+        first = Renderer(scene, device=self.devices[0], lens=lens)
+        self.renderers = [first] + [Renderer(scene, device=d, packed=first.packed, lens=lens)
                                     for d in self.devices[1:]]
+        self.lens = first.lens
         self.packed = first.packed
 
     def render(self, width=None, height=None, spp=1, bounces=1, seed=None, rr=False,
                rr_depth=3, stats=False, out_f64=False, row_begin=0, row_end=None,
-               lanes_per_pixel=0, aa=False):
+               lanes_per_pixel=0, aa=False, lens=None):
         r0 = self.renderers[0]
         p = r0.params(width, height, spp, bounces, seed, rr, rr_depth, count=stats,
                       out_f64=out_f64, row_begin=row_begin, row_end=row_end,
-                      lanes_per_pixel=lanes_per_pixel, aa=aa)
+                      lanes_per_pixel=lanes_per_pixel, aa=aa, lens=lens)
         rows = r0.band_rows(p)
         out = np.zeros((rows, p.width, 3), dtype=np.float64 if out_f64 else np.float32)
         hs = (C.c_void_p * len(self.renderers))(*[r._h.value for r in self.renderers])
@@ -253,7 +274,7 @@ class MultiRenderer:
 
     def render_adaptive(self, width=None, height=None, max_spp=64, bounces=1, seed=None,
                         rr=False, rr_depth=3, tol=0.05, megakernel=False, denoise=None, aa=False,
-                        **rule):
+                        lens=None, **rule):
         """Renderer.render_adaptive over the devices (no checkpointing): one
         banded accumulator per device, each running the pass loop of its own
         interleaved rows; the bands' tiles are merged on the first device,
@@ -266,7 +287,7 @@ class MultiRenderer:
                                  "run is not checkpointed")
         return adaptive.render_adaptive_multi(self.renderers, width, height, max_spp, bounces, seed,
                                               rr, rr_depth, tol, megakernel=megakernel,
-                                              denoise=denoise, aa=aa, **rule)
+                                              denoise=denoise, aa=aa, lens=lens, **rule)
 
     def close(self):
         for r in self.renderers:
