@@ -134,10 +134,15 @@ extern "C" {
  * without the flag is the pinhole render.  Allowed beside it: PT_FLAG_AA,
  * PT_FLAG_RR, PT_FLAG_FORCE_F64, PT_FLAG_OUT_F64, PT_FLAG_MEGAKERNEL; with
  * PT_FLAG_COUNT, PT_FLAG_WALK_COUNT or PT_FLAG_KERNEL_TIMES it is PT_EINVAL.
- * Every launch with the flag takes the single kernel (scenes with a BVH
- * included; the wavefront form is not built).  An accumulator remembers the
- * bit as it remembers PT_FLAG_AA and refuses a mixed pass.  Features and the
- * denoiser keep the centre ray from the eye.                               */
+ * Scenes with a BVH render through the wavefront kernels under the conditions
+ * of a launch without the flag (each path slot starts a closest query from its
+ * sample's lens point, with or without PT_FLAG_AA; the same lanes per pixel,
+ * so the frame and S, Q, n are the single kernel's bit for bit); the single
+ * kernel takes the launch on a scene without a BVH, with PT_FLAG_MEGAKERNEL or
+ * PT_FLAG_FORCE_F64, on a tree deeper than the walk stack and at 2^29 path
+ * slots or more (pt_last_launch_info tells which).  An accumulator remembers
+ * the bit as it remembers PT_FLAG_AA and refuses a mixed pass.  Features and
+ * the denoiser keep the centre ray from the eye.                           */
 #define PT_FLAG_LENS (1u << 9)
 
 /*
@@ -293,6 +298,21 @@ int pt_render_multi(pt_scene* const* scenes, int32_t n, const pt_render_params* 
 /* Kernel time (ms) of the last pt_render_device launch on this handle. */
 int pt_last_kernel_ms(pt_scene* scene, float* ms);
 
+/* Which path the handle's last launch took (v7, additive): a host-side record
+ * without synchronisation, written by every pt_render_device, pt_render and
+ * pt_accum_render(_stats) call that launches (pt_render_multi: each handle's
+ * own); a call that launches nothing leaves it as it was. */
+#define PT_PATH_NONE 0       /* no launch on this handle yet */
+#define PT_PATH_SINGLE 1
+#define PT_PATH_WAVEFRONT 2
+typedef struct pt_launch_info {
+    int32_t path;             /* PT_PATH_* of the handle's last launch */
+    int32_t steps;            /* wavefront: shade launches issued; single kernel: 1 */
+    int32_t lanes_per_pixel;  /* the split the launch used */
+    uint32_t flags;           /* the launch's PT_FLAG_* */
+} pt_launch_info;             /* 16 bytes */
+int pt_last_launch_info(pt_scene* scene, pt_launch_info* info);
+
 /* Adaptive sampling to a noise target (v7, additive; build extension — the
  * reference spends -r samples on every pixel, main.py:186-271).  A pt_accum is
  * a device-resident accumulator of one (width, height) frame of `scene`.  Per
@@ -353,8 +373,9 @@ int pt_accum_select(pt_accum* acc, const pt_adapt_params* a, void* stream,
  * out_row_stride 0, lanes_per_pixel 0, flags within PT_FLAG_RR |
  * PT_FLAG_FORCE_F64 | PT_FLAG_MEGAKERNEL | PT_FLAG_WALK_COUNT |
  * PT_FLAG_KERNEL_TIMES | PT_FLAG_AA | PT_FLAG_LENS (one value of PT_FLAG_AA
- * and one of PT_FLAG_LENS between resets, see the flags; a PT_FLAG_LENS pass
- * takes the single kernel); anything else is PT_EINVAL.  Scenes with a BVH run
+ * and one of PT_FLAG_LENS between resets, see the flags; PT_FLAG_LENS with
+ * PT_FLAG_WALK_COUNT or PT_FLAG_KERNEL_TIMES is PT_EINVAL on either path);
+ * anything else is PT_EINVAL.  Scenes with a BVH run
  * the pass through the wavefront kernels (shade, sort and walk steps over the
  * slots of the listed pixels) under pt_render_device's conditions, and
  * through the single kernel with PT_FLAG_MEGAKERNEL or PT_FLAG_FORCE_F64;

@@ -50,6 +50,16 @@ def make_lens(lens):
     return L
 
 
+PT_PATH_NONE, PT_PATH_SINGLE, PT_PATH_WAVEFRONT = 0, 1, 2
+PATH_NAMES = {PT_PATH_NONE: "none", PT_PATH_SINGLE: "single", PT_PATH_WAVEFRONT: "wavefront"}
+
+
+class PtLaunchInfo(C.Structure):
+    """pt_launch_info (include/pt_capi.h): which path a handle's last launch took."""
+    _fields_ = [("path", C.c_int32), ("steps", C.c_int32), ("lanes_per_pixel", C.c_int32),
+                ("flags", C.c_uint32)]
+
+
 class PtRenderParams(C.Structure):
     _fields_ = [
         ("width", C.c_int32), ("height", C.c_int32), ("spp", C.c_int32),

@@ -7,7 +7,7 @@ raise `NativeError` — loudly, never silently.
 import ctypes as C
 import os
 
-from ._abi import PtAccumBand, PtAdaptParams, PtDenoiseParams, PtLens, PtMesh, PtRenderParams, PtSceneDesc, PtStats  # noqa: F401 (PtMesh re-exported)
+from ._abi import PtAccumBand, PtAdaptParams, PtDenoiseParams, PtLaunchInfo, PtLens, PtMesh, PtRenderParams, PtSceneDesc, PtStats  # noqa: F401 (PtMesh re-exported)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PT_HIP_LIB", os.path.join(HERE, "_lib", "libpt_hip.so"))
@@ -39,6 +39,7 @@ def _bind(lib):
         "pt_render_device": ([vp, C.POINTER(PtRenderParams), vp, vp, C.POINTER(PtStats)], C.c_int),
         "pt_render": ([vp, C.POINTER(PtRenderParams), vp, C.POINTER(PtStats)], C.c_int),
         "pt_last_kernel_ms": ([vp, C.POINTER(C.c_float)], C.c_int),
+        "pt_last_launch_info": ([vp, C.POINTER(PtLaunchInfo)], C.c_int),
         "pt_intersect_objects": ([vp, dp, C.c_int64, ip, dp], C.c_int),
         "pt_compute_color": ([vp, ip, dp, dp, dp, C.c_int64, dp], C.c_int),
         "pt_image_u8_device": ([vp, C.c_int32, C.c_int32, C.c_uint32, vp, vp], C.c_int),
@@ -96,7 +97,8 @@ EXPORTS = ("pt_api_version", "pt_last_error", "pt_build_id", "pt_test_fault_inje
            "pt_accum_render", "pt_accum_render_stats", "pt_accum_resolve_device", "pt_accum_read",
            "pt_denoise_device", "pt_denoise", "pt_denoise_times", "pt_accum_features", "pt_accum_read_features",
            "pt_accum_denoise_device", "pt_accum_set_band", "pt_accum_tile_bytes",
-           "pt_accum_export_band_device", "pt_accum_import_band_device", "pt_accum_write")
+           "pt_accum_export_band_device", "pt_accum_import_band_device", "pt_accum_write",
+           "pt_last_launch_info")
 
 
 def lib():

@@ -28,8 +28,10 @@ UNITS = {"pt_k2.hip": _ILP, "pt_shade.hip": _ILP}
 # the antialiasing kernels (pt_aa.hip), a unit of their own as well so that
 # the other units' code does not move; its flags are chosen apart from the two
 # above: the ILP scheduler again (k_render_aa -0.8%)
-# the thin-lens kernels (pt_lens.hip) likewise: their own unit, the same flags
-AA_UNITS = {"pt_aa.hip": _ILP, "pt_lens.hip": _ILP}
+# the thin-lens kernels (pt_lens.hip) likewise: their own unit, the same flags;
+# and the lens's wavefront shade kernels (pt_shade_lens.hip), apart from
+# pt_shade.hip so that its four kernels stay as they were
+AA_UNITS = {"pt_aa.hip": _ILP, "pt_lens.hip": _ILP, "pt_shade_lens.hip": _ILP}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 # -ffp-contract=off: every f64 operation rounds separately, as the reference's

@@ -794,6 +794,7 @@ struct pt_scene {
     int device = 0;
     uint64_t fingerprint = 0;   // of the scene descriptor (pt_render_multi: one scene on every handle)
     bool has_lens = false;      // created by pt_scene_create_lens with a lens (PT_FLAG_LENS is allowed)
+    pt_launch_info last{};      // the last launch on this handle (pt_last_launch_info; host side only)
     int n_cu = 256;   // compute units of the device (MI355X: 256 in 8 XCDs)
     HostScene host;
     SceneK dev{};
@@ -1064,9 +1065,11 @@ static bool aa_stats_refused(uint32_t flags) {
 // without the slot count).
 static bool wf_scene_ok(const pt_scene* s, uint32_t flags) {
     return s->dev.n_bnode > 0 &&
-           !(flags & (PT_FLAG_COUNT | PT_FLAG_FORCE_F64 | PT_FLAG_MEGAKERNEL | PT_FLAG_LENS)) &&
+           !(flags & (PT_FLAG_COUNT | PT_FLAG_FORCE_F64 | PT_FLAG_MEGAKERNEL)) &&
            s->dev.n_qnode > 0 && s->dev.qstack <= kWalkStack;
 }
+// (PT_FLAG_LENS does not decide it: the lens has its wavefront form,
+// pt_shade_lens.hip.)
 // This launch takes the wavefront kernels: BVH scenes, unless the caller asks
 // for the single kernel, or for counting / forced f64, which only the single
 // kernel implements (wf_scene_ok), or the launch has 2^29 or more path slots,
@@ -1197,7 +1200,9 @@ static uint64_t min_lanes_of(int n_cu) {
 // every slot; steps after that would find no work.  An antialiased launch
 // (PT_FLAG_AA in `flags`) has no shared primary query: k_wf_shade_aa starts a
 // query per sample, so a sample takes bounces + 1 steps, step 0's closest
-// walk is over the slots' own records, and CQP stays unused.
+// walk is over the slots' own records, and CQP stays unused.  A thin-lens
+// launch (PT_FLAG_LENS) is of that form with or without PT_FLAG_AA — every
+// sample has its own origin — through the kernels of pt_shade_lens.hip.
 //
 // The list form (L, an accumulator pass: pt_accum_render): the same loop over
 // the slots of the active list's entries, with the list kernels for the
@@ -1238,8 +1243,9 @@ static int render_wavefront(pt_scene* s, const RenderK& R, const WfList* L, dim3
     const uint32_t split_log2 = L ? L->R.split_log2 : R.split_log2;
     const int32_t split = (int32_t)(1u << split_log2);
     const int32_t per_slot = ((L ? L->max_k : R.spp) + split - 1) / split;
-    const bool aa = (flags & PT_FLAG_AA) != 0;
-    const int32_t steps = per_slot * ((L ? L->R.bounces : R.bounces) + (aa ? 1 : 0)) + 2;
+    const bool aa = (flags & PT_FLAG_AA) != 0, lens = (flags & PT_FLAG_LENS) != 0;
+    const bool own = aa || lens;   // a primary query per sample, in the slots' own records
+    const int32_t steps = per_slot * ((L ? L->R.bounces : R.bounces) + (own ? 1 : 0)) + 2;
     const unsigned sh_blocks =
         std::max(1u, std::min<unsigned>(grid.x, (unsigned)PT_WF_SHADOW_BLOCKS_PER_CU * (unsigned)s->n_cu));
     const unsigned cl_blocks =
@@ -1326,12 +1332,20 @@ static int render_wavefront(pt_scene* s, const RenderK& R, const WfList* L, dim3
     auto mark = [&](int32_t step, int k, int end, hipStream_t on) -> hipError_t {
         return times ? hipEventRecord(s->prof_ev[(size_t)step * kEv + k * 2 + end], on) : hipSuccess;
     };
+    s->last = pt_launch_info{PT_PATH_WAVEFRONT, steps, split, flags};
     HIPCHK(hipEventRecord(s->ev0, st));
     for (int32_t step = 0; step < steps; ++step) {
         HIPCHK(hipMemsetAsync(B.counters, 0, 4 * sizeof(int32_t), st));
         HIPCHK(mark(step, 0, 0, st));
         const dim3 sgrid((unsigned)((slots + kShadeBlock - 1) / kShadeBlock)), pgrid((n_prim + 255) / 256);
-        if (aa) {   // (the slots start their own primary queries)
+        if (lens) {   // (a lens point per sample; validate: never with the stats flags)
+            if (L)
+                pt_wf_shade_list_lens(aa, sgrid, st, s->dev, L->R, step, L->list, (const uint32_t*)L->n, B.W, B.SQ,
+                                      B.CQ, B.lists, B.counters, (uint32_t)slots, B.keys, B.home);
+            else
+                pt_wf_shade_lens(aa, sgrid, st, s->dev, R, step, B.W, B.SQ, B.CQ, B.lists, B.counters,
+                                 (uint32_t)slots, B.keys);
+        } else if (aa) {   // (the slots start their own primary queries)
             if (L)
                 hipLaunchKernelGGL(k_wf_shade_list_aa, sgrid, dim3(kShadeBlock), 0, st, s->dev, L->R, step,
                                    L->list, (const uint32_t*)L->n, B.W, B.SQ, B.CQ, B.lists, B.counters,
@@ -1370,7 +1384,7 @@ static int render_wavefront(pt_scene* s, const RenderK& R, const WfList* L, dim3
             HIPCHK(mark(step, 2, 0, cs));
             // step 0 walks the primary queries (CQP, one per pixel / entry, the
             // spill home in its first slot), later steps the slots' (CQ)
-            const bool prim = step == 0 && !aa;
+            const bool prim = step == 0 && !own;
             launch_wf_closest(s->dev.bunitc != nullptr, wcount, cl_blocks, cs, s->dev, B.W, prim ? B.CQP : B.CQ,
                               closest_list, B.counters + 2, wc + 3, B.ovf_cr, B.ovf_cd, prim ? split_log2 : 0u);
             HIPCHK(mark(step, 2, 1, cs));
@@ -1508,7 +1522,8 @@ int pt_render_device(pt_scene* s, const pt_render_params* p, void* out_dev, void
     if (aa_stats_refused(p->flags)) return fail(PT_EINVAL, kAaNoCount);
     if (count) HIPCHK(hipMemsetAsync(s->stats, 0, sizeof(StatsDev), st));
     HIPCHK(hipEventRecord(s->ev0, st));
-    if (p->flags & PT_FLAG_LENS) {   // (validate: never with count; wf_scene_ok: never the wavefront kernels)
+    s->last = pt_launch_info{PT_PATH_SINGLE, 1, (int32_t)R.split, p->flags};
+    if (p->flags & PT_FLAG_LENS) {   // (validate: never with count)
         pt_lens_render(f64, s->dev.n_bnode > 0, aa, rgrid, st, s->dev, R, out_dev);
     } else if (aa) {   // (validate: never with count)
         pt_aa_render(f64, s->dev.n_bnode > 0, rgrid, st, s->dev, R, out_dev);
@@ -1846,7 +1861,7 @@ int pt_accum_render_stats(pt_accum* a, const pt_render_params* p, const pt_adapt
         if (rc) return rc;
         a->list_valid = false;   // the pass changes n, S, Q
         a->aa = aa ? 1 : 0;
-        a->lens = 0;   // (wf_scene_ok: a lens pass never comes here)
+        a->lens = lens ? 1 : 0;
         WfList L;
         L.R = R;
         L.R.lanes = wf_blocks * 256u;
@@ -1871,6 +1886,7 @@ int pt_accum_render_stats(pt_accum* a, const pt_render_params* p, const pt_adapt
     a->list_valid = false;   // the pass changes n, S, Q
     a->aa = aa ? 1 : 0;
     a->lens = lens ? 1 : 0;
+    s->last = pt_launch_info{PT_PATH_SINGLE, 1, (int32_t)R.split, p->flags};
     const dim3 grid((unsigned)blocks), block(kRenderBlock);
     if (lens) {
         pt_lens_render_list(f64, bvh, aa, grid, st, s->dev, R, a->list, a->S, a->Q, a->n);
@@ -2453,6 +2469,12 @@ int pt_wait_flags(const uint64_t* flags, int32_t n, int32_t stride, uint64_t val
         __builtin_ia32_pause();
     }
     std::atomic_thread_fence(std::memory_order_acquire);
+    return PT_OK;
+}
+
+int pt_last_launch_info(pt_scene* s, pt_launch_info* info) {
+    if (!s || !info) return fail(PT_EINVAL, "null argument");
+    *info = s->last;   // (PT_PATH_NONE before the first launch)
     return PT_OK;
 }
 

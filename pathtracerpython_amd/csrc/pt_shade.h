@@ -65,3 +65,13 @@ __global__ __launch_bounds__(kShadeBlock) void k_wf_shade_list_aa(
     WfPath* __restrict__ W, WfShadowQ* __restrict__ SQ, WfClosestQ* __restrict__ CQ,
     int32_t* __restrict__ lists, int32_t* counters, uint32_t slots, uint16_t* __restrict__ keys,
     double* __restrict__ home);
+
+// The thin-lens forms (PT_FLAG_LENS on a BVH scene; pt_shade_lens.hip): the
+// launchers of k_wf_shade_lens<AA> / k_wf_shade_list_lens<AA> on grid x
+// kShadeBlock work-items, aa: PT_FLAG_AA beside the lens.
+void pt_wf_shade_lens(bool aa, dim3 grid, hipStream_t st, const SceneK& S, const RenderK& R, int32_t step,
+                      WfPath* W, WfShadowQ* SQ, WfClosestQ* CQ, int32_t* lists, int32_t* counters, uint32_t slots,
+                      uint16_t* keys);
+void pt_wf_shade_list_lens(bool aa, dim3 grid, hipStream_t st, const SceneK& S, const ListK& R, int32_t step,
+                           const uint32_t* list, const uint32_t* accN, WfPath* W, WfShadowQ* SQ, WfClosestQ* CQ,
+                           int32_t* lists, int32_t* counters, uint32_t slots, uint16_t* keys, double* home);

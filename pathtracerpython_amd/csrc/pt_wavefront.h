@@ -26,6 +26,8 @@
 // With antialiasing (PT_FLAG_AA) a slot has no cached primary hit: every
 // sample starts with its own closest query from the eye (wf_aa_start), issued
 // by the shade step that ends the sample before it (wf_shade_aa).
+// With the thin lens (PT_FLAG_LENS) likewise, from the sample's own lens point
+// (wf_lens_start, wf_shade_lens), with or without PT_FLAG_AA.
 #pragma once
 #include <stddef.h>
 
@@ -239,6 +241,48 @@ PT_HD uint32_t wf_aa_start(const SceneK& S, const LaneJob& J, const AaPixel& X, 
     return kWfWantClosest;
 }
 
+// The thin lens (PT_FLAG_LENS, pt_path.h lens_primary): wf_aa_start with the
+// lens rule.  Sample W->si starts at its own lens point eye' along lens_dir's
+// ray; eye' is the query's origin (kSpP, which wf_finish reads back as the
+// origin of closest_finish) and stays in the record's rows kSpLens for the
+// sample's bounces (bounce<true>; these forms cache no primary hit, so the
+// rows are free).  The eye units are tested in lens_closest's form from the
+// slot's own origin.  AA: PT_FLAG_AA beside the lens, a template parameter
+// down to the kernels (pt_path.h lens_point).
+template <bool AA>
+PT_HD uint32_t wf_lens_start(const SceneK& S, const LaneJob& J, const AaPixel& X, WfPath* W,
+                             WfClosestQ* cq) {
+    const Spill sp{W->sp, 1};
+    double jx, jy, lx, ly;
+    lens_point<AA>(J.seed, J.pixel, (uint32_t)(J.sample0 + W->si * J.sample_stride), S.kd[kKdLensR], &jx, &jy,
+                   &lx, &ly);
+    const D3 eye = d3(S.kd[kKdEye] + lx, S.kd[kKdEye + 1] + ly, S.kd[kKdEye + 2]);
+    const D3 d0 = lens_dir(S, X.W, X.H, X.ix, X.iy, jx, jy, lx, ly, eye.x, eye.y);
+    sp.put(kSpLens, eye.x);
+    sp.put(kSpLens + 1, eye.y);
+    const D3 dn = unit(d0);
+    sp.put3(kSpP, eye);
+    sp.put3(kSpNd, d0);
+    const F3 o32 = to_f3(eye - ld3(S.kd + kKdCenter));
+    const F3 d32 = to_f3(dn);
+    ClosestAcc acc = closest_init();
+    for (int u = 0; u < S.n_unit; ++u) {   // from the lens point: the unit_eye records
+        const UnitF U = S.unit_eye[u];
+#if PT_WF_AA_PRIMARY_M
+        const OriginU O = origin_q(U, o32);
+        if (closest_unit_m(U, O, U.grp == -1, d32, &acc))   // rare
+            fused_fallback<false, false, true, 2>(S, U, closest_bits_m(U, O, U.grp == -1, d32), nullptr,
+                                                  &acc, sp, nullptr, nullptr);
+#else
+        closest_unit<false>(S, U, origin_u(U, o32), d32, U.grp == -1, sp, kSpP, kSpNd, &acc,
+                            nullptr);
+#endif
+    }
+    wf_put_closest(cq, o32, -1, d32, acc);
+    W->set(kWfPrimary, false, 0);
+    return kWfWantClosest;
+}
+
 // The body of render_lane's loop up to its walks: RNG, light samples, next
 // ray, the fused pass over the uniform units (pt_path.h render_lane).
 // The sort key of a query origin (the BVH frame; render_wavefront's sort):
@@ -263,91 +307,19 @@ PT_HD uint32_t wf_cell(const SceneK& S, F3 o) {
     return m;
 }
 // KEY: the origin's cell in bits 16..27 of the result (the shade kernels take it off, pt_shade.hip)
+// The body is pt_wf_bounce.h, once per camera (wf_begin_bounce_lens: the
+// specular term's eye is the sample's lens point, wf_lens_start).
 template <bool KEY = false>
 PT_HD uint32_t wf_begin_bounce(const SceneK& S, const LaneJob& J, WfPath* W, WfShadowQ* shq,
                                WfClosestQ* cq) {
-    const Spill sp{W->sp, 1};
-    const D3 P = sp.get3(kSpP);
-    const int tri = W->tri, b = W->b();
-    const uint32_t sample = (uint32_t)(J.sample0 + W->si * J.sample_stride);
-    const int obj = S.tri_obj[tri];
-    const TriS R = S.tris[tri];
-    const Mat& m = S.mat[obj];
-    const int ogrp = S.tri_grp[tri];
-    ShadowSet sh;
-    uint32_t w[16];
-#if PT_RNG_PERBLOCK   // as render_lane: one Philox block per light sample, where it is used
-#pragma unroll
-    for (int k = 0; k < kLightSamples; ++k) {
-        uint32_t c[4];
-        rng_block(J.seed, J.pixel, sample, (uint32_t)b, (uint32_t)k, c);
-        shadow_setup_k<false, !PT_WF_LRNG>(S, P, ld3(R.n), k, u_of(c[0]), u_of(c[1]), u_of(c[2]),
-                                           u_of(c[3]), &sh, sp);
-    }
-    sh.key2 = S.n_obj;
-    sh.leak = S.n_obj - 1;
-    rng_block(J.seed, J.pixel, sample, (uint32_t)b, 3u, &w[12]);
-#else
-    // (shadow_setup stores the light points into the home's kSpL slots, where
-    // a PT_WF_LRNG record keeps its RNG key: the two switches exclude each
-    // other)
-    static_assert(!PT_WF_LRNG, "PT_WF_LRNG needs PT_RNG_PERBLOCK (the light points must not overwrite the key)");
-    rng_blocks4(J.seed, J.pixel, sample, (uint32_t)b, w);
-    {
-        double u12[12];
-#pragma unroll
-        for (int i = 0; i < 12; ++i) u12[i] = u_of(w[i]);
-        shadow_setup<false>(S, P, ld3(R.n), u12, &sh, sp);
-    }
-#endif
-    double kf;
-    const D3 nd = bounce(S, R, m, P, sp.get3(kSpNd), u_of(w[12]), u_of(w[13]), u_of(w[14]), &kf);
-    const double kn = W->k * kf;
-    bool trace = (b + 1 < J.bounces);
-    double kk = kn;
-    if (trace && J.rr_depth >= 0 && b >= J.rr_depth) {   // build extension
-        double q = fabs(kn);
-        q = q < 0.05 ? 0.05 : (q > 1.0 ? 1.0 : q);
-        if (u_of(w[15]) >= q) trace = false;
-        else kk = kn / q;
-    }
-    sp.put3(kSpNd, nd);
-    const F3 o32 = to_f3(P - ld3(S.kd + kKdCenter));      // the BVH's frame (the walks)
-    const F3 o32u = to_f3(P - ld3(S.kd + kKdCenterS));   // the uniform units' frame
-    const F3 n32 = to_f3(unit(nd));
-    ClosestAcc ca = closest_init();
-    const bool any_trace = PT_WAVE_ANY(trace);
-    {
-        float oc[kLightSamples] = {-1.0f, -1.0f, -1.0f};
-        for (int u = 0; u < S.n_obj_unit; ++u) {
-            const UnitF U = S.unit[u];
-            const OriginU O = PT_QUAD ? origin_q(U, o32u) : origin_u(U, o32u);
-            const bool do_shadow = PT_WAVE_ANY(!(oc[0] > 0.0f && oc[1] > 0.0f && oc[2] > 0.0f));
-            fused_unit<false, false, true, 3, PT_WF_LRNG != 0>(S, U, O, U.grp == ogrp, do_shadow, any_trace,
-                                                               &sh, n32, &ca, sp, nullptr, 15u, oc);
-        }
-#pragma unroll
-        for (int k = 0; k < kLightSamples; ++k) sh.occ[k] = oc[k] > 0.0f;
-    }
-    if (any_trace) {
-        for (int u = S.n_obj_unit; u < S.n_unit; ++u) {   // the light's units
-            const UnitF U = S.unit[u];
-            closest_unit<false>(S, U, origin_u(U, o32u), n32, U.grp == ogrp, sp, kSpP, kSpNd, &ca,
-                                nullptr);
-        }
-    }
-    uint32_t want = KEY ? wf_cell(S, o32) << 16 : 0u;
-    wf_put_shadow(shq, o32, ogrp, sh);
-    want |= shadow_open<false>(S, &sh);   // the rays still open, one walk each
-    if (trace) {
-        wf_put_closest(cq, o32, ogrp, n32, ca);
-        want |= kWfWantClosest;
-    }
-#pragma unroll
-    for (int k = 0; k < kLightSamples; ++k) W->ln[k] = sh.ln[k];
-    W->kk = kk;
-    W->set(kWfBounce, trace, b);
-    return want;
+    constexpr bool LENS = false;
+#include "pt_wf_bounce.h"
+}
+template <bool KEY = false>
+PT_HD uint32_t wf_begin_bounce_lens(const SceneK& S, const LaneJob& J, WfPath* W, WfShadowQ* shq,
+                                    WfClosestQ* cq) {
+    constexpr bool LENS = true;
+#include "pt_wf_bounce.h"
 }
 
 // Shade step >= 1, first half: finish the pending work of the slot with the
@@ -371,16 +343,22 @@ struct WfMoments : MomentMem { static constexpr bool kMoments = true; };
 // AaMomentSched's order), and a path's end restarts from the eye.  Returns
 // kWfNextPrimary when the slot's next sample is to be started in this shade
 // step (wf_aa_start; d0 and pq are unused).
+// LENS (the thin lens, wf_lens_start): AA's per-sample form whether or not the
+// launch is antialiased (AA is then the jitter alone), the primary query's
+// origin being the sample's lens point, which kSpP still holds.
 enum : int { kWfNextNone = 0, kWfNextBounce = 1, kWfNextPrimary = 2 };
-template <class Home, bool AA = false>
+template <class Home, bool AA = false, bool LENS = false>
 PT_HD int wf_finish(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, const WfShadowQ* shq,
                     const WfClosestQ* cq, const WfClosestQ* pq, Home home) {
     const Spill sp{W->sp, 1};
-    if constexpr (AA) {
+    if constexpr (AA || LENS) {
         if (W->state() == kWfPrimary) {   // aa_primary: closest(eye, d0 of this sample)
             const D3 dj = sp.get3(kSpNd);
             D3 P0 = d3(0, 0, 0);
-            const int tri0 = closest_finish<false, false, true>(S, wf_get_acc(*cq), ld3(S.eye), unit(dj),
+            D3 eye;
+            if constexpr (LENS) eye = sp.get3(kSpP);   // lens_primary: from the sample's lens point
+            else eye = ld3(S.eye);
+            const int tri0 = closest_finish<false, false, true>(S, wf_get_acc(*cq), eye, unit(dj),
                                                                 &P0, nullptr);
             if (tri0 >= 0 && tri0 < S.n_obj_tri) {
                 W->set(kWfBegin, false, 0);   // (b = 0; begin_bounce sets the state)
@@ -471,7 +449,7 @@ PT_HD int wf_finish(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, const W
             acc = d3(0, 0, 0);
         }
         ++si;
-        if constexpr (AA) {   // next sample: its own primary query
+        if constexpr (AA || LENS) {   // next sample: its own primary query
             W->acc[0] = acc.x; W->acc[1] = acc.y; W->acc[2] = acc.z;
             W->si = si;
             if (si < J.n_samples) return kWfNextPrimary;
@@ -516,6 +494,15 @@ PT_HD uint32_t wf_shade_aa(const SceneK& S, const LaneJob& J, const AaPixel& X, 
     if (next == kWfNextBounce) return wf_begin_bounce<KEY>(S, J, W, shq, cq);
     return next == kWfNextPrimary ? wf_aa_start(S, J, X, W, cq) : 0u;
 }
+// The thin-lens shade step: wf_shade_aa with the lens's sample start and the
+// specular term's eye (AA: PT_FLAG_AA beside the lens).
+template <bool KEY, bool AA, class Home = WfSum>
+PT_HD uint32_t wf_shade_lens(const SceneK& S, const LaneJob& J, const AaPixel& X, WfPath* W, WfShadowQ* shq,
+                             WfClosestQ* cq, Home home = Home{}) {
+    const int next = wf_finish<Home, AA, true>(S, J, d3(0, 0, 0), W, shq, cq, nullptr, home);
+    if (next == kWfNextBounce) return wf_begin_bounce_lens<KEY>(S, J, W, shq, cq);
+    return next == kWfNextPrimary ? wf_lens_start<AA>(S, J, X, W, cq) : 0u;
+}
 
 // Where the slots of a launch get their jobs (pt_job.h): the pixels of a
 // frame, `split` slots each, or the entries of an accumulator pass's active
@@ -554,7 +541,9 @@ PT_HD uint32_t wf_primary_step(const SceneK& S, const Src& src, uint32_t entry, 
 // later sample starts in the step that ends the one before it.
 // Later steps: a finished slot costs one load, its job is only built when it
 // runs.
-template <bool AA, class Src, class Home>
+// LENS (the thin lens): AA's form — a primary query per sample — whether or
+// not the launch is antialiased, started by wf_lens_start.
+template <bool AA, bool LENS = false, class Src, class Home>
 PT_HD uint32_t wf_slot_step(const SceneK& S, const Src& src, int32_t step, uint32_t tid, WfPath* W,
                             WfShadowQ* SQ, WfClosestQ* CQ, const WfClosestQ* CQP, Home home) {
     const uint32_t entry = tid >> src.R.split_log2;
@@ -565,17 +554,25 @@ PT_HD uint32_t wf_slot_step(const SceneK& S, const Src& src, int32_t step, uint3
         W[tid].acc[0] = W[tid].acc[1] = W[tid].acc[2] = 0.0;
         W[tid].put_rkey(j.J);
         const bool go = j.valid && j.J.n_samples > 0 && j.J.bounces > 0;
-        if constexpr (AA) {
+        if constexpr (AA || LENS) {
             W[tid].si = 0;
             W[tid].set(kWfDone, false, 0);
             j.J.seed = src.R.seed;   // (wave-uniform: aa_jitter's rng_block takes its key in scalar registers)
-            if (go) want = wf_aa_start(S, j.J, AaPixel{src.R.W, src.R.H, j.ix, j.iy}, &W[tid], &CQ[tid]);
+            if constexpr (LENS) {
+                if (go) want = wf_lens_start<AA>(S, j.J, AaPixel{src.R.W, src.R.H, j.ix, j.iy}, &W[tid], &CQ[tid]);
+            } else {
+                if (go) want = wf_aa_start(S, j.J, AaPixel{src.R.W, src.R.H, j.ix, j.iy}, &W[tid], &CQ[tid]);
+            }
         } else {
             W[tid].set(go ? kWfPrimary : kWfDone, false, 0);
         }
     } else if (entry < src.n_prim() && W[tid].state() != kWfDone) {
         auto j = src.job(S, tid);
-        if constexpr (AA) {
+        if constexpr (LENS) {
+            j.J.seed = src.R.seed;   // (as in step 0; the slot is valid)
+            want = wf_shade_lens<true, AA>(S, j.J, AaPixel{src.R.W, src.R.H, j.ix, j.iy}, &W[tid], &SQ[tid],
+                                           &CQ[tid], home);
+        } else if constexpr (AA) {
             j.J.seed = src.R.seed;   // (as in step 0; the slot is valid)
             want = wf_shade_aa<true>(S, j.J, AaPixel{src.R.W, src.R.H, j.ix, j.iy}, &W[tid], &SQ[tid], &CQ[tid],
                                      home);

@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _native
 from ._abi import (PT_FLAG_AA, PT_FLAG_COUNT, PT_FLAG_LENS, PT_FLAG_FORCE_F64, PT_FLAG_KERNEL_TIMES, PT_FLAG_MEGAKERNEL,
-                   PT_FLAG_OUT_F64, PT_FLAG_RR, PT_FLAG_WALK_COUNT, PtStats, band_rows, make_denoise,
+                   PT_FLAG_OUT_F64, PT_FLAG_RR, PT_FLAG_WALK_COUNT, PtLaunchInfo, PtStats, band_rows, make_denoise,
                    make_lens, make_params)
 from .pack import pack_scene
 
@@ -113,7 +113,8 @@ class Renderer:
         aa=True: a jittered primary ray per sample (not with stats; on
         scenes with a BVH through the wavefront kernels, like any render).
         lens: through the renderer's lens (None: iff it has one; not with
-        stats; always the single kernel)."""
+        stats; on scenes with a BVH through the wavefront kernels, like any
+        render — last_launch() tells which path a launch took)."""
         p = self.params(width, height, spp, bounces, seed, rr, rr_depth, force_f64,
                         count=stats, out_f64=out_f64, megakernel=megakernel, aa=aa, lens=lens, **band)
         return self.render_params(p, stats=stats)
@@ -163,6 +164,16 @@ class Renderer:
         ms = C.c_float(0)
         _native.check(self._lib.pt_last_kernel_ms(self._h, C.byref(ms)), "pt_last_kernel_ms")
         return ms.value
+
+    def last_launch(self):
+        """The path of this handle's last launch (pt_last_launch_info): path
+        (PT_PATH_NONE / PT_PATH_SINGLE / PT_PATH_WAVEFRONT), steps (the
+        wavefront's shade launches; 1 for the single kernel), lanes_per_pixel
+        and flags."""
+        info = PtLaunchInfo()
+        _native.check(self._lib.pt_last_launch_info(self._h, C.byref(info)), "pt_last_launch_info")
+        return {"path": info.path, "steps": info.steps, "lanes_per_pixel": info.lanes_per_pixel,
+                "flags": info.flags}
 
     # ------------------------------------------- batched Pool callables --
     def intersect_objects(self, rays):

@@ -4,7 +4,9 @@ document and writes it to --out, default profiles/lens_k2.json, stamped with
 pt_build_id).
 
     python3 scripts/bench_lens.py [--parts uniform,list,effect] [--out FILE]
+    python3 scripts/bench_lens.py --parts k5            (writes profiles/lens_k5.json)
     python3 scripts/bench_lens.py --parts parent --parent-root DIR [--rounds 5]
+    python3 scripts/bench_lens.py --parts parent_k5 --parent-root DIR [--rounds 5]
 
 The K2 frame: Cornell 512x512, 64 spp, 4 bounces, seed 9, lens R = 0.25,
 zf = -24.  Kernel times are HIP events (pt_last_kernel_ms), one process, the
@@ -21,10 +23,23 @@ last --keep (default 10).
   parent   `python bench.py --gpus 1` on this tree and on the parent commit's
            (DIR: a built checkout of it) in alternating child processes,
            --rounds each (scripts/bench_aa.py part_parent; its own document,
-           default profiles/lens_k2_parent.json)"""
+           default profiles/lens_k2_parent.json)
+  k5       a scene with a BVH (synth.write_k5_scene, 100k triangles, seed 0,
+           512x512, 16 spp, 4 bounces, the same lens): the lens through the
+           wavefront kernels (pt_shade_lens.hip) with and without PT_FLAG_AA
+           beside the lens single kernel (megakernel=True), the antialiased and
+           the centre-ray wavefront render (lens=False), each launch's path
+           from pt_last_launch_info; and all 64 samples in one list pass
+           through both lens paths
+  parent_k5  `python bench.py --gpus 1` and `python bench.py --gpus 1 --config
+           k5` (bench.py's own steps and warm-up) on this tree and on the
+           parent commit's, alternating child processes, --rounds each: the
+           parent's min-max and this tree's median per config (its own
+           document, default profiles/lens_k5_parent.json)"""
 import argparse
 import json
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -48,15 +63,21 @@ def main():
     ap.add_argument("--steps", type=int, default=20, help="part parent: bench.py --steps")
     ap.add_argument("--warmup", type=int, default=5, help="part parent: bench.py --warmup")
     ap.add_argument("--parent-root", default=None)
+    ap.add_argument("--configs", default="k2,k5", help="part parent_k5: bench.py --config values")
+    ap.add_argument("--order", default="parent,new", help="part parent_k5: which tree runs first in a round")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     parts = args.parts.split(",")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "lens_k2_parent.json" if parts == ["parent"] else "lens_k2.json")
-    if parts == ["parent"]:
+        name = {"parent": "lens_k2_parent.json", "parent_k5": "lens_k5_parent.json", "k5": "lens_k5.json"}
+        args.out = os.path.join(ROOT, "profiles", name.get(parts[0], "lens_k2.json") if len(parts) == 1
+                                else "lens_k2.json")
+    if parts in (["parent"], ["parent_k5"]):
         if not args.parent_root:
-            raise SystemExit("--parts parent needs --parent-root")
-        res = part_parent(args)
+            raise SystemExit("--parts %s needs --parent-root" % parts[0])
+        res = part_parent(args) if parts == ["parent"] else part_parent_k5(args)
+    elif parts == ["k5"]:
+        res = part_k5(args)
     else:
         res = measure(args, parts)
     text = json.dumps(res, indent=1)
@@ -64,6 +85,112 @@ def main():
     with open(args.out, "w") as f:
         f.write(text + "\n")
     print(text)
+
+
+def part_parent_k5(args):
+    """bench.py's K2 and K5 lines of the parent's tree and of this one, in
+    alternating child processes."""
+    def line(root, config):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--config", config],
+                             cwd=root, capture_output=True, text=True, timeout=900)
+        if out.returncode != 0:
+            raise SystemExit(f"bench.py --config {config} in {root} failed:\n{out.stderr[-2000:]}")
+        d = json.loads(out.stdout.strip().splitlines()[-1])
+        print(f"{config} {os.path.relpath(root, ROOT)}: {d['ms_per_step']:.4f} ms per step", file=sys.stderr, flush=True)
+        return d
+    roots = {"parent": os.path.abspath(args.parent_root), "new": ROOT}
+    trees = tuple((name, roots[name]) for name in args.order.split(","))
+    res = {"rounds": args.rounds, "order": ", ".join(n for n, _ in trees) + ", ... per config"}
+    for config in args.configs.split(","):
+        rows = {name: [] for name, _ in trees}
+        for _ in range(args.rounds):
+            for name, root in trees:
+                rows[name].append(line(root, config))
+        row = {"command": "bench.py --gpus 1 --config " + config, "metric": "ms_per_step"}
+        for name in rows:
+            v = [float(d["ms_per_step"]) for d in rows[name]]
+            row[name] = {"build_id": rows[name][-1].get("build_id"), "ms_per_step": stat(v), "values": v,
+                         "value": stat([float(d["value"]) for d in rows[name]]), "unit": rows[name][-1].get("unit")}
+        row["new_median_inside_parent_spread"] = bool(
+            row["parent"]["ms_per_step"]["min"] <= row["new"]["ms_per_step"]["median"]
+            <= row["parent"]["ms_per_step"]["max"])
+        res[config] = row
+    return res
+
+
+def part_k5(args):
+    """The lens on a BVH scene: its wavefront form beside the single kernel,
+    the antialiased and the centre-ray wavefront render."""
+    import tempfile
+    import torch
+    torch.cuda.set_device(0)
+    from pathtracerpython_amd import _native, scene_reader
+    from pathtracerpython_amd._abi import PATH_NAMES, make_adapt
+    from pathtracerpython_amd.adaptive import Accumulator
+    from pathtracerpython_amd.render import Renderer
+    from pathtracerpython_amd.synth import write_k5_scene
+    scene_reader.VERBOSE = False
+    Wb = Hb = 512
+    spp, bounces = 16, 4
+    k5 = scene_reader.Scene(write_k5_scene(tempfile.mkdtemp(), n_tris=100_000, seed=0, size=Wb))
+    out = {"shape": {"scene": "K5 synth", "n_tris": 100_000, "width": Wb, "height": Hb, "spp": spp,
+                     "bounces": bounces, "seed": SEED, "lens": {"radius": LENS[0], "focus_z": LENS[1]}},
+           "build_id": _native.build_id(), "library": os.path.relpath(_native.LIB_PATH, ROOT),
+           "device": torch.cuda.get_device_name(0), "launches": args.launches, "keep": args.keep}
+
+    def last(xs):
+        return stat(xs[-args.keep:])
+
+    with Renderer(k5, lens=LENS) as rb:
+        fb = torch.empty((Hb, Wb, 3), dtype=torch.float32, device="cuda")
+        p = {"lens_aa_wavefront": rb.params(Wb, Hb, spp, bounces, SEED, aa=True),
+             "lens_wavefront": rb.params(Wb, Hb, spp, bounces, SEED),
+             "lens_aa_single_kernel": rb.params(Wb, Hb, spp, bounces, SEED, aa=True, megakernel=True),
+             "lens_single_kernel": rb.params(Wb, Hb, spp, bounces, SEED, megakernel=True),
+             "aa_wavefront": rb.params(Wb, Hb, spp, bounces, SEED, aa=True, lens=False),
+             "centre_wavefront": rb.params(Wb, Hb, spp, bounces, SEED, lens=False)}
+        ms = {k: [] for k in p}
+        info = {}
+        for _ in range(args.launches):
+            for k in p:
+                rb.render_device(p[k], fb.data_ptr(), 0)
+                torch.cuda.synchronize()
+                ms[k].append(rb.last_kernel_ms())
+                info[k] = rb.last_launch()
+        for k in p:
+            out[k] = {"kernel_ms": last(ms[k]), "path": PATH_NAMES[info[k]["path"]], "steps": info[k]["steps"],
+                      "lanes_per_pixel": info[k]["lanes_per_pixel"]}
+        med = {k: out[k]["kernel_ms"]["median"] for k in p}
+        out["ratio_lens_aa_wavefront_to_lens_aa_single_kernel"] = med["lens_aa_wavefront"] / med["lens_aa_single_kernel"]
+        out["ratio_lens_wavefront_to_lens_single_kernel"] = med["lens_wavefront"] / med["lens_single_kernel"]
+        out["ratio_lens_aa_wavefront_to_aa_wavefront"] = med["lens_aa_wavefront"] / med["aa_wavefront"]
+        out["ratio_lens_wavefront_to_centre_wavefront"] = med["lens_wavefront"] / med["centre_wavefront"]
+        # all 64 samples in one list pass through both lens paths
+        with Accumulator(rb, Wb, Hb) as acc:
+            adapt = make_adapt(0.0, 64, 64, 64)
+            pa = {"lens_aa_wavefront": rb.params(Wb, Hb, 64, bounces, SEED, aa=True),
+                  "lens_aa_single_kernel": rb.params(Wb, Hb, 64, bounces, SEED, aa=True, megakernel=True)}
+            kern = {k: [] for k in pa}
+            linfo, n = {}, {}
+            runs = max(3, args.launches // 5)
+            for _ in range(runs):
+                for k in pa:
+                    acc.reset()
+                    acc.render(pa[k], adapt)
+                    torch.cuda.synchronize()
+                    kern[k].append(rb.last_kernel_ms())
+                    linfo[k] = rb.last_launch()
+                    n[k] = acc.read(S=True, n=True)
+            row = {k: {"pass_kernel_ms": stat(kern[k][-max(2, runs // 2):]), "path": PATH_NAMES[linfo[k]["path"]],
+                       "steps": linfo[k]["steps"], "lanes_per_pixel": linfo[k]["lanes_per_pixel"],
+                       "samples": int(n[k]["n"].sum())} for k in pa}
+            row["same_sums_bit_for_bit"] = bool(np.array_equal(n["lens_aa_wavefront"]["S"].view(np.uint64),
+                                                               n["lens_aa_single_kernel"]["S"].view(np.uint64)))
+            row["kernel_ratio_wavefront_to_single_kernel"] = (
+                row["lens_aa_wavefront"]["pass_kernel_ms"]["median"] /
+                row["lens_aa_single_kernel"]["pass_kernel_ms"]["median"])
+            out["list_all_64_one_pass"] = row
+    return out
 
 
 def measure(args, parts):

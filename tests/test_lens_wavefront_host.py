@@ -1,0 +1,284 @@
+"""The thin-lens wavefront state machine on the host (pt_wavefront.h
+wf_lens_start / wf_shade_lens: a primary query per sample from the sample's own
+lens point, in the slot's own record; tests/hostcheck/pt_lens_wf_host.cpp), in
+its uniform and its list form, against the single kernel's lane code
+(pt_lens_host.cpp hc_render_lens: render_lane_lens / render_lane_moments_lens)
+bit for bit and against the oracle's per-sample colours through the lens
+(tests/lens_ref.py on the mesh scene, cases A and B).  The GPU cases are
+tests/test_gpu_lens_wavefront.py."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import lens_wf_ref as ref
+from conftest import ROOT
+
+from pathtracerpython_amd import _abi
+from pathtracerpython_amd._abi import PT_FLAG_AA, PT_FLAG_LENS, PT_FLAG_RR, make_lens, make_params
+from pathtracerpython_amd.pack import pack_scene
+
+_dp = C.POINTER(C.c_double)
+_up = C.POINTER(C.c_uint32)
+_ip = C.POINTER(C.c_int32)
+
+W = H = 12
+BOUNCES, SEED = ref.BOUNCES, ref.SEED
+ALL = np.arange(W * H, dtype=np.uint32)
+TOL = 1e-12   # the project's f64 bar
+CAP = 64
+
+
+def flags_of(case, extra=0):
+    return PT_FLAG_LENS | (PT_FLAG_AA if ref.CASES[case]["aa"] else 0) | extra
+
+
+def lens_of(case):
+    return make_lens((ref.CASES[case]["R"], ref.CASES[case]["zf"]))
+
+
+def _build(tmp, name):
+    d = os.path.join(ROOT, "tests", "hostcheck")
+    out = str(tmp / ("lib" + name + ".so"))
+    subprocess.run([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-shared",
+                    "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-o", out, name + ".cpp"],
+                   cwd=d, check=True)
+    return C.CDLL(out)
+
+
+@pytest.fixture(scope="module")
+def libs(tmp_path_factory):
+    """pt_lens_wf_host.cpp (the state machine, and the antialiased one it is
+    built on) and pt_lens_host.cpp (the single kernel's lane code)."""
+    tmp = tmp_path_factory.mktemp("lens_wf_host")
+    wf, lane = _build(tmp, "pt_lens_wf_host"), _build(tmp, "pt_lens_host")
+    wf.hc_lens_wf_render.restype = C.c_int
+    wf.hc_lens_wf_render.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, _dp, _ip, _ip,
+                                     C.c_int32]
+    wf.hc_lens_wf_pass.restype = C.c_int
+    wf.hc_lens_wf_pass.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _up, C.c_uint32, C.c_uint32, C.c_uint32,
+                                   C.c_uint32, C.c_uint32, C.c_int, _dp, _dp, _up, _ip, _ip, C.c_int32]
+    wf.hc_aa_wf_render.restype = C.c_int
+    wf.hc_aa_wf_render.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, _dp, _ip, _ip, C.c_int32]
+    lane.hc_render_lens.restype = C.c_int
+    lane.hc_render_lens.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int32, _dp, _dp, _dp]
+    return wf, lane
+
+
+@pytest.fixture(scope="module")
+def pk(mesh_golden):
+    ref.use_scene(mesh_golden[0])
+    return pack_scene(mesh_golden[0])
+
+
+@pytest.fixture(scope="module")
+def frames(pk):
+    """{case: the oracle's per-sample frames [n, H, W, 3]}, coverage asserted."""
+    return {c: ref.frames(c) for c in ("A", "B")}
+
+
+def wf_render(lib, pk, L, p, split, fresh=1):
+    """(sum [H, W, 3], shade steps that found work, busy slots after each step)"""
+    out = np.zeros((p.height, p.width, 3))
+    steps = C.c_int32(0)
+    busy = np.full(CAP, -1, dtype=np.int32)
+    rc = lib.hc_lens_wf_render(C.addressof(pk.desc), C.addressof(L), C.addressof(p), split, fresh,
+                               out.ctypes.data_as(_dp), C.byref(steps), busy.ctypes.data_as(_ip), CAP)
+    assert rc == 0
+    return out, steps.value, busy
+
+
+def wf_pass(lib, pk, L, p, lst, rule, split, S, Q, n, fresh=1):
+    """One list pass on copies of S, Q, n: (S, Q, n, steps, busy)."""
+    S, Q, n = S.copy(), Q.copy(), n.copy()
+    lst = np.ascontiguousarray(lst, dtype=np.uint32)
+    steps = C.c_int32(0)
+    busy = np.full(CAP, -1, dtype=np.int32)
+    rc = lib.hc_lens_wf_pass(C.addressof(pk.desc), C.addressof(L), C.addressof(p), lst.ctypes.data_as(_up),
+                             len(lst), *rule, split, fresh, S.ctypes.data_as(_dp), Q.ctypes.data_as(_dp),
+                             n.ctypes.data_as(_up), C.byref(steps), busy.ctypes.data_as(_ip), CAP)
+    assert rc == 0
+    return S, Q, n, steps.value, busy
+
+
+def aa_wf_render(lib, pk, p, split):
+    out = np.zeros((p.height, p.width, 3))
+    steps = C.c_int32(0)
+    busy = np.full(CAP, -1, dtype=np.int32)
+    rc = lib.hc_aa_wf_render(C.addressof(pk.desc), C.addressof(p), split, 1, out.ctypes.data_as(_dp),
+                             C.byref(steps), busy.ctypes.data_as(_ip), CAP)
+    assert rc == 0
+    return out
+
+
+def lane_code(lib, pk, L, p, lanes):
+    """(sum, S, Q) of the single kernel's lane code, `lanes` per pixel; L None:
+    the scene without a lens."""
+    a, S, Q = (np.zeros((p.height, p.width, 3)) for _ in range(3))
+    rc = lib.hc_render_lens(C.addressof(pk.desc), C.addressof(L) if L is not None else None, C.addressof(p), 0,
+                            int(lanes), a.ctypes.data_as(_dp), S.ctypes.data_as(_dp), Q.ctypes.data_as(_dp))
+    assert rc == 0
+    return a, S, Q
+
+
+def same(a, b):
+    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
+
+
+def empty(h=H, w=W, n0=0):
+    return np.zeros((h, w, 3)), np.zeros((h, w, 3)), np.full((h, w), n0, dtype=np.uint32)
+
+
+@pytest.mark.parametrize("case", ["A", "B"])
+@pytest.mark.parametrize("spp", [8, 5, 3])
+@pytest.mark.parametrize("split", [1, 4, 8])
+def test_both_forms_are_the_lane_code_bit_for_bit(libs, pk, frames, split, spp, case):
+    """Spp 3 on 4 slots, 5 and 3 on 8: slots without a sample."""
+    wf, lane = libs
+    L = lens_of(case)
+    p = make_params(W, H, spp, BOUNCES, SEED, flags_of(case))
+    a, wS, wQ = lane_code(lane, pk, L, p, split)
+    got, steps, _ = wf_render(wf, pk, L, p, split)
+    assert a.any() and same(got, a)
+    per_slot = -(-spp // split)
+    assert 2 < steps <= per_slot * (BOUNCES + 1) + 2
+    S, Q, n, _, _ = wf_pass(wf, pk, L, p, ALL, (spp, spp, spp), split, *empty())
+    assert same(S, wS) and same(Q, wQ) and (n == spp).all()
+    ws, wq = ref.sums(frames[case][:spp])
+    d = [float(np.abs(x - y).max()) for x, y in ((got, ws), (S, ws), (Q, wq))]
+    print(f"{case} split {split} spp {spp}: |sum|, |S|, |Q| vs oracle = {d}")
+    assert max(d) <= TOL
+
+
+def test_mixed_list_pass(libs, pk, frames):
+    """One pass with pixels of unequal n and k (k = 3 from n = 0, k = 5 from
+    n = 3) at 2 slots per entry, on a strict subset; an entry that is no pixel
+    of the frame is skipped."""
+    wf, lane = libs
+    fr = frames["A"]
+    L = lens_of("A")
+    rs = np.random.RandomState(7)
+    n0 = rs.choice(np.array([0, 3, 16], dtype=np.uint32), size=(H, W))
+    S0 = np.where((n0 == 3)[..., None], fr[:3].sum(axis=0), 0.0) + (n0 == 16)[..., None] * 0.25
+    Q0 = np.where((n0 == 3)[..., None], (fr[:3] ** 2).sum(axis=0), 0.0)
+    lst = np.flatnonzero(rs.rand(W * H) < 0.4).astype(np.uint32)
+    lst = lst[n0.ravel()[lst] < 16]
+    assert 20 < len(lst) < W * H - 20 and (np.diff(lst) > 1).any()
+    assert {0, 3} <= set(n0.ravel()[lst].tolist())
+    rule = (3, 17, 5)
+    S, Q, n, _, _ = wf_pass(wf, pk, L, make_params(W, H, 17, BOUNCES, SEED, flags_of("A")),
+                            np.append(lst, np.uint32(W * H + 5)), rule, 2, S0, Q0, n0)
+    listed = np.zeros(W * H, dtype=bool)
+    listed[lst] = True
+    listed = listed.reshape(H, W)
+    for got, was in ((S, S0), (Q, Q0), (n, n0)):
+        assert np.array_equal(got[~listed], was[~listed])
+    k = np.where(n0 < 3, 3, 5)
+    assert np.array_equal(n[listed], (n0 + k)[listed])
+    # the single kernel's list pass: the lane code of each pixel's own range
+    _, s3, q3 = lane_code(lane, pk, L, make_params(W, H, 3, BOUNCES, SEED, flags_of("A")), 2)
+    _, s5, q5 = lane_code(lane, pk, L, make_params(W, H, 5, BOUNCES, SEED, flags_of("A"), sample_begin=3), 2)
+    first = (n0 == 0)[..., None]
+    assert same(S[listed], (S0 + np.where(first, s3, s5))[listed])
+    assert same(Q[listed], (Q0 + np.where(first, q3, q5))[listed])
+    upto = np.where(listed, n0 + k, 0)
+    wS = sum(fr[s] * (s < upto)[..., None] for s in range(8))
+    wQ = sum(fr[s] ** 2 * (s < upto)[..., None] for s in range(8))
+    assert np.abs(S - wS)[listed].max() <= TOL and np.abs(Q - wQ)[listed].max() <= TOL
+
+
+@pytest.mark.parametrize("case", ["rr", "no_bounces", "one_bounce"])
+def test_other_paths(libs, pk, case):
+    wf, lane = libs
+    flags, rr_depth, bounces = {"rr": (PT_FLAG_RR, 1, 4), "no_bounces": (0, 3, 0),
+                                "one_bounce": (0, 3, 1)}[case]
+    w = h = 8
+    L = lens_of("A")
+    p = make_params(w, h, 4, bounces, SEED, flags_of("A", flags), rr_depth)
+    want = None
+    if bounces:
+        import lens_ref
+        want = lens_ref.to_image(ref.samples("A", w, h, bounces, 4, flags, rr_depth), w, h)
+    for split in (1, 4):
+        a, wS, wQ = lane_code(lane, pk, L, p, split)
+        got, steps, _ = wf_render(wf, pk, L, p, split)
+        S, Q, n, lsteps, _ = wf_pass(wf, pk, L, p, np.arange(w * h), (4, 4, 4), split, *empty(h, w))
+        assert same(got, a) and same(S, wS) and same(Q, wQ) and (n == 4).all()
+        if bounces == 0:
+            assert not got.any() and not S.any() and not Q.any()
+            assert steps == 1 and lsteps == 1       # step 0 only: no slot ever starts
+        else:
+            assert got.any()
+            assert np.abs(got - want.sum(axis=0)).max() <= TOL
+            assert np.abs(Q - (want ** 2).sum(axis=0)).max() <= TOL
+
+
+@pytest.mark.parametrize("case", ["A", "B"])
+def test_drain_needs_the_primary_steps(libs, pk, case):
+    """A sample takes its primary query and then `bounces` bounce steps, with
+    PT_FLAG_AA beside the lens (A) and without it (B): every slot is done after
+    per_slot (bounces + 1) + 2 shade steps, and at one slot per pixel some are
+    still busy after the centre-ray form's bound."""
+    wf, _ = libs
+    L = lens_of(case)
+    for spp, split in ((8, 1), (8, 4), (5, 4)):
+        per_slot = -(-spp // split)
+        bound, centre = per_slot * (BOUNCES + 1) + 2, per_slot * BOUNCES + 2
+        p = make_params(W, H, spp, BOUNCES, SEED, flags_of(case))
+        _, steps, busy = wf_render(wf, pk, L, p, split)
+        _, _, _, lsteps, lbusy = wf_pass(wf, pk, L, p, ALL, (spp, spp, spp), split, *empty())
+        for s, b in ((steps, busy), (lsteps, lbusy)):
+            print(f"{case} spp {spp} split {split}: {s} steps of {bound}; busy after step {centre}: {b[centre - 1]}")
+            assert s <= bound and b[s - 1] == 0 and (b[:s - 1] > 0).all()
+            assert np.array_equal(busy[:s], b[:s])
+            if split == 1:
+                assert b[centre - 1] > 0      # the centre-ray step count would cut these paths
+
+
+def test_stale_buffers(libs, pk):
+    """The buffers hold another run's state (a wider launch of the other form,
+    another seed, an antialiased run without the lens): step 0 initialises
+    everything a run reads."""
+    wf, _ = libs
+    L, Lb = lens_of("A"), lens_of("B")
+    p = make_params(W, H, 5, BOUNCES, SEED, flags_of("A"))
+    other = make_params(W, H, 8, 2, 11, flags_of("B", PT_FLAG_RR), 0)
+    clean = wf_render(wf, pk, L, p, 2)[0]
+    clean_l = wf_pass(wf, pk, L, p, ALL, (5, 5, 5), 2, *empty())[:3]
+    wf_pass(wf, pk, Lb, other, ALL, (8, 8, 8), 4, *empty())
+    assert same(wf_render(wf, pk, L, p, 2, fresh=0)[0], clean)
+    wf_render(wf, pk, Lb, other, 8)
+    got = wf_pass(wf, pk, L, p, ALL, (5, 5, 5), 2, *empty(), fresh=0)[:3]
+    assert same(got[0], clean_l[0]) and same(got[1], clean_l[1]) and np.array_equal(got[2], clean_l[2])
+    assert same(wf_render(wf, pk, L, p, 2, fresh=0)[0], clean)
+    aa_wf_render(wf, pk, make_params(W, H, 8, BOUNCES, 11, PT_FLAG_AA), 4)   # (the same buffers)
+    assert same(wf_render(wf, pk, L, p, 2, fresh=0)[0], clean)
+    got = wf_pass(wf, pk, L, p, ALL, (5, 5, 5), 2, *empty(), fresh=0)[:3]
+    assert same(got[0], clean_l[0]) and same(got[1], clean_l[1]) and np.array_equal(got[2], clean_l[2])
+
+
+def test_radius_zero(libs, pk):
+    """R = 0: with PT_FLAG_AA the antialiased state machine, without it the
+    centre-ray lane code, bit for bit."""
+    wf, lane = libs
+    L0 = make_lens((0.0, -24.0))
+    for split in (1, 4):
+        aa = aa_wf_render(wf, pk, make_params(W, H, 8, BOUNCES, SEED, PT_FLAG_AA), split)
+        got = wf_render(wf, pk, L0, make_params(W, H, 8, BOUNCES, SEED, PT_FLAG_LENS | PT_FLAG_AA), split)[0]
+        assert aa.any() and same(got, aa)
+        plain = lane_code(lane, pk, None, make_params(W, H, 8, BOUNCES, SEED), split)[0]
+        got = wf_render(wf, pk, L0, make_params(W, H, 8, BOUNCES, SEED, PT_FLAG_LENS), split)[0]
+        assert same(got, plain) and not same(plain, aa)
+
+
+def test_abi(libs):
+    wf, _ = libs
+    assert C.sizeof(_abi.PtLaunchInfo) == 16 and wf.hc_launch_info_size() == 16
+    assert _abi.PT_API_VERSION == 7 and wf.hc_api_version() == 7
+    assert (_abi.PT_PATH_NONE, _abi.PT_PATH_SINGLE, _abi.PT_PATH_WAVEFRONT) == (0, 1, 2)
+    hdr = open(os.path.join(ROOT, "include", "pt_capi.h")).read()
+    assert "int pt_last_launch_info(pt_scene* scene, pt_launch_info* info);" in hdr
+    for name, v in (("NONE", 0), ("SINGLE", 1), ("WAVEFRONT", 2)):
+        assert f"#define PT_PATH_{name} {v}" in hdr
