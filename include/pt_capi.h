@@ -313,6 +313,82 @@ typedef struct pt_launch_info {
 } pt_launch_info;             /* 16 bytes */
 int pt_last_launch_info(pt_scene* scene, pt_launch_info* info);
 
+/* Radiance for caller-supplied rays (build extension; v7,
+ * additive): the path loop of main.py:186-271 for any camera.  A ray record: */
+typedef struct pt_ray {
+    double o[3];             /* the primary ray's origin                      */
+    double d[3];             /* its direction, any finite length != 0 (not
+                                checked, see below)                           */
+    uint32_t key;            /* the Philox pixel word of the record's draws   */
+    uint32_t reserved;       /* 0 */
+} pt_ray;                    /* 56 bytes */
+/* THE RULE.  Sample s (absolute index: s = sample_begin + j, as for a frame)
+ * of record i is the reference's sample of main.py:186-271 with three
+ * substitutions:
+ *  - the primary ray's origin is o;
+ *  - its direction is d, used exactly where a frame's d0 is used (so it is
+ *    normalised by the same code, and stays unnormalised where d0 does: the
+ *    incoming direction of bounce 0);
+ *  - eye = o wherever the sample reads the eye, the specular term of the
+ *    bounce included.
+ * The Philox pixel word of every draw of the sample is `key` (a frame's
+ * k = ix*H + iy); record i's position in the batch plays no part.  An escape
+ * contributes 0, a light hit light_rgb, per sample; bounces <= 0 gives 0.  The
+ * result of a record is the mean over the spp samples; with out_S / out_Q, also
+ * the per-channel sums S of the sample colours and Q of their squares, formed
+ * sample by sample as an accumulator pass forms them (a whole path per
+ * sample), and then the mean is S / spp.  The value depends on (seed, key, s,
+ * o, d) only: not on the batch, its order, or — at a fixed lanes_per_pixel —
+ * on how a record's samples are dealt to lanes (with lanes_per_pixel 0 the
+ * library chooses from n_rays, and results agree to ~1e-15 relative).  Records
+ * with the same key are allowed and share draws.  Without out_S / out_Q the
+ * samples are summed as a frame's are, so the rays of a frame with the
+ * frame's keys (o = eye, d = (x - ex, y - ey, 0 - ez), key = ix*H + iy) give
+ * pt_render's pixels bit for bit at the same lanes per pixel — the lanes the
+ * frame's launch really gave the pixel: on a scene without a BVH pt_render
+ * gives the frame's top sixteenth of rows (iy >= H - ceil(H/16)) up to 8 times
+ * the lanes of lanes_per_pixel where spp allows it (min(64, spp) caps them),
+ * so those rows agree to ~1e-15 relative instead, unless spp leaves no room
+ * (lanes_per_pixel = the largest power of two <= spp).  A ray that
+ * crosses z = 0 going forward at p is the reference's primary ray of pixel k
+ * on a descriptor with eye = o, H = 1, W = k + 1, ortho = (., p.y, p.x, .).
+ *
+ * A scene made for rays: pt_scene_create_rays sizes the f32 filter's "all"
+ * frame for primary origins anywhere in box ({lo x, y, z, hi x, y, z}, finite,
+ * lo <= hi) as well as the eye, as pt_scene_create_lens does for its disc.
+ * box == NULL: exactly pt_scene_create_on; scenes made by the other entries
+ * keep their records byte for byte.  A ray whose origin lies outside the
+ * frame the scene was prepared for is answered all the same: its primary query
+ * alone is decided in f64, as PT_FLAG_FORCE_F64 decides every query (the f32
+ * bounds are never consulted outside the extent they were derived for); on a
+ * scene made without a box that is every origin outside the box of the
+ * triangles and the eye (the cube of its longest side about its centre).    */
+int pt_scene_create_rays(const pt_scene_desc* desc, int32_t device, const double box[6],
+                         pt_scene** out);
+/* rays_dev: n_rays records in DEVICE memory.  out_rgb_dev: [n_rays][3] float32
+ * (float64 with PT_FLAG_OUT_F64), in the records' order.  out_S_dev, out_Q_dev:
+ * [n_rays][3] float64 each, both or neither (NULL).  p: width, height and the
+ * row fields are ignored; spp >= 1, bounces, seed, sample_begin, rr_depth and
+ * lanes_per_pixel (0, or a power of two <= min(64, spp)) apply.  Flags:
+ * PT_FLAG_RR, PT_FLAG_FORCE_F64 and PT_FLAG_OUT_F64; any other bit is
+ * PT_EINVAL (PT_FLAG_AA, PT_FLAG_LENS, PT_FLAG_COUNT and the stats flags
+ * among them), and so are a NULL ray or output array with n_rays > 0, n_rays
+ * < 0 or >= 2^30, and a launch of 2^32 work-items or more.  n_rays = 0
+ * succeeds and writes nothing.  One launch of the single kernel
+ * k_render_rays, asynchronous on `stream`; pt_last_kernel_ms and
+ * pt_last_launch_info report it.  The device form does not read `reserved`.
+ * Neither form checks o or d: a record whose d is zero or whose o or d is not
+ * finite has a NaN direction or origin, every test against it fails as the
+ * reference's comparisons do, and the record's value is unspecified (0, as an
+ * escape, or NaN); no other record is affected and nothing is read or
+ * written out of bounds.                                                      */
+int pt_radiance_device(pt_scene* scene, const pt_ray* rays_dev, int64_t n_rays,
+                       const pt_render_params* p, void* out_rgb_dev, double* out_S_dev,
+                       double* out_Q_dev, void* stream);
+/* Same, synchronous, on HOST arrays; a record with reserved != 0 is PT_EINVAL. */
+int pt_radiance(pt_scene* scene, const pt_ray* rays, int64_t n_rays, const pt_render_params* p,
+                void* out_rgb, double* out_S, double* out_Q);
+
 /* Adaptive sampling to a noise target (v7, additive; build extension — the
  * reference spends -r samples on every pixel, main.py:186-271).  A pt_accum is
  * a device-resident accumulator of one (width, height) frame of `scene`.  Per

@@ -60,6 +60,34 @@ class PtLaunchInfo(C.Structure):
                 ("flags", C.c_uint32)]
 
 
+# pt_ray (include/pt_capi.h): a record of pt_radiance, 56 bytes
+RAY_DTYPE = [("o", "<f8", (3,)), ("d", "<f8", (3,)), ("key", "<u4"), ("reserved", "<u4")]
+
+
+def make_rays(origins, dirs, keys=None):
+    """The pt_ray records of origins, dirs (n, 3) f64 and keys (n,) u32
+    (None: 0..n-1), a numpy structured array."""
+    import numpy as np
+    o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
+    d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+    n = o.shape[0]
+    if d.shape[0] != n:
+        raise ValueError("origins and dirs must have the same length")
+    if keys is None:
+        k = np.arange(n, dtype=np.uint32)
+    else:
+        k = np.asarray(keys)
+        if k.shape != (n,):
+            raise ValueError("keys must be (n,)")
+        if k.size and (k.min() < 0 or k.max() > 0xFFFFFFFF):
+            raise ValueError("keys must fit 32 bits")
+        k = k.astype(np.uint32)
+    rec = np.zeros(n, dtype=np.dtype(RAY_DTYPE))
+    assert rec.dtype.itemsize == 56
+    rec["o"], rec["d"], rec["key"] = o, d, k
+    return rec
+
+
 class PtRenderParams(C.Structure):
     _fields_ = [
         ("width", C.c_int32), ("height", C.c_int32), ("spp", C.c_int32),

@@ -32,6 +32,9 @@ def _bind(lib):
         "pt_scene_create": ([C.POINTER(PtSceneDesc), C.POINTER(vp)], C.c_int),
         "pt_scene_create_on": ([C.POINTER(PtSceneDesc), C.c_int32, C.POINTER(vp)], C.c_int),
         "pt_scene_create_lens": ([C.POINTER(PtSceneDesc), C.c_int32, C.POINTER(PtLens), C.POINTER(vp)], C.c_int),
+        "pt_scene_create_rays": ([C.POINTER(PtSceneDesc), C.c_int32, dp, C.POINTER(vp)], C.c_int),
+        "pt_radiance_device": ([vp, vp, C.c_int64, C.POINTER(PtRenderParams), vp, vp, vp, vp], C.c_int),
+        "pt_radiance": ([vp, vp, C.c_int64, C.POINTER(PtRenderParams), vp, vp, vp], C.c_int),
         "pt_render_multi": ([C.POINTER(vp), C.c_int32, C.POINTER(PtRenderParams), vp,
                              C.POINTER(PtStats)], C.c_int),
         "pt_scene_destroy": ([vp], None),
@@ -98,7 +101,7 @@ EXPORTS = ("pt_api_version", "pt_last_error", "pt_build_id", "pt_test_fault_inje
            "pt_denoise_device", "pt_denoise", "pt_denoise_times", "pt_accum_features", "pt_accum_read_features",
            "pt_accum_denoise_device", "pt_accum_set_band", "pt_accum_tile_bytes",
            "pt_accum_export_band_device", "pt_accum_import_band_device", "pt_accum_write",
-           "pt_last_launch_info")
+           "pt_last_launch_info", "pt_scene_create_rays", "pt_radiance_device", "pt_radiance")
 
 
 def lib():

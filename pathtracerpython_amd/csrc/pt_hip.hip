@@ -45,6 +45,7 @@ static int fail(int code, const std::string& msg) {
 #include "pt_render.h"
 #include "pt_aa.h"   // the antialiasing kernels' launchers (pt_aa.hip)
 #include "pt_lens.h" // the thin-lens kernels' launchers (pt_lens.hip)
+#include "pt_rays.h" // the ray kernel's launcher (pt_rays.hip)
 #if PT_K2_OWN_TU
 extern template __global__ void k_render<false, false, false>(SceneK, RenderK, void*, StatsDev*);
 #endif
@@ -931,7 +932,8 @@ int pt_scene_create_on(const pt_scene_desc* desc, int32_t device, pt_scene** out
     return pt_scene_create(desc, out);
 }
 
-static int scene_create(const pt_scene_desc* desc, const pt_lens* lens, pt_scene** out);
+static int scene_create(const pt_scene_desc* desc, const pt_lens* lens, pt_scene** out,
+                        const double* ray_box = nullptr);
 int pt_scene_create_lens(const pt_scene_desc* desc, int32_t device, const pt_lens* lens, pt_scene** out) {
     if (!lens) return pt_scene_create_on(desc, device, out);
     if (!out) return fail(PT_EINVAL, "null output handle");
@@ -945,6 +947,21 @@ int pt_scene_create_lens(const pt_scene_desc* desc, int32_t device, const pt_len
                                    std::to_string(ndev) + " visible)");
     DeviceGuard g(device);
     return scene_create(desc, lens, out);
+}
+
+int pt_scene_create_rays(const pt_scene_desc* desc, int32_t device, const double box[6], pt_scene** out) {
+    if (!box) return pt_scene_create_on(desc, device, out);
+    if (!out) return fail(PT_EINVAL, "null output handle");
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(PT_ENODEV, "no HIP device visible (the MI355X path needs a gfx950 GPU)");
+    if (device == -1) return scene_create(desc, nullptr, out, box);   // the current device
+    if (device < 0 || device >= ndev)
+        return fail(PT_EINVAL, "device " + std::to_string(device) + " out of range (" +
+                                   std::to_string(ndev) + " visible)");
+    DeviceGuard g(device);
+    return scene_create(desc, nullptr, out, box);
 }
 
 // FNV-1a over the descriptor's arrays and constants
@@ -967,19 +984,20 @@ static uint64_t scene_fingerprint(const pt_scene_desc* d) {
 
 int pt_scene_create(const pt_scene_desc* desc, pt_scene** out) { return scene_create(desc, nullptr, out); }
 
-static int scene_create(const pt_scene_desc* desc, const pt_lens* lens, pt_scene** out) {
+static int scene_create(const pt_scene_desc* desc, const pt_lens* lens, pt_scene** out, const double* ray_box) {
     if (!out) return fail(PT_EINVAL, "null output handle");
     *out = nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(PT_ENODEV, "no HIP device visible (the MI355X path needs a gfx950 GPU)");
     pt_scene* s = new pt_scene();
-    std::string err = prepare_scene(desc, &s->host, lens);
+    std::string err = prepare_scene(desc, &s->host, lens, ray_box);
     if (!err.empty()) { delete s; return fail(PT_EINVAL, err); }
     s->has_lens = lens != nullptr;
     if (hipGetDevice(&s->device) != hipSuccess) { delete s; return fail(PT_EHIP, "hipGetDevice failed"); }
     s->fingerprint = scene_fingerprint(desc);   // (prepare_scene checked the arrays)
     if (lens) fnv(&s->fingerprint, lens, sizeof(*lens));   // (another frame: no mixing with lens-free handles)
+    if (ray_box) fnv(&s->fingerprint, ray_box, 6 * sizeof(double));   // (likewise)
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, s->device) == hipSuccess) {
         if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos) {
@@ -1557,6 +1575,104 @@ int pt_render_device(pt_scene* s, const pt_render_params* p, void* out_dev, void
         }
     }
     return PT_OK;
+}
+
+// pt_radiance (include/pt_capi.h): one launch of k_render_rays (pt_rays.hip)
+static_assert(sizeof(pt_ray) == sizeof(RayK) && offsetof(pt_ray, d) == offsetof(RayK, d) &&
+                  offsetof(pt_ray, key) == offsetof(RayK, key),
+              "pt_ray is the kernels' RayK");
+int pt_radiance_device(pt_scene* s, const pt_ray* rays_dev, int64_t n_rays, const pt_render_params* p,
+                       void* out_rgb_dev, double* out_S_dev, double* out_Q_dev, void* stream) {
+    if (!p) return fail(PT_EINVAL, "null params");
+    if (!s) return fail(PT_EINVAL, "null scene");
+    if (p->flags & ~(uint32_t)(PT_FLAG_RR | PT_FLAG_FORCE_F64 | PT_FLAG_OUT_F64))
+        return fail(PT_EINVAL, "unsupported flag bits: pt_radiance takes PT_FLAG_RR, PT_FLAG_FORCE_F64 and "
+                               "PT_FLAG_OUT_F64 only (the ray kernel does not count, jitter or draw a lens point)");
+    if (p->spp <= 0) return fail(PT_EINVAL, "spp must be > 0");
+    if (p->bounces < 0) return fail(PT_EINVAL, "bounces must be >= 0");
+    if (p->sample_begin < 0) return fail(PT_EINVAL, "sample_begin must be >= 0");
+    uint32_t cap = 64;
+    while (cap > 1 && (int32_t)cap > p->spp) cap >>= 1;
+    if (p->lanes_per_pixel != 0) {
+        const int32_t l = p->lanes_per_pixel;
+        if (l < 0 || (l & (l - 1)) != 0 || l > (int32_t)cap)
+            return fail(PT_EINVAL, "lanes_per_pixel must be 0 or a power of two <= min(64, spp)");
+    }
+    if (n_rays < 0 || n_rays >= ((int64_t)1 << 30)) return fail(PT_EINVAL, "need 0 <= n_rays < 2^30");
+    if ((out_S_dev == nullptr) != (out_Q_dev == nullptr)) return fail(PT_EINVAL, "out_S and out_Q: both or neither");
+    if (n_rays == 0) return PT_OK;
+    if (!rays_dev) return fail(PT_EINVAL, "null ray array");
+    if (!out_rgb_dev) return fail(PT_EINVAL, "null output");
+    DeviceGuard g(s->device);
+    hipStream_t st = (hipStream_t)stream;
+    const bool bvh = s->dev.n_bnode > 0;
+    RaysK R;
+    R.spp = p->spp; R.bounces = p->bounces;
+    R.seed = p->seed;
+    R.rr_depth = (p->flags & PT_FLAG_RR) ? std::max(0, p->rr_depth) : -1;
+    R.sample_begin = p->sample_begin;
+    R.n_rays = (uint32_t)n_rays;
+    R.out_f64 = (p->flags & PT_FLAG_OUT_F64) ? 1 : 0;
+    R.frame_x = s->host.frame_x;
+    // lanes per record: the rule of a launch of n_rays pixels
+    R.split = p->lanes_per_pixel > 0 ? (uint32_t)p->lanes_per_pixel
+                                     : choose_split((uint64_t)n_rays, (uint64_t)n_rays, p->spp, bvh,
+                                                    min_lanes_of(s->n_cu));
+    R.split_log2 = log2_ceil(R.split);
+    const uint64_t threads = (uint64_t)n_rays << R.split_log2;
+    if (threads >= ((uint64_t)1 << 32))
+        return fail(PT_EINVAL, "launch needs 2^32 or more work-items (32-bit lane index)");
+    if (s->timed) HIPCHK(hipStreamWaitEvent(st, s->ev1, 0));
+    const dim3 grid((unsigned)((threads + kRenderBlock - 1) / kRenderBlock));
+    HIPCHK(hipEventRecord(s->ev0, st));
+    s->last = pt_launch_info{PT_PATH_SINGLE, 1, (int32_t)R.split, p->flags};
+    pt_rays_render((p->flags & PT_FLAG_FORCE_F64) != 0, bvh, grid, st, s->dev, R, (const RayK*)rays_dev,
+                   out_rgb_dev, out_S_dev, out_Q_dev);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(s->ev1, st));
+    s->timed = true;
+    return PT_OK;
+}
+
+int pt_radiance(pt_scene* s, const pt_ray* rays, int64_t n_rays, const pt_render_params* p, void* out_rgb,
+                double* out_S, double* out_Q) {
+    if (!p) return fail(PT_EINVAL, "null params");
+    if (!s) return fail(PT_EINVAL, "null scene");
+    if (n_rays < 0 || n_rays >= ((int64_t)1 << 30)) return fail(PT_EINVAL, "need 0 <= n_rays < 2^30");
+    if (n_rays > 0 && !rays) return fail(PT_EINVAL, "null ray array");
+    if (n_rays > 0 && !out_rgb) return fail(PT_EINVAL, "null output");
+    for (int64_t i = 0; i < n_rays; ++i)
+        if (rays[i].reserved != 0) return fail(PT_EINVAL, "ray record " + std::to_string(i) + ": reserved must be 0");
+    if ((out_S == nullptr) != (out_Q == nullptr)) return fail(PT_EINVAL, "out_S and out_Q: both or neither");
+    DeviceGuard g(s->device);
+    const bool mom = out_S != nullptr;
+    const size_t n = (size_t)n_rays;
+    const size_t elem = (p->flags & PT_FLAG_OUT_F64) ? sizeof(double) : sizeof(float);
+    // one staging block: the records, the means, S and Q (256-byte aligned sections)
+    const size_t b_rays = align_up(n * sizeof(pt_ray)), b_rgb = align_up(n * 3 * elem), b_m = align_up(n * 3 * sizeof(double));
+    char* blk = nullptr;
+    if (n > 0) HIPCHK(hipMalloc((void**)&blk, b_rays + b_rgb + 2 * b_m));
+    int rc = PT_OK;
+    if (n > 0 && hipMemcpyAsync(blk, rays, n * sizeof(pt_ray), hipMemcpyHostToDevice, s->stream) != hipSuccess)
+        rc = fail(PT_EHIP, "hipMemcpy ray records");
+    double* dS = mom && blk ? (double*)(blk + b_rays + b_rgb) : nullptr;
+    double* dQ = mom && blk ? (double*)(blk + b_rays + b_rgb + b_m) : nullptr;
+    // (n_rays = 0: the device form checks the parameters and launches nothing)
+    if (rc == PT_OK)
+        rc = pt_radiance_device(s, (const pt_ray*)blk, n_rays, p, blk ? (void*)(blk + b_rays) : nullptr, dS, dQ,
+                                s->stream);
+    if (rc == PT_OK && n > 0) {
+        if (hipMemcpyAsync(out_rgb, blk + b_rays, n * 3 * elem, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+            (mom && (hipMemcpyAsync(out_S, dS, n * 3 * sizeof(double), hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
+                     hipMemcpyAsync(out_Q, dQ, n * 3 * sizeof(double), hipMemcpyDeviceToHost, s->stream) != hipSuccess)) ||
+            hipStreamSynchronize(s->stream) != hipSuccess)
+            rc = fail(PT_EHIP, "copying the results back");
+    }
+    if (blk) {
+        (void)hipStreamSynchronize(s->stream);
+        (void)hipFree(blk);
+    }
+    return rc;
 }
 
 int pt_render(pt_scene* s, const pt_render_params* p, void* out_host, pt_stats* stats) {

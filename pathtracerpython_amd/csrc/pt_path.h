@@ -1795,9 +1795,12 @@ PT_HD D3 nee(const SceneK& S, D3 P, D3 n, int obj, int ogrp, const double u[12],
 // direction and the throughput factor (accumulated_k update).
 // LENS (PT_FLAG_LENS): the specular term's eye is the sample's lens point
 // eye', which the sample's start left in the lane's home rows kSpLens.
-template <bool LENS = false>
+// LENS = 2 (caller-supplied rays, pt_radiance): the eye is the ray record's
+// origin, the three doubles at eye_o.
+template <int LENS = 0>
 PT_HD D3 bounce(const SceneK& S, const TriS& R, const Mat& m, D3 P, D3 d_old,
-                double u_sel, double u_phi, double u_theta, double* kf, const Spill* sp = nullptr) {
+                double u_sel, double u_phi, double u_theta, double* kf, const Spill* sp = nullptr,
+                const double* eye_o = nullptr) {
     const D3 n = ld3(R.n);
     const double xi = 0.0 + (m.kdks - 0.0) * u_sel;
     if (xi <= m.kd) {   // diffuse: phi = arccos(sqrt(u)), theta = 6.28 u
@@ -1814,7 +1817,8 @@ PT_HD D3 bounce(const SceneK& S, const TriS& R, const Mat& m, D3 P, D3 d_old,
     const double nd2 = dot(n, d_old) * 2;
     const D3 r = unit(d3(nd2 * n.x - d_old.x, nd2 * n.y - d_old.y, nd2 * n.z - d_old.z));
     D3 eye;
-    if constexpr (LENS) eye = d3(sp->get(kSpLens), sp->get(kSpLens + 1), S.kd[kKdEye + 2]);
+    if constexpr (LENS == 2) eye = ld3(eye_o);
+    else if constexpr (LENS == 1) eye = d3(sp->get(kSpLens), sp->get(kSpLens + 1), S.kd[kKdEye + 2]);
     else eye = ld3(S.kd + kKdEye);
     const D3 e = unit(eye - P);
     const D3 nd = rotate_y(R, r);
@@ -1927,6 +1931,18 @@ template <class Sched, class = void>
 struct sched_lens { static constexpr bool value = false; };
 template <class Sched>
 struct sched_lens<Sched, decltype((void)Sched::kLens)> { static constexpr bool value = Sched::kLens; };
+// A scheduler of the ray kernels (pt_rays.hip) declares kRays and eye_o(): the
+// origin of its lane's ray record is the specular term's eye (bounce<2>).
+template <class Sched, class = void>
+struct sched_rays {
+    static constexpr bool value = false;
+    PT_HD static const double* eye_o(const Sched&) { return nullptr; }
+};
+template <class Sched>
+struct sched_rays<Sched, decltype((void)Sched::kRays)> {
+    static constexpr bool value = Sched::kRays;
+    PT_HD static const double* eye_o(const Sched& q) { return q.eye_o(); }
+};
 
 // The bounce loop: paths are regenerated in place (Sched::advance), so a
 // wave keeps tracing until all its lanes are out of samples.  The lane's
@@ -1986,8 +2002,9 @@ PT_HD void render_loop(const SceneK& S, const LaneJob& J, int tri, const Spill& 
 #endif
         // next ray (main.py:236-268): it does not depend on the colour
         double kf;
-        const D3 nd = bounce<sched_lens<Sched>::value>(S, R, m, P, sp.get3(kSpNd), u_of(w[12]),
-                                                       u_of(w[13]), u_of(w[14]), &kf, &sp);
+        const D3 nd = bounce<sched_rays<Sched>::value ? 2 : sched_lens<Sched>::value ? 1 : 0>(
+            S, R, m, P, sp.get3(kSpNd), u_of(w[12]), u_of(w[13]), u_of(w[14]), &kf, &sp,
+            sched_rays<Sched>::eye_o(q));
         const double kn = k * kf;
         bool trace = (b + 1 < J.bounces);
         double kk = kn;
@@ -2670,6 +2687,126 @@ PT_HD void render_lane_moments_lens(const SceneK& S, const LaneJob& J, const AaP
     int tri = -1;
     D3 acc = d3(0, 0, 0);
     if (q.start(S, sp, &tri, cnt)) render_loop<FORCE64, false, BVH>(S, J, tri, sp, cnt, q, &acc);
+}
+
+// ------------------------------------------------ caller-supplied rays --
+// pt_radiance (build extension, include/pt_capi.h): sample s
+// of a ray record is the reference's sample (main.py:186-271) with the primary
+// ray's origin o, its direction d where a frame has d0, and eye = o wherever
+// the sample reads the eye; the Philox pixel word is the record's key.  The
+// primary ray is the same for every sample of a record, so its hit is traced
+// once per lane and cached in the home rows kSpP0 as a frame's is
+// (LaneSched).  What LaneSched rebuilds from two rows and the scene's eye, the
+// direction, comes back from the record instead, and so does the specular
+// term's eye: with the direction read from the record the home has two free
+// rows (kSpD0's) beside the cached hit, and o and d are six values; a record
+// is 56 read-only bytes that every sample of the lane shares.
+struct RayK {
+    double o[3], d[3];
+    uint32_t key, reserved;
+};
+static_assert(sizeof(RayK) == 56, "pt_ray is 56 B");
+
+// The f32 filter's bounds over unit_eye and the BVH records hold for origins
+// within X = HostScene::frame_x of the "all" frame's centre on every axis
+// (prepare_scene; the launch record carries it: no scene record changes);
+// anywhere else, a NaN included, they are not consulted.
+PT_HD bool rays_in_frame(const SceneK& S, double X, D3 o) {
+    return fabs(o.x - S.kd[kKdCenter]) <= X && fabs(o.y - S.kd[kKdCenter + 1]) <= X &&
+           fabs(o.z - S.kd[kKdCenter + 2]) <= X;
+}
+
+// The record's primary hit: lens_closest's unit form with per-lane origin
+// terms for an origin inside the frame, FORCE_F64's query for this ray alone
+// outside it (the bounces start on scene surfaces and take the filter again).
+// f32_route (may be null; the host checks): set when the filter's branch ran.
+template <bool FORCE64, bool BVH>
+PT_HD int rays_primary(const SceneK& S, double frame_x, D3 o, D3 d0, const Spill& sp, D3* P, Counters* cnt,
+                       bool* f32_route = nullptr) {
+    if (!FORCE64 && rays_in_frame(S, frame_x, o)) {
+        if (f32_route) *f32_route = true;
+        return lens_closest<false, BVH>(S, o, d0, sp, P, cnt);
+    }
+    return closest<true, false, BVH>(S, o, d0, -1, sp, P, cnt, true);
+}
+
+// LaneSched / MomentSched with the record in the place of (kSpD0, the eye)
+struct RaySched {
+    static constexpr bool kRays = true;
+    const LaneJob& J;
+    const RayK* ray;
+    int tri0;
+    int si;
+    PT_HD uint32_t sample() const { return (uint32_t)(J.sample0 + si * J.sample_stride); }
+    PT_HD uint32_t pixel() const { return J.pixel; }
+    PT_HD const double* eye_o() const { return ray->o; }
+    template <bool COUNT>
+    PT_HD bool advance(const SceneK&, bool done, const Spill& sp, int* tri, D3*, Counters*) {
+        if (!done) return true;
+        if (++si >= J.n_samples) return false;
+        *tri = tri0;
+        sp.put3(kSpP, sp.get3(kSpP0));
+        sp.put3(kSpNd, ld3(ray->d));
+        return true;
+    }
+};
+template <class Home>
+struct RayMomentSched {
+    static constexpr bool kRays = true;
+    const LaneJob& J;
+    const RayK* ray;
+    int tri0;
+    int si;
+    Home& home;
+    PT_HD uint32_t sample() const { return (uint32_t)(J.sample0 + si * J.sample_stride); }
+    PT_HD uint32_t pixel() const { return J.pixel; }
+    PT_HD const double* eye_o() const { return ray->o; }
+    template <bool COUNT>
+    PT_HD bool advance(const SceneK&, bool done, const Spill& sp, int* tri, D3* acc, Counters*) {
+        if (!done) return true;
+        home.add(*acc);
+        *acc = d3(0, 0, 0);
+        if (++si >= J.n_samples) return false;
+        *tri = tri0;
+        sp.put3(kSpP, sp.get3(kSpP0));
+        sp.put3(kSpNd, ld3(ray->d));
+        return true;
+    }
+};
+
+// render_lane / render_lane_moments for a record: tri0, P0 its primary hit
+template <bool FORCE64, bool BVH>
+PT_HD D3 render_lane_rays(const SceneK& S, const LaneJob& J, const RayK* ray, int tri0, D3 P0,
+                          const Spill& sp, Counters* cnt) {
+    D3 acc = d3(0, 0, 0);
+    if (J.n_samples <= 0 || J.bounces <= 0) return acc;
+    if (tri0 < 0 || tri0 >= S.n_obj_tri) {   // the ray escapes or hits the light
+        const D3 v = tri0 < 0 ? d3(0, 0, 0) : ld3(S.kd + kKdLightRgb);
+        for (int i = 0; i < J.n_samples; ++i) acc = acc + v;
+        return acc;
+    }
+    sp.put3(kSpP0, P0);
+    sp.put3(kSpP, P0);
+    sp.put3(kSpNd, ld3(ray->d));
+    RaySched q{J, ray, tri0, 0};
+    render_loop<FORCE64, false, BVH>(S, J, tri0, sp, cnt, q, &acc);
+    return acc;
+}
+template <bool FORCE64, bool BVH, class Home>
+PT_HD void render_lane_moments_rays(const SceneK& S, const LaneJob& J, const RayK* ray, int tri0, D3 P0,
+                                    const Spill& sp, Counters* cnt, Home& home) {
+    if (J.n_samples <= 0) return;
+    if (J.bounces <= 0 || tri0 < 0 || tri0 >= S.n_obj_tri) {
+        const D3 v = (J.bounces <= 0 || tri0 < 0) ? d3(0, 0, 0) : ld3(S.kd + kKdLightRgb);
+        for (int i = 0; i < J.n_samples; ++i) home.add(v);
+        return;
+    }
+    sp.put3(kSpP0, P0);
+    sp.put3(kSpP, P0);
+    sp.put3(kSpNd, ld3(ray->d));
+    D3 acc = d3(0, 0, 0);
+    RayMomentSched<Home> q{J, ray, tri0, 0, home};
+    render_loop<FORCE64, false, BVH>(S, J, tri0, sp, cnt, q, &acc);
 }
 
 }  // namespace pt

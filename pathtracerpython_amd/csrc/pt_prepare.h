@@ -34,6 +34,9 @@ struct HostScene {
     std::vector<int32_t> light_tri;
     std::vector<double> light_cum;
     SceneK k{};   // pointers unset; constants filled
+    // how far from k.center, on every axis, a primary origin may lie for the
+    // f32 filter's eye-frame bounds to hold (pt_path.h rays_in_frame)
+    double frame_x = 0.0;
 };
 
 constexpr int kBvhMinTris = 64;   // objects this large are traversed through the BVH
@@ -430,7 +433,10 @@ inline std::string lens_check(const double eye[3], const pt_lens& L) {
 
 // Returns "" on success, else an error message.  lens (may be null): the
 // thin lens of PT_FLAG_LENS — primary rays start anywhere on its disc.
-inline std::string prepare_scene(const pt_scene_desc* d, HostScene* H, const pt_lens* lens = nullptr) {
+// ray_box (may be null; {lo x, y, z, hi x, y, z}, pt_scene_create_rays): the
+// primary rays of pt_radiance start anywhere in it as well.
+inline std::string prepare_scene(const pt_scene_desc* d, HostScene* H, const pt_lens* lens = nullptr,
+                                 const double* ray_box = nullptr) {
     if (!d) return "null scene descriptor";
     if (d->n_tri <= 0 || d->n_obj_tri < 0 || d->n_obj_tri >= d->n_tri)
         return "need 0 <= n_obj_tri < n_tri (the light must have triangles)";
@@ -467,6 +473,10 @@ inline std::string prepare_scene(const pt_scene_desc* d, HostScene* H, const pt_
         const std::string e = lens_check(d->eye, *lens);
         if (!e.empty()) return e;
     }
+    if (ray_box)
+        for (int i = 0; i < 3; ++i)
+            if (!isfinite(ray_box[i]) || !isfinite(ray_box[3 + i]) || !(ray_box[i] <= ray_box[3 + i]))
+                return "ray box: need finite lo <= hi on every axis";
     double Cs[3], Xs = 0.0;
     for (int i = 0; i < 3; ++i) {
         Cs[i] = 0.5 * (lo[i] + hi[i]);
@@ -478,12 +488,21 @@ inline std::string prepare_scene(const pt_scene_desc* d, HostScene* H, const pt_
         const double r = lens && i < 2 ? lens->radius : 0.0;
         lo[i] = std::min(lo[i], d->eye[i] - r);
         hi[i] = std::max(hi[i], d->eye[i] + r);
+        if (ray_box) {   // (the frame of a scene made without one is untouched)
+            lo[i] = std::min(lo[i], ray_box[i]);
+            hi[i] = std::max(hi[i], ray_box[3 + i]);
+        }
     }
     double C[3], X = 0.0;
     for (int i = 0; i < 3; ++i) {
         C[i] = 0.5 * (lo[i] + hi[i]);
         X = std::max(X, 0.5 * (hi[i] - lo[i]));
     }
+    // rays_in_frame's extent: half of X's padding, so that an origin it admits
+    // is inside |x_i| <= X after its own f32 rounding as well, and the eye and
+    // the box's corners, which sit on the unpadded extent, are admitted whatever
+    // the rounding of C
+    const double Xin = X * 1.0005 + 5e-7;
     X = X * 1.001 + 1e-6;
     const double u = 1.0 / 16777216.0;   // f32 unit roundoff
 
@@ -814,6 +833,7 @@ inline std::string prepare_scene(const pt_scene_desc* d, HostScene* H, const pt_
         H->kd[kKdLightRgb + i] = K.light_rgb[i];
     }
     H->kd[kKdLightSum] = K.light_sum;
+    H->frame_x = Xin;
     if (lens) {
         H->kd[kKdLensR] = lens->radius;
         H->kd[kKdLensZf] = lens->focus_z;

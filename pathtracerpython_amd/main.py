@@ -22,7 +22,10 @@ every flag above; scenes with a BVH keep the wavefront kernels), --aperture R
 --focus-z Z (a thin-lens camera: a lens point per sample on a disc of radius R
 around the eye, focused on the plane z = Z, PT_FLAG_LENS; the two go together;
 with --aa, --noise, --denoise, --checkpoint, --chunk-spp and --local-devices,
-not with --devices N > 1; always the single kernel).  The
+not with --devices N > 1; always the single kernel), --look-at EX EY EZ TX
+TY TZ [--up UX UY UZ] [--fov DEG] (a pinhole at E looking at T in place of the
+scene's camera: cameras.look_at_rays through Renderer.render_rays,
+pt_radiance; with -r, -b, --rr, --seed, --size, --out and --save-raw only).  The
 reference's interactive 3-D viewer flags (--show-scene, --show-normals,
 --show-screen, --show-inter -> plot.py) are accepted and ignored with a
 notice: the pyqtgraph viewer is out of scope.
@@ -54,6 +57,15 @@ def setup(argv=None):
                              '(with --focus-z); the features and --denoise keep the pinhole')
     parser.add_argument('--focus-z', type=float, default=None, metavar='Z',
                         help='with --aperture: the z of the plane in focus (the screen is z = 0)')
+    parser.add_argument('--look-at', type=float, nargs=6, default=None,
+                        metavar=('EX', 'EY', 'EZ', 'TX', 'TY', 'TZ'),
+                        help='render through a pinhole at E looking at T instead of the scene\'s '
+                             'camera (cameras.look_at_rays through Renderer.render_rays); with '
+                             '-r, -b, --rr, --seed, --size, --out and --save-raw only')
+    parser.add_argument('--up', type=float, nargs=3, default=None, metavar=('UX', 'UY', 'UZ'),
+                        help='with --look-at: the direction towards the top of the image (default 0 1 0)')
+    parser.add_argument('--fov', type=float, default=None, metavar='DEG',
+                        help='with --look-at: the vertical field of view in degrees (default 40)')
     parser.add_argument('--size', type=int, nargs=2, metavar=('W', 'H'), default=None)
     parser.add_argument('--save-raw', default=None,
                         help='also save the float framebuffer (.npy, before normalisation)')
@@ -139,6 +151,22 @@ def check_args(args):
     """Reject flag combinations before any rank process starts."""
     if (args.aperture is None) != (args.focus_z is None):
         raise SystemExit('--aperture and --focus-z go together')
+    if args.look_at is None and (args.up is not None or args.fov is not None):
+        raise SystemExit('--up and --fov go with --look-at')
+    if args.look_at is not None:
+        args.up = [0.0, 1.0, 0.0] if args.up is None else args.up
+        args.fov = 40.0 if args.fov is None else args.fov
+        # (the ray kernel is one launch of the single kernel on one device)
+        for on, name in ((args.aa, '--aa'), (args.aperture is not None, '--aperture'),
+                         (args.noise is not None, '--noise'), (args.denoise, '--denoise'),
+                         (args.devices > 1, '--devices > 1'), (args.local_devices is not None, '--local-devices'),
+                         (args.chunk_spp, '--chunk-spp'), (args.checkpoint, '--checkpoint'),
+                         (args.save_aov, '--save-aov')):
+            if on:
+                raise SystemExit(f'--look-at does not combine with {name}: it takes -r, -b, --rr, --seed, '
+                                 '--size, --out and --save-raw')
+        if not 0.0 < args.fov < 180.0:
+            raise SystemExit('--fov: need 0 < DEG < 180')
     if args.aperture is not None and args.devices > 1:
         raise SystemExit('--aperture runs in one process (--devices 1; --local-devices N for more GPUs)')
     if args.local_devices is not None:
@@ -227,6 +255,8 @@ def main(argv=None):
         if rank != 0:
             return None
         return finish(args, arr, fb)
+    if args.look_at is not None:
+        return finish(args, None, render_look_at(scene, args, W, H))
     through_accum = args.noise is not None or args.denoise   # (adaptive.py)
     if args.local_devices is not None:   # N GPUs of this process (render.MultiRenderer)
         from .render import MultiRenderer, image_u8
@@ -276,6 +306,23 @@ def main(argv=None):
         spp = f'up to {args.n_rays}' if args.noise is not None else f'{args.n_rays}'
         print(f'render: {W}x{H}, {spp} spp, {args.n_bounces} bounces, {last}')
     return finish(args, arr, fb)
+
+
+def render_look_at(scene, args, W, H):
+    """The f64 frame of --look-at: cameras.look_at_rays through
+    Renderer.render_rays, the scene prepared for the eye point."""
+    from .cameras import look_at_rays, rays_to_image
+    from .render import Renderer
+    eye = args.look_at[:3]
+    try:
+        o, d, keys = look_at_rays(eye, args.look_at[3:], args.up, args.fov, W, H)
+    except ValueError as e:
+        raise SystemExit(f'--look-at: {e}')
+    with Renderer(scene, ray_box=(eye, eye)) as r:
+        rgb = r.render_rays(o, d, keys, spp=args.n_rays, bounces=args.n_bounces, seed=args.seed, rr=args.rr)
+        print(f'render: {W}x{H} through --look-at, {args.n_rays} spp, {args.n_bounces} bounces, '
+              f'kernel {r.last_kernel_ms():.3f} ms')
+    return np.ascontiguousarray(rays_to_image(rgb, W, H))
 
 
 def report_adaptive(args, res, W, H):

@@ -20,7 +20,7 @@ import numpy as np
 from . import _native
 from ._abi import (PT_FLAG_AA, PT_FLAG_COUNT, PT_FLAG_LENS, PT_FLAG_FORCE_F64, PT_FLAG_KERNEL_TIMES, PT_FLAG_MEGAKERNEL,
                    PT_FLAG_OUT_F64, PT_FLAG_RR, PT_FLAG_WALK_COUNT, PtLaunchInfo, PtStats, band_rows, make_denoise,
-                   make_lens, make_params)
+                   make_lens, make_params, make_rays)
 from .pack import pack_scene
 
 _dp = C.POINTER(C.c_double)
@@ -31,15 +31,26 @@ class Renderer:
     """A scene uploaded to a HIP device (one `pt_scene` handle): the current
     device, or `device`.  lens=(R, zf): a thin-lens camera of aperture radius
     R focused on the plane z = zf (pt_scene_create_lens); renders of this
-    handle then use it unless told otherwise (lens=False)."""
+    handle then use it unless told otherwise (lens=False).  ray_box=(lo, hi):
+    the box the origins of render_rays' rays lie in (pt_scene_create_rays);
+    rays from elsewhere are answered too, their first hit in f64."""
 
-    def __init__(self, scene, device=None, packed=None, lens=None):
+    def __init__(self, scene, device=None, packed=None, lens=None, ray_box=None):
         self.scene = scene
         self.packed = packed if packed is not None else pack_scene(scene)
         self._lib = _native.lib()
         self.lens = None if lens is None else (float(lens[0]), float(lens[1]))
         h = C.c_void_p()
-        if self.lens is not None:
+        self.ray_box = None
+        if ray_box is not None:
+            if lens is not None:
+                raise ValueError("a renderer takes a lens or a ray box, not both")
+            box = np.ascontiguousarray(np.asarray(ray_box, dtype=np.float64).reshape(6))
+            self.ray_box = box.reshape(2, 3)
+            _native.check(self._lib.pt_scene_create_rays(C.byref(self.packed.desc),
+                                                         -1 if device is None else int(device),
+                                                         box.ctypes.data_as(_dp), C.byref(h)), "pt_scene_create_rays")
+        elif self.lens is not None:
             L = make_lens(self.lens)
             _native.check(self._lib.pt_scene_create_lens(C.byref(self.packed.desc),
                                                          -1 if device is None else int(device),
@@ -159,6 +170,27 @@ class Renderer:
         from .adaptive import render_adaptive
         return render_adaptive(self, width, height, max_spp, bounces, seed, rr, rr_depth, tol,
                                megakernel=megakernel, denoise=denoise, aa=aa, lens=lens, **rule)
+
+    def render_rays(self, origins, dirs, keys=None, spp=1, bounces=1, seed=None, rr=False, rr_depth=3,
+                    force_f64=False, out_f64=True, moments=False, sample_begin=0, lanes_per_pixel=0):
+        """Path-traced radiance of caller-supplied rays (pt_radiance): origins,
+        dirs (n, 3) f64, keys (n,) u32 — the Philox pixel word of each ray's
+        draws; None means 0..n-1.  Returns rgb (n, 3), the mean over spp
+        samples, float64 (float32 with out_f64=False); with moments=True
+        (rgb, S, Q), the per-channel sums of the sample colours and of their
+        squares.  The cameras module makes the rays of a few cameras."""
+        rec = make_rays(origins, dirs, keys)
+        n = rec.shape[0]
+        p = self.params(1, 1, spp, bounces, seed, rr, rr_depth, force_f64, out_f64=out_f64,
+                        sample_begin=sample_begin, lanes_per_pixel=lanes_per_pixel, lens=False)
+        rgb = np.zeros((n, 3), dtype=np.float64 if out_f64 else np.float32)
+        S = np.zeros((n, 3), dtype=np.float64) if moments else None
+        Q = np.zeros((n, 3), dtype=np.float64) if moments else None
+        _native.check(self._lib.pt_radiance(self._h, C.c_void_p(rec.ctypes.data), n, C.byref(p),
+                                            C.c_void_p(rgb.ctypes.data),
+                                            C.c_void_p(S.ctypes.data) if moments else None,
+                                            C.c_void_p(Q.ctypes.data) if moments else None), "pt_radiance")
+        return (rgb, S, Q) if moments else rgb
 
     def last_kernel_ms(self):
         ms = C.c_float(0)
