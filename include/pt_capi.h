@@ -144,6 +144,11 @@ extern "C" {
  * the bit as it remembers PT_FLAG_AA and refuses a mixed pass.  Features and
  * the denoiser keep the centre ray from the eye.                           */
 #define PT_FLAG_LENS (1u << 9)
+/* pt_radiance / pt_radiance_device only (v7, additive): the launch takes the
+ * single kernel k_render_rays whatever the scene (see the routing paragraph
+ * under pt_radiance; what PT_FLAG_MEGAKERNEL is to a frame — that flag stays
+ * refused there).  Every other entry answers PT_EINVAL.                      */
+#define PT_FLAG_RAYS_SINGLE (1u << 10)
 
 /*
  * Flattened scene, as produced by scene_reader.Scene
@@ -370,13 +375,28 @@ int pt_scene_create_rays(const pt_scene_desc* desc, int32_t device, const double
  * [n_rays][3] float64 each, both or neither (NULL).  p: width, height and the
  * row fields are ignored; spp >= 1, bounces, seed, sample_begin, rr_depth and
  * lanes_per_pixel (0, or a power of two <= min(64, spp)) apply.  Flags:
- * PT_FLAG_RR, PT_FLAG_FORCE_F64 and PT_FLAG_OUT_F64; any other bit is
- * PT_EINVAL (PT_FLAG_AA, PT_FLAG_LENS, PT_FLAG_COUNT and the stats flags
- * among them), and so are a NULL ray or output array with n_rays > 0, n_rays
- * < 0 or >= 2^30, and a launch of 2^32 work-items or more.  n_rays = 0
- * succeeds and writes nothing.  One launch of the single kernel
- * k_render_rays, asynchronous on `stream`; pt_last_kernel_ms and
- * pt_last_launch_info report it.  The device form does not read `reserved`.
+ * PT_FLAG_RR, PT_FLAG_FORCE_F64, PT_FLAG_OUT_F64 and PT_FLAG_RAYS_SINGLE; any
+ * other bit is PT_EINVAL (PT_FLAG_AA, PT_FLAG_LENS, PT_FLAG_COUNT,
+ * PT_FLAG_MEGAKERNEL and the stats flags among them), and so are a NULL ray
+ * or output array with n_rays > 0, n_rays < 0 or >= 2^30, and a launch of
+ * 2^32 work-items or more.  n_rays = 0 succeeds, writes nothing and leaves
+ * the handle's last-launch record as it was.
+ * ROUTING, by a frame's rule: on a scene with a BVH the launch goes through
+ * the wavefront kernels (the ray forms of the shade, primary and final
+ * kernels, pt_shade_rays.hip; the frames' walk and sort kernels): one primary
+ * query per record, its hit cached, ceil(spp / lanes) x bounces + 2 shade
+ * steps.  The single kernel k_render_rays takes the launch on a scene
+ * without a BVH, with PT_FLAG_RAYS_SINGLE or PT_FLAG_FORCE_F64, on a tree
+ * deeper than the walk stack, and at 2^29 path slots (n_rays x lanes) or
+ * more.  The lanes per record come from one rule on both paths, and the two
+ * paths agree bit for bit in the mean, S and Q.  A record whose origin lies
+ * outside the frame has its primary query decided in f64 on either path.  The
+ * wavefront buffers are the handle's, shared with its frames and grown on
+ * demand: about 440 B per path slot (+ 48 B with out_S / out_Q) and 48 B per
+ * record; a failed allocation is PT_ENOMEM (a batch is not chunked).
+ * Asynchronous on `stream`; pt_last_kernel_ms covers the whole launch and
+ * pt_last_launch_info tells the path.  The device form does not read
+ * `reserved`.
  * Neither form checks o or d: a record whose d is zero or whose o or d is not
  * finite has a NaN direction or origin, every test against it fails as the
  * reference's comparisons do, and the record's value is unspecified (0, as an

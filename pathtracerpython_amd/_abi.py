@@ -21,6 +21,7 @@ PT_FLAG_KERNEL_TIMES = 1 << 6
 # bit 7: reserved (v4's PT_FLAG_TREE_WALK, retired in v5)
 PT_FLAG_AA = 1 << 8   # antialiasing: a jittered primary ray per sample
 PT_FLAG_LENS = 1 << 9   # thin lens: a lens point per sample (a scene created with a lens)
+PT_FLAG_RAYS_SINGLE = 1 << 10   # pt_radiance only: the single kernel k_render_rays whatever the scene
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)

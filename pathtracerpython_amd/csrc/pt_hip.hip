@@ -1253,17 +1253,29 @@ struct WfList {
     uint32_t* n;
     int32_t max_k;   // the most samples the pass adds to a pixel
 };
+// The ray form (Y, pt_radiance_device): the same loop over the slots of the
+// batch's records — a centre-ray launch with the record in the place of the
+// pixel — through the kernels of pt_shade_rays.hip for the shade, primary and
+// final steps; with S and Q the slots' moment home as in the list form.
+// Bytes in s->wf: ~440 per slot (WfPath 256, WfShadowQ 96, WfClosestQ 48, the
+// lists, keys and sorted list 34), + 48 with S and Q, and 48 per record.
+struct WfRayBatch {
+    RaysK R;
+    const RayK* rays;
+    double *S, *Q;   // both or neither
+};
 static int render_wavefront(pt_scene* s, const RenderK& R, const WfList* L, dim3 grid, void* out_dev,
-                            hipStream_t st, uint32_t flags, pt_stats* stats) {
+                            hipStream_t st, uint32_t flags, pt_stats* stats, const WfRayBatch* Y = nullptr) {
     const size_t slots = (size_t)grid.x * 256;
-    // primary queries (one per pixel / list entry), slots per query, samples per slot
-    const uint32_t n_prim = L ? L->R.n_list : R.npix;
-    const uint32_t split_log2 = L ? L->R.split_log2 : R.split_log2;
+    // primary queries (one per pixel / list entry / record), slots per query, samples per slot
+    const uint32_t n_prim = Y ? Y->R.n_rays : L ? L->R.n_list : R.npix;
+    const uint32_t split_log2 = Y ? Y->R.split_log2 : L ? L->R.split_log2 : R.split_log2;
     const int32_t split = (int32_t)(1u << split_log2);
-    const int32_t per_slot = ((L ? L->max_k : R.spp) + split - 1) / split;
+    const int32_t per_slot = ((Y ? Y->R.spp : L ? L->max_k : R.spp) + split - 1) / split;
     const bool aa = (flags & PT_FLAG_AA) != 0, lens = (flags & PT_FLAG_LENS) != 0;
     const bool own = aa || lens;   // a primary query per sample, in the slots' own records
-    const int32_t steps = per_slot * ((L ? L->R.bounces : R.bounces) + (own ? 1 : 0)) + 2;
+    const int32_t steps = per_slot * ((Y ? Y->R.bounces : L ? L->R.bounces : R.bounces) + (own ? 1 : 0)) + 2;
+    const bool moments = L || (Y && Y->S);   // the slots' moment home [6][slots]
     const unsigned sh_blocks =
         std::max(1u, std::min<unsigned>(grid.x, (unsigned)PT_WF_SHADOW_BLOCKS_PER_CU * (unsigned)s->n_cu));
     const unsigned cl_blocks =
@@ -1282,7 +1294,7 @@ static int render_wavefront(pt_scene* s, const RenderK& R, const WfList* L, dim3
         int32_t* lists_o;            // the sorted shadow list [3 slots]
         uint32_t *bin_hist, *bin_rowsum, *bin_base;   // the sort's count matrix (its rows' prefix sums in
                                                       // place), the row totals and their scan
-        double* home;                // the list form's moment home [6][slots]
+        double* home;                // the moment home [6][slots] (the list form; rays with S, Q)
     } B;
     auto carve = [&](char* base) -> size_t {   // returns the bytes carved
         Bump m{base};
@@ -1301,7 +1313,7 @@ static int render_wavefront(pt_scene* s, const RenderK& R, const WfList* L, dim3
         B.bin_hist = m.take<uint32_t>((size_t)kBins * kBinBlocks);
         B.bin_rowsum = m.take<uint32_t>(kBins);
         B.bin_base = m.take<uint32_t>(kBins);
-        B.home = m.take<double>(L ? 6 * slots : 0);
+        B.home = m.take<double>(moments ? 6 * slots : 0);
         return m.at;
     };
     const size_t need = carve(nullptr) + 256;
@@ -1356,7 +1368,12 @@ static int render_wavefront(pt_scene* s, const RenderK& R, const WfList* L, dim3
         HIPCHK(hipMemsetAsync(B.counters, 0, 4 * sizeof(int32_t), st));
         HIPCHK(mark(step, 0, 0, st));
         const dim3 sgrid((unsigned)((slots + kShadeBlock - 1) / kShadeBlock)), pgrid((n_prim + 255) / 256);
-        if (lens) {   // (a lens point per sample; validate: never with the stats flags)
+        if (Y) {   // (a record per entry; pt_radiance_device: no AA, lens or stats flags)
+            pt_wf_shade_rays(sgrid, st, s->dev, Y->R, step, Y->rays, B.W, B.SQ, B.CQ, (const WfClosestQ*)B.CQP,
+                             B.lists, B.counters, (uint32_t)slots, B.keys, moments ? B.home : nullptr);
+            if (step == 0)
+                pt_wf_primary_rays(pgrid, st, s->dev, Y->R, Y->rays, B.W, B.CQP, closest_list, B.counters + 2);
+        } else if (lens) {   // (a lens point per sample; validate: never with the stats flags)
             if (L)
                 pt_wf_shade_list_lens(aa, sgrid, st, s->dev, L->R, step, L->list, (const uint32_t*)L->n, B.W, B.SQ,
                                       B.CQ, B.lists, B.counters, (uint32_t)slots, B.keys, B.home);
@@ -1421,7 +1438,10 @@ static int render_wavefront(pt_scene* s, const RenderK& R, const WfList* L, dim3
             if (side) HIPCHK(hipStreamWaitEvent(st, s->wf_ev_walk, 0));
         }
     }
-    if (L)
+    if (Y)
+        pt_wf_final_rays(grid, st, Y->R, (const WfPath*)B.W, moments ? (const double*)B.home : nullptr,
+                         (uint32_t)slots, out_dev, Y->S, Y->Q);
+    else if (L)
         hipLaunchKernelGGL(k_wf_final_list, grid, dim3(256), 0, st, L->R, L->list, (const double*)B.home,
                            (uint32_t)slots, L->S, L->Q, L->n);
     else
@@ -1577,7 +1597,11 @@ int pt_render_device(pt_scene* s, const pt_render_params* p, void* out_dev, void
     return PT_OK;
 }
 
-// pt_radiance (include/pt_capi.h): one launch of k_render_rays (pt_rays.hip)
+// pt_radiance (include/pt_capi.h): on a BVH scene the wavefront kernels'
+// ray form (render_wavefront with a WfRayBatch), by the frames' rule
+// (wf_route); else, or with PT_FLAG_RAYS_SINGLE, one launch of k_render_rays
+// (pt_rays.hip).  The lanes per record are chosen before the route, so both
+// paths deal a record's samples alike and agree bit for bit.
 static_assert(sizeof(pt_ray) == sizeof(RayK) && offsetof(pt_ray, d) == offsetof(RayK, d) &&
                   offsetof(pt_ray, key) == offsetof(RayK, key),
               "pt_ray is the kernels' RayK");
@@ -1585,9 +1609,10 @@ int pt_radiance_device(pt_scene* s, const pt_ray* rays_dev, int64_t n_rays, cons
                        void* out_rgb_dev, double* out_S_dev, double* out_Q_dev, void* stream) {
     if (!p) return fail(PT_EINVAL, "null params");
     if (!s) return fail(PT_EINVAL, "null scene");
-    if (p->flags & ~(uint32_t)(PT_FLAG_RR | PT_FLAG_FORCE_F64 | PT_FLAG_OUT_F64))
-        return fail(PT_EINVAL, "unsupported flag bits: pt_radiance takes PT_FLAG_RR, PT_FLAG_FORCE_F64 and "
-                               "PT_FLAG_OUT_F64 only (the ray kernel does not count, jitter or draw a lens point)");
+    if (p->flags & ~(uint32_t)(PT_FLAG_RR | PT_FLAG_FORCE_F64 | PT_FLAG_OUT_F64 | PT_FLAG_RAYS_SINGLE))
+        return fail(PT_EINVAL, "unsupported flag bits: pt_radiance takes PT_FLAG_RR, PT_FLAG_FORCE_F64, "
+                               "PT_FLAG_OUT_F64 and PT_FLAG_RAYS_SINGLE only (the ray kernels do not count, jitter "
+                               "or draw a lens point)");
     if (p->spp <= 0) return fail(PT_EINVAL, "spp must be > 0");
     if (p->bounces < 0) return fail(PT_EINVAL, "bounces must be >= 0");
     if (p->sample_begin < 0) return fail(PT_EINVAL, "sample_begin must be >= 0");
@@ -1623,6 +1648,11 @@ int pt_radiance_device(pt_scene* s, const pt_ray* rays_dev, int64_t n_rays, cons
     if (threads >= ((uint64_t)1 << 32))
         return fail(PT_EINVAL, "launch needs 2^32 or more work-items (32-bit lane index)");
     if (s->timed) HIPCHK(hipStreamWaitEvent(st, s->ev1, 0));
+    const dim3 wgrid((unsigned)((threads + 255) / 256));   // (the wavefront's slots)
+    if (!(p->flags & PT_FLAG_RAYS_SINGLE) && wf_route(s, p->flags, (uint64_t)wgrid.x * 256u)) {
+        const WfRayBatch Y{R, (const RayK*)rays_dev, out_S_dev, out_Q_dev};
+        return render_wavefront(s, RenderK{}, nullptr, wgrid, out_rgb_dev, st, p->flags, nullptr, &Y);
+    }
     const dim3 grid((unsigned)((threads + kRenderBlock - 1) / kRenderBlock));
     HIPCHK(hipEventRecord(s->ev0, st));
     s->last = pt_launch_info{PT_PATH_SINGLE, 1, (int32_t)R.split, p->flags};

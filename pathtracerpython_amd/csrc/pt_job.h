@@ -1,5 +1,5 @@
-// pt_job.h — the launch records (RenderK, ListK) and the mapping work-item ->
-// job of a launch (slot_job, list_job), without the HIP runtime: the kernels
+// pt_job.h — the launch records (RenderK, ListK, RaysK) and the mapping work-item ->
+// job of a launch (slot_job, list_job, rays_job), without the HIP runtime: the kernels
 // (pt_render.h) and the host checks (tests/hostcheck) compile the same text.
 #pragma once
 #include "pt_path.h"
@@ -122,6 +122,50 @@ PT_HD ListJob list_job(const SceneK& S, const ListK& R, const uint32_t* __restri
         j.J.pixel = (uint32_t)ix * (uint32_t)R.H + (uint32_t)iy;
         j.J.sample0 = (int32_t)(n0 + c);
         j.J.n_samples = c < j.k ? (int32_t)((j.k - c + R.split - 1u) >> R.split_log2) : 0;
+    }
+    return j;
+}
+
+// pt_radiance's launch (include/pt_capi.h): n_rays records, `split` adjacent
+// work-items each
+struct RaysK {
+    int32_t spp, bounces;
+    uint64_t seed;
+    int32_t rr_depth;   // -1: off
+    int32_t sample_begin;
+    uint32_t split, split_log2;
+    uint32_t n_rays;
+    int32_t out_f64;
+    double frame_x;   // rays_in_frame's extent (HostScene::frame_x)
+};
+// Work-item -> (record, sample slice) of a ray launch through the wavefront
+// kernels, k_render_rays' mapping (pt_rays.hip): `split` adjacent slots share
+// record `entry` and stride its spp samples from sample_begin on; the Philox
+// pixel word is the record's key.  There is no pixel: the primary ray, and the
+// eye wherever a sample reads it, are the record's.  A record past the batch
+// is never dereferenced (ray stays null).
+struct RayJob {
+    LaneJob J;
+    const RayK* ray;
+    bool valid;
+};
+PT_HD RayJob rays_job(const RaysK& R, const RayK* __restrict__ rays, uint32_t tid) {
+    RayJob j;
+    const uint32_t entry = tid >> R.split_log2;
+    const int32_t c = (int32_t)(tid & (R.split - 1u)), sp = (int32_t)R.split;
+    j.valid = entry < R.n_rays;
+    j.ray = nullptr;
+    j.J = LaneJob{};
+    // (the launch's constants outside the branch, as list_job keeps them)
+    j.J.seed = R.seed;
+    j.J.sample_stride = sp;
+    j.J.bounces = R.bounces;
+    j.J.rr_depth = R.rr_depth;
+    if (j.valid) {
+        j.ray = rays + entry;
+        j.J.pixel = j.ray->key;
+        j.J.sample0 = R.sample_begin + c;
+        j.J.n_samples = (c < R.spp) ? (R.spp - c + sp - 1) / sp : 0;
     }
     return j;
 }

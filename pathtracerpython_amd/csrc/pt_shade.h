@@ -72,6 +72,16 @@ __global__ __launch_bounds__(kShadeBlock) void k_wf_shade_list_aa(
 void pt_wf_shade_lens(bool aa, dim3 grid, hipStream_t st, const SceneK& S, const RenderK& R, int32_t step,
                       WfPath* W, WfShadowQ* SQ, WfClosestQ* CQ, int32_t* lists, int32_t* counters, uint32_t slots,
                       uint16_t* keys);
+// The ray forms (pt_radiance on a BVH scene; pt_shade_rays.hip): the launchers
+// of k_wf_shade_rays<MOM>, k_wf_primary_rays and k_wf_final_rays<MOM>; home
+// (the moment home [6][slots]) non-null: MOM, the moments S, Q as well.
+void pt_wf_shade_rays(dim3 grid, hipStream_t st, const SceneK& S, const RaysK& R, int32_t step, const RayK* rays,
+                      WfPath* W, WfShadowQ* SQ, WfClosestQ* CQ, const WfClosestQ* CQP, int32_t* lists,
+                      int32_t* counters, uint32_t slots, uint16_t* keys, double* home);
+void pt_wf_primary_rays(dim3 grid, hipStream_t st, const SceneK& S, const RaysK& R, const RayK* rays, WfPath* W,
+                        WfClosestQ* CQP, int32_t* qlist, int32_t* counters);
+void pt_wf_final_rays(dim3 grid, hipStream_t st, const RaysK& R, const WfPath* W, const double* home,
+                      uint32_t slots, void* out, double* outS, double* outQ);
 void pt_wf_shade_list_lens(bool aa, dim3 grid, hipStream_t st, const SceneK& S, const ListK& R, int32_t step,
                            const uint32_t* list, const uint32_t* accN, WfPath* W, WfShadowQ* SQ, WfClosestQ* CQ,
                            int32_t* lists, int32_t* counters, uint32_t slots, uint16_t* keys, double* home);

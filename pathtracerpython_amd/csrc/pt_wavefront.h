@@ -313,12 +313,21 @@ template <bool KEY = false>
 PT_HD uint32_t wf_begin_bounce(const SceneK& S, const LaneJob& J, WfPath* W, WfShadowQ* shq,
                                WfClosestQ* cq) {
     constexpr bool LENS = false;
+    constexpr const double* eye_o = nullptr;
 #include "pt_wf_bounce.h"
 }
 template <bool KEY = false>
 PT_HD uint32_t wf_begin_bounce_lens(const SceneK& S, const LaneJob& J, WfPath* W, WfShadowQ* shq,
                                     WfClosestQ* cq) {
     constexpr bool LENS = true;
+    constexpr const double* eye_o = nullptr;
+#include "pt_wf_bounce.h"
+}
+// caller-supplied rays: the eye is the record's origin (bounce<2>, RaySched::eye_o)
+template <bool KEY = false>
+PT_HD uint32_t wf_begin_bounce_rays(const SceneK& S, const LaneJob& J, const double* eye_o, WfPath* W,
+                                    WfShadowQ* shq, WfClosestQ* cq) {
+    constexpr int LENS = 2;
 #include "pt_wf_bounce.h"
 }
 
@@ -346,10 +355,18 @@ struct WfMoments : MomentMem { static constexpr bool kMoments = true; };
 // LENS (the thin lens, wf_lens_start): AA's per-sample form whether or not the
 // launch is antialiased (AA is then the jitter alone), the primary query's
 // origin being the sample's lens point, which kSpP still holds.
+// RAYS (caller-supplied rays, wf_rays_primary_step): the centre-ray form — a
+// primary query per record, its hit cached in tri0 / kSpP0 — with the record
+// `ray` in the place of (the job's d0, kSpD0, the scene's eye), as RaySched
+// has it: the home keeps no direction, a sample's restart reads ray->d.  A
+// record whose primary query was decided in f64 (pq->pad = kWfPrimF64) has
+// issued no walk: its hit is in its first slot W0 (tri0, kSpP0).
 enum : int { kWfNextNone = 0, kWfNextBounce = 1, kWfNextPrimary = 2 };
-template <class Home, bool AA = false, bool LENS = false>
+enum : int32_t { kWfPrimF32 = 0, kWfPrimF64 = 1 };   // WfClosestQ::pad of a record's primary query
+template <class Home, bool AA = false, bool LENS = false, bool RAYS = false>
 PT_HD int wf_finish(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, const WfShadowQ* shq,
-                    const WfClosestQ* cq, const WfClosestQ* pq, Home home) {
+                    const WfClosestQ* cq, const WfClosestQ* pq, Home home, const RayK* ray = nullptr,
+                    const WfPath* W0 = nullptr) {
     const Spill sp{W->sp, 1};
     if constexpr (AA || LENS) {
         if (W->state() == kWfPrimary) {   // aa_primary: closest(eye, d0 of this sample)
@@ -385,8 +402,19 @@ PT_HD int wf_finish(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, const W
     } else
     if (W->state() == kWfPrimary) {   // k_render: closest(eye, d0) then render_lane's prologue
         D3 P0 = d3(0, 0, 0);
-        const int tri0 = closest_finish<false, false, true>(S, wf_get_acc(*pq), ld3(S.eye), unit(d0),
-                                                            &P0, nullptr);
+        int tri0;
+        if constexpr (RAYS) {
+            d0 = ld3(ray->d);
+            if (pq->pad == kWfPrimF64) {   // decided in f64 by the primary step
+                tri0 = W0->tri0;
+                P0 = ld3(W0->sp + kSpP0);
+            } else {
+                tri0 = closest_finish<false, false, true>(S, wf_get_acc(*pq), ld3(ray->o), unit(d0), &P0,
+                                                          nullptr);
+            }
+        } else {
+            tri0 = closest_finish<false, false, true>(S, wf_get_acc(*pq), ld3(S.eye), unit(d0), &P0, nullptr);
+        }
         if (tri0 < 0 || tri0 >= S.n_obj_tri) {   // primary ray escapes or hits the light
             const D3 v = tri0 < 0 ? d3(0, 0, 0) : ld3(S.kd + kKdLightRgb);
             D3 acc = d3(0, 0, 0);
@@ -401,12 +429,18 @@ PT_HD int wf_finish(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, const W
         }
         W->si = 0;
         W->set(kWfBegin, false, 0);   // (b = 0; begin_bounce sets the state)
+        // (a record decided in f64: its first slot holds the hit already, and
+        // the record's other slots read it there in this very step)
+        bool own = true;
+        if constexpr (RAYS) own = W != W0 || pq->pad != kWfPrimF64;
         W->tri = tri0;
-        W->tri0 = tri0;
+        if (own) W->tri0 = tri0;
         W->k = 1.0;
-        sp.put(kSpD0, d0.x);
-        sp.put(kSpD0 + 1, d0.y);
-        sp.put3(kSpP0, P0);
+        if constexpr (!RAYS) {   // (rays: the direction comes back from the record)
+            sp.put(kSpD0, d0.x);
+            sp.put(kSpD0 + 1, d0.y);
+        }
+        if (own) sp.put3(kSpP0, P0);
         sp.put3(kSpP, P0);
         sp.put3(kSpNd, d0);   // incoming direction of bounce 0 (main.py:191)
         return kWfNextBounce;
@@ -461,7 +495,8 @@ PT_HD int wf_finish(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, const W
             tri = W->tri0;
             k = 1.0;
             sp.put3(kSpP, sp.get3(kSpP0));
-            sp.put3(kSpNd, d3(sp.get(kSpD0), sp.get(kSpD0 + 1), 0.0 - S.eye[2]));
+            if constexpr (RAYS) sp.put3(kSpNd, ld3(ray->d));   // RaySched::advance
+            else sp.put3(kSpNd, d3(sp.get(kSpD0), sp.get(kSpD0 + 1), 0.0 - S.eye[2]));
         }
     }
     W->acc[0] = acc.x; W->acc[1] = acc.y; W->acc[2] = acc.z;
@@ -504,20 +539,41 @@ PT_HD uint32_t wf_shade_lens(const SceneK& S, const LaneJob& J, const AaPixel& X
     return next == kWfNextPrimary ? wf_lens_start<AA>(S, J, X, W, cq) : 0u;
 }
 
+// The ray shade step: wf_shade with the record (W0: the record's first slot).
+template <bool KEY = false, class Home = WfSum>
+PT_HD uint32_t wf_shade_rays(const SceneK& S, const LaneJob& J, const RayK* ray, WfPath* W, const WfPath* W0,
+                             WfShadowQ* shq, WfClosestQ* cq, const WfClosestQ* pq, Home home = Home{}) {
+    return wf_finish<Home, false, false, true>(S, J, d3(0, 0, 0), W, shq, cq, pq, home, ray, W0) == kWfNextBounce
+               ? wf_begin_bounce_rays<KEY>(S, J, ray->o, W, shq, cq)
+               : 0u;
+}
+
 // Where the slots of a launch get their jobs (pt_job.h): the pixels of a
-// frame, `split` slots each, or the entries of an accumulator pass's active
-// list.  n_prim(): the launch's primary queries, one per pixel / entry.
+// frame, `split` slots each, the entries of an accumulator pass's active
+// list, or the records of a ray batch (kRays: no pixel, ix or iy; the job
+// carries the record).  n_prim(): the launch's primary queries, one per pixel
+// / entry / record.
 struct WfFrame {
+    static constexpr bool kRays = false;
     const RenderK& R;
     PT_HD SlotJob job(const SceneK& S, uint32_t tid) const { return slot_job(S, R, tid); }
     PT_HD uint32_t n_prim() const { return R.npix; }
 };
 struct WfActive {
+    static constexpr bool kRays = false;
     const ListK& R;
     const uint32_t* list;
     const uint32_t* accN;
     PT_HD ListJob job(const SceneK& S, uint32_t tid) const { return list_job(S, R, list, accN, tid); }
     PT_HD uint32_t n_prim() const { return R.n_list; }
+};
+
+struct WfRays {
+    static constexpr bool kRays = true;
+    const RaysK& R;
+    const RayK* rays;
+    PT_HD RayJob job(const SceneK&, uint32_t tid) const { return rays_job(R, rays, tid); }
+    PT_HD uint32_t n_prim() const { return R.n_rays; }
 };
 
 // The primary query of pixel / entry `entry` (centre rays: its `split` slots
@@ -529,6 +585,55 @@ PT_HD uint32_t wf_primary_step(const SceneK& S, const Src& src, uint32_t entry, 
     const uint32_t slot = entry << src.R.split_log2;
     const auto j = src.job(S, slot);
     return j.valid ? wf_start(S, j.J, j.d0, &W[slot], &CQP[entry]) : 0u;
+}
+
+// The primary query of record `entry` of a ray batch (its `split` slots share
+// it): wf_start's body from the record's origin, in lens_closest's unit form
+// (per-lane origin_q over unit_eye) — what rays_primary runs for an origin
+// inside the f32 filter's frame; the home rows kSpP / kSpNd of the entry's
+// first slot get o and d.  An origin outside the frame (a NaN included,
+// rays_in_frame): the query is decided here in f64, once per record, as
+// closest<true, false, true> decides it in k_render_rays; no walk is issued,
+// tri0 and P0 stay in the first slot's record and CQP[entry].pad says so.
+// Returns the queries wanted.
+PT_HD uint32_t wf_rays_primary_step(const SceneK& S, const WfRays& src, uint32_t entry, WfPath* W,
+                                    WfClosestQ* CQP) {
+    if (entry >= src.n_prim()) return 0u;
+    const uint32_t slot = entry << src.R.split_log2;
+    const RayJob j = src.job(S, slot);
+    if (j.J.n_samples <= 0 || j.J.bounces <= 0) return 0u;   // (wf_start: main.py:192 never runs)
+    WfPath* const W0 = &W[slot];
+    WfClosestQ* const cq = &CQP[entry];
+    const Spill sp{W0->sp, 1};
+    const D3 o = ld3(j.ray->o), d0 = ld3(j.ray->d);
+    if (!rays_in_frame(S, src.R.frame_x, o)) {
+        D3 P0 = d3(0, 0, 0);
+        W0->tri0 = closest<true, false, true>(S, o, d0, -1, sp, &P0, nullptr, true);
+        sp.put3(kSpP0, P0);
+        cq->pad = kWfPrimF64;
+        return 0u;
+    }
+    const D3 dn = unit(d0);
+    sp.put3(kSpP, o);
+    sp.put3(kSpNd, d0);
+    const F3 o32 = to_f3(o - ld3(S.kd + kKdCenter));
+    const F3 d32 = to_f3(dn);
+    ClosestAcc acc = closest_init();
+    for (int u = 0; u < S.n_unit; ++u) {   // the unit_eye records, from the record's origin
+        const UnitF U = S.unit_eye[u];
+#if PT_WF_AA_PRIMARY_M
+        const OriginU O = origin_q(U, o32);
+        if (closest_unit_m(U, O, U.grp == -1, d32, &acc))   // rare
+            fused_fallback<false, false, true, 2>(S, U, closest_bits_m(U, O, U.grp == -1, d32), nullptr,
+                                                  &acc, sp, nullptr, nullptr);
+#else
+        closest_unit<false>(S, U, origin_u(U, o32), d32, U.grp == -1, sp, kSpP, kSpNd, &acc,
+                            nullptr);
+#endif
+    }
+    wf_put_closest(cq, o32, -1, d32, acc);
+    cq->pad = kWfPrimF32;
+    return kWfWantClosest;
 }
 
 // One shade step of slot tid < slots (the four shade kernels' body, and the
@@ -576,6 +681,9 @@ PT_HD uint32_t wf_slot_step(const SceneK& S, const Src& src, int32_t step, uint3
             j.J.seed = src.R.seed;   // (as in step 0; the slot is valid)
             want = wf_shade_aa<true>(S, j.J, AaPixel{src.R.W, src.R.H, j.ix, j.iy}, &W[tid], &SQ[tid], &CQ[tid],
                                      home);
+        } else if constexpr (Src::kRays) {
+            want = wf_shade_rays<true>(S, j.J, j.ray, &W[tid], &W[entry << src.R.split_log2], &SQ[tid], &CQ[tid],
+                                       &CQP[entry], home);
         } else {
             want = wf_shade<true>(S, j.J, j.d0, &W[tid], &SQ[tid], &CQ[tid], &CQP[entry], home);
         }

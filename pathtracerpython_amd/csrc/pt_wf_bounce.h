@@ -1,11 +1,13 @@
 // pt_wf_bounce.h — the body of wf_begin_bounce (pt_wavefront.h), included
-// once per camera: LENS (a constexpr bool of the including function) selects
-// the specular term's eye — the scene's, or the sample's lens point in the
-// record's rows kSpLens (wf_lens_start).  A text fragment rather than a
+// once per camera: LENS (a constexpr of the including function, bounce's
+// mode) selects the specular term's eye — 0 the scene's, 1 the sample's lens
+// point in the record's rows kSpLens (wf_lens_start), 2 the origin of the
+// slot's ray record, the three doubles at eye_o (wf_begin_bounce_rays; null
+// in the other two, where bounce never reads it).  A text fragment rather than a
 // template parameter: the body's constants are named after the function they
 // stand in, and wf_begin_bounce<KEY> keeps its name and with it the text the
 // kernels without a lens compile to.  No include guard.
-// In scope: S, J, W, shq, cq; KEY, LENS.
+// In scope: S, J, W, shq, cq; KEY, LENS, eye_o.
     const Spill sp{W->sp, 1};
     const D3 P = sp.get3(kSpP);
     const int tri = W->tri, b = W->b();
@@ -41,7 +43,7 @@
     }
 #endif
     double kf;
-    const D3 nd = bounce<LENS>(S, R, m, P, sp.get3(kSpNd), u_of(w[12]), u_of(w[13]), u_of(w[14]), &kf, &sp);
+    const D3 nd = bounce<LENS>(S, R, m, P, sp.get3(kSpNd), u_of(w[12]), u_of(w[13]), u_of(w[14]), &kf, &sp, eye_o);
     const double kn = W->k * kf;
     bool trace = (b + 1 < J.bounces);
     double kk = kn;

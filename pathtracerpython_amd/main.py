@@ -25,7 +25,9 @@ with --aa, --noise, --denoise, --checkpoint, --chunk-spp and --local-devices,
 not with --devices N > 1; always the single kernel), --look-at EX EY EZ TX
 TY TZ [--up UX UY UZ] [--fov DEG] (a pinhole at E looking at T in place of the
 scene's camera: cameras.look_at_rays through Renderer.render_rays,
-pt_radiance; with -r, -b, --rr, --seed, --size, --out and --save-raw only).  The
+pt_radiance, which takes the wavefront kernels on a scene with a BVH and the
+single ray kernel otherwise; with -r, -b, --rr, --seed, --size, --out and
+--save-raw only).  The
 reference's interactive 3-D viewer flags (--show-scene, --show-normals,
 --show-screen, --show-inter -> plot.py) are accepted and ignored with a
 notice: the pyqtgraph viewer is out of scope.
@@ -60,7 +62,8 @@ def setup(argv=None):
     parser.add_argument('--look-at', type=float, nargs=6, default=None,
                         metavar=('EX', 'EY', 'EZ', 'TX', 'TY', 'TZ'),
                         help='render through a pinhole at E looking at T instead of the scene\'s '
-                             'camera (cameras.look_at_rays through Renderer.render_rays); with '
+                             'camera (cameras.look_at_rays through Renderer.render_rays: the '
+                             'wavefront kernels on a scene with a BVH, else the single ray kernel); with '
                              '-r, -b, --rr, --seed, --size, --out and --save-raw only')
     parser.add_argument('--up', type=float, nargs=3, default=None, metavar=('UX', 'UY', 'UZ'),
                         help='with --look-at: the direction towards the top of the image (default 0 1 0)')
@@ -156,7 +159,8 @@ def check_args(args):
     if args.look_at is not None:
         args.up = [0.0, 1.0, 0.0] if args.up is None else args.up
         args.fov = 40.0 if args.fov is None else args.fov
-        # (the ray kernel is one launch of the single kernel on one device)
+        # (a ray batch is one launch on one device: the wavefront kernels on a
+        # scene with a BVH, else the single ray kernel; no jitter, lens or moments)
         for on, name in ((args.aa, '--aa'), (args.aperture is not None, '--aperture'),
                          (args.noise is not None, '--noise'), (args.denoise, '--denoise'),
                          (args.devices > 1, '--devices > 1'), (args.local_devices is not None, '--local-devices'),
@@ -320,8 +324,9 @@ def render_look_at(scene, args, W, H):
         raise SystemExit(f'--look-at: {e}')
     with Renderer(scene, ray_box=(eye, eye)) as r:
         rgb = r.render_rays(o, d, keys, spp=args.n_rays, bounces=args.n_bounces, seed=args.seed, rr=args.rr)
+        from ._abi import PATH_NAMES
         print(f'render: {W}x{H} through --look-at, {args.n_rays} spp, {args.n_bounces} bounces, '
-              f'kernel {r.last_kernel_ms():.3f} ms')
+              f'{PATH_NAMES[r.last_launch()["path"]]} path, kernel {r.last_kernel_ms():.3f} ms')
     return np.ascontiguousarray(rays_to_image(rgb, W, H))
 
 

@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _native
 from ._abi import (PT_FLAG_AA, PT_FLAG_COUNT, PT_FLAG_LENS, PT_FLAG_FORCE_F64, PT_FLAG_KERNEL_TIMES, PT_FLAG_MEGAKERNEL,
-                   PT_FLAG_OUT_F64, PT_FLAG_RR, PT_FLAG_WALK_COUNT, PtLaunchInfo, PtStats, band_rows, make_denoise,
+                   PT_FLAG_OUT_F64, PT_FLAG_RAYS_SINGLE, PT_FLAG_RR, PT_FLAG_WALK_COUNT, PtLaunchInfo, PtStats, band_rows, make_denoise,
                    make_lens, make_params, make_rays)
 from .pack import pack_scene
 
@@ -172,17 +172,24 @@ class Renderer:
                                megakernel=megakernel, denoise=denoise, aa=aa, lens=lens, **rule)
 
     def render_rays(self, origins, dirs, keys=None, spp=1, bounces=1, seed=None, rr=False, rr_depth=3,
-                    force_f64=False, out_f64=True, moments=False, sample_begin=0, lanes_per_pixel=0):
+                    force_f64=False, out_f64=True, moments=False, sample_begin=0, lanes_per_pixel=0,
+                    single_kernel=False):
         """Path-traced radiance of caller-supplied rays (pt_radiance): origins,
         dirs (n, 3) f64, keys (n,) u32 — the Philox pixel word of each ray's
         draws; None means 0..n-1.  Returns rgb (n, 3), the mean over spp
         samples, float64 (float32 with out_f64=False); with moments=True
         (rgb, S, Q), the per-channel sums of the sample colours and of their
-        squares.  The cameras module makes the rays of a few cameras."""
+        squares.  The cameras module makes the rays of a few cameras.
+        A scene with a BVH takes the launch through the wavefront kernels, as
+        its frames go; single_kernel=True (PT_FLAG_RAYS_SINGLE) asks for the
+        single ray kernel whatever the scene.  The two agree bit for bit, and
+        last_launch() tells which ran."""
         rec = make_rays(origins, dirs, keys)
         n = rec.shape[0]
         p = self.params(1, 1, spp, bounces, seed, rr, rr_depth, force_f64, out_f64=out_f64,
                         sample_begin=sample_begin, lanes_per_pixel=lanes_per_pixel, lens=False)
+        if single_kernel:
+            p.flags |= PT_FLAG_RAYS_SINGLE
         rgb = np.zeros((n, 3), dtype=np.float64 if out_f64 else np.float32)
         S = np.zeros((n, 3), dtype=np.float64) if moments else None
         Q = np.zeros((n, 3), dtype=np.float64) if moments else None
