@@ -573,6 +573,53 @@ int pt_accum_import_band_device(pt_accum* acc, const pt_accum_band* band,
  * invalidated.  A run continues from the written state as from its own. */
 int pt_accum_write(pt_accum* acc, const double* S, const double* Q, const uint32_t* n);
 
+/* Ray accumulators (v7, additive): adaptive sampling for caller-supplied rays.
+ * A pt_accum of width x height elements, n = width*height with 1 <= n < 2^30
+ * (PT_EINVAL otherwise), whose element e belongs to ray record e — not to a
+ * pixel of the scene's camera.  rays_dev: the n records in DEVICE memory; they
+ * are copied at create, so the caller's buffer may go away on return.  The
+ * copy runs on a stream of the accumulator's own and is not ordered after any
+ * stream of the caller's: the records must be complete in device memory (the
+ * work that wrote them synchronised) before the call.  The
+ * device form does not read `reserved`, as pt_radiance_device does not.  A
+ * flat batch uses height = 1; an image uses its own shape with the records in
+ * image orientation, e = (height-1-iy)*width + ix.
+ * THE RULE.  A pass adds the samples n[e] .. n[e]+k-1 of record e to each
+ * listed element, k as for a frame accumulator; each of them is THE RULE of
+ * pt_radiance with s the absolute sample index, formed sample by sample (a
+ * whole path per sample).  The value depends on (seed, key, s, o, d) only: not
+ * on the record's position, the list, the pass that takes the sample, or — at a
+ * fixed lanes per record — on how the samples are dealt to lanes.  The rays of
+ * a frame with the frame's keys, in image orientation, therefore give a frame
+ * accumulator's S, Q and n bit for bit at the same lanes per record.
+ * On a ray accumulator pt_accum_reset, _select, _read, _write,
+ * _resolve_device, _set_band, _tile_bytes, _export_band_device,
+ * _import_band_device and _destroy mean what they mean on a frame accumulator
+ * and run the same code (a "row" is a row of the width x height shape); in
+ * pt_accum_band, lanes_per_pixel is lanes per record, with the same
+ *     split = min(L, largest power of two <= min(kmin, 64)).
+ * pt_accum_render(_stats): p->width and p->height are the accumulator's,
+ * spp = a->max_spp, and the row fields, sample_begin, out_row_stride and
+ * lanes_per_pixel stay at their whole-frame values.  Flags: PT_FLAG_RR,
+ * PT_FLAG_FORCE_F64 and PT_FLAG_RAYS_SINGLE (accepted, no effect yet: reserved
+ * for the wavefront form); any other bit — PT_FLAG_AA, PT_FLAG_LENS,
+ * PT_FLAG_MEGAKERNEL, PT_FLAG_COUNT, PT_FLAG_WALK_COUNT, PT_FLAG_KERNEL_TIMES
+ * and PT_FLAG_OUT_F64 among them — is PT_EINVAL with a message naming it, and
+ * so is a launch of 2^32 work-items or more.  The pass is one launch of the
+ * list kernel over ray records (k_render_rays_list, pt_rays_list.hip) on every
+ * scene, a scene with a BVH included; pt_last_launch_info reports
+ * PT_PATH_SINGLE, the lanes per record and the flags; stats stay 0.  A record
+ * whose origin lies outside the frame the scene was prepared for
+ * (pt_scene_create_rays) has its primary query decided in f64.
+ * pt_accum_features traces each record's ray, o and d used as a pass uses them
+ * (outside the frame: in f64); tri, obj, N and P keep their layout, so
+ * pt_accum_read_features and pt_accum_denoise_device work unchanged on the
+ * width x height shape (whole band only): the filter reads S, Q, n and the
+ * features, nothing of the camera.  Neighbours in the filter are neighbours in
+ * the shape, which is meaningful for an image of records. */
+int pt_accum_create_rays(pt_scene* scene, const pt_ray* rays_dev, int32_t width, int32_t height,
+                         pt_accum** out);
+
 /* Denoising an adaptive render on the device (additive; build extension — the
  * reference has no filter).  An edge-avoiding a-trous filter over the frame,
  * guided by the per-pixel variance of the mean (from an accumulator's S, Q, n)

@@ -73,6 +73,8 @@ def _bind(lib):
         "pt_accum_export_band_device": ([vp, vp, vp], C.c_int),
         "pt_accum_import_band_device": ([vp, C.POINTER(PtAccumBand), vp, vp], C.c_int),
         "pt_accum_write": ([vp, dp, dp, C.POINTER(C.c_uint32)], C.c_int),
+        # ray accumulators (v7, additive)
+        "pt_accum_create_rays": ([vp, vp, C.c_int32, C.c_int32, C.POINTER(vp)], C.c_int),
         # denoising (additive)
         "pt_denoise_device": ([C.c_int32, C.c_int32, C.POINTER(PtDenoiseParams), vp, vp, vp, vp, vp,
                                C.c_uint32, vp, vp, vp], C.c_int),
@@ -101,7 +103,8 @@ EXPORTS = ("pt_api_version", "pt_last_error", "pt_build_id", "pt_test_fault_inje
            "pt_denoise_device", "pt_denoise", "pt_denoise_times", "pt_accum_features", "pt_accum_read_features",
            "pt_accum_denoise_device", "pt_accum_set_band", "pt_accum_tile_bytes",
            "pt_accum_export_band_device", "pt_accum_import_band_device", "pt_accum_write",
-           "pt_last_launch_info", "pt_scene_create_rays", "pt_radiance_device", "pt_radiance")
+           "pt_last_launch_info", "pt_scene_create_rays", "pt_radiance_device", "pt_radiance",
+           "pt_accum_create_rays")
 
 
 def lib():

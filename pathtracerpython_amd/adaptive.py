@@ -25,7 +25,13 @@ N of them, one per device, run their own pass loops with no exchange until
 the end (render.MultiRenderer.render_adaptive; band tiles move the state:
 export_band / import_band); and a run can be cut between any two passes and
 continued from its moments (AccumCheckpoint, Accumulator.write).
+
+The same for rays the caller supplies (RayAccumulator, render_rays_adaptive;
+pt_accum_create_rays): element e of the accumulator belongs to ray record e,
+sample s of a record is pt_radiance's sample s, and everything above — the
+rule, the bands, the checkpoints, the denoiser — works on the records' shape.
 """
+import hashlib
 import ctypes as C
 import json
 import os
@@ -36,7 +42,7 @@ import numpy as np
 
 from . import _native
 from ._abi import (PT_FLAG_AA, PT_FLAG_FORCE_F64, PT_FLAG_LENS, PT_FLAG_MEGAKERNEL, PT_FLAG_OUT_F64, PT_FLAG_RR, PtAccumBand,
-                   PtStats, band_pixels, make_adapt, make_band, make_denoise, make_params)
+                   PtStats, band_pixels, make_adapt, make_band, make_denoise, make_params, make_rays)
 from .progressive import lens_of, scene_fingerprint
 
 
@@ -58,9 +64,9 @@ class AdaptiveResult:
         self.samples = int(sum(s for _, s in self.passes))
 
     def __repr__(self):
-        H, W = self.counts.shape
-        return (f"AdaptiveResult({W}x{H}, {len(self.passes)} passes, {self.samples} samples, "
-                f"{self.samples / max(1, W * H):.2f} spp mean)")
+        shape = "x".join(str(v) for v in self.counts.shape[::-1])   # (a flat ray batch: its length)
+        return (f"AdaptiveResult({shape}, {len(self.passes)} passes, {self.samples} samples, "
+                f"{self.samples / max(1, self.counts.size):.2f} spp mean)")
 
 
 def check_rule(tol, max_spp, min_spp=8, step_spp=8, floor=0.01):
@@ -107,10 +113,7 @@ class Accumulator:
         self._lib = renderer._lib
         self.renderer = renderer
         self.width, self.height = int(width), int(height)
-        h = C.c_void_p()
-        _native.check(self._lib.pt_accum_create(renderer._h, self.width, self.height, C.byref(h)),
-                      "pt_accum_create")
-        self._h = h
+        self._h = self._create(renderer)
         # the accumulator must go before its scene: Renderer.close() closes
         # the accumulators still open on it first
         if not hasattr(renderer, "_accums"):
@@ -119,6 +122,12 @@ class Accumulator:
         self.band = make_band(self.height)
         if band is not None:
             self.set_band(band)
+
+    def _create(self, renderer):
+        h = C.c_void_p()
+        _native.check(self._lib.pt_accum_create(renderer._h, self.width, self.height, C.byref(h)),
+                      "pt_accum_create")
+        return h
 
     def set_band(self, band):
         """Restrict the selects, and so the passes, to the rows of `band`
@@ -302,6 +311,47 @@ class Accumulator:
             pass
 
 
+def ray_records(o, d, keys=None, shape=None):
+    """(records, (H, W)) of a ray accumulator: the pt_ray records of o, d
+    (n, 3) f64 and keys (n,) u32 (None: 0..n-1) as element e's, and the shape
+    they fill — (1, n) for a flat batch, shape=(H, W) with H*W = n for an image
+    whose records are in image orientation, e = (H-1-iy)*W + ix."""
+    rec = make_rays(o, d, keys)
+    n = rec.shape[0]
+    if shape is None:
+        H, W = 1, n
+    else:
+        H, W = (int(v) for v in shape)
+        if H < 1 or W < 1 or H * W != n:
+            raise ValueError(f"shape {tuple(shape)} does not hold the {n} records")
+    if not 1 <= n < 1 << 30:
+        raise ValueError("a ray accumulator needs 1 <= n < 2^30 records")
+    return rec, (H, W)
+
+
+class RayAccumulator(Accumulator):
+    """A `pt_accum` whose element e belongs to ray record e instead of a pixel
+    of the scene's camera (pt_accum_create_rays): o, d (n, 3) f64 and keys
+    (n,) u32 as for Renderer.render_rays; shape=None is a flat batch (height
+    1, width n), shape=(H, W) an image of records in image orientation.  The
+    records are uploaded and copied by the library at create.  Every method of
+    Accumulator applies, on the arrays' (H, W) shape."""
+
+    def __init__(self, renderer, o, d, keys=None, shape=None, band=None):
+        self.records, (H, W) = ray_records(o, d, keys, shape)
+        super().__init__(renderer, W, H, band)
+
+    def _create(self, renderer):
+        import torch
+        h = C.c_void_p()
+        with self._device():
+            dev = torch.from_numpy(self.records.view(np.uint8)).cuda()
+            torch.cuda.current_stream().synchronize()   # the upload has landed
+            _native.check(self._lib.pt_accum_create_rays(renderer._h, C.c_void_p(dev.data_ptr()), self.width,
+                                                         self.height, C.byref(h)), "pt_accum_create_rays")
+        return h   # (the library made its own copy: dev may go)
+
+
 def _pass_loop(acc, params, adapt, on_pass, limit, done=(), stop_after=None, after_pass=None):
     """select, stop on an empty list, render — continuing the passes `done`.
     Returns (passes, finished): finished False when stop_after passes were
@@ -373,11 +423,14 @@ class AccumCheckpoint:
             os.remove(self.path)
 
 
-def accum_key(packed, width, height, bounces, seed, rr, rr_depth, lanes_per_pixel, aa=False, lens=None):
+def accum_key(packed, width, height, bounces, seed, rr, rr_depth, lanes_per_pixel, aa=False, lens=None,
+              rays=None, shape=None):
     """AccumCheckpoint's key: what defines sample s of a pixel and the sum
     order of the moments.  "aa" is present only when antialiasing is on and
     "lens": [R, zf] only when the samples go through a lens, so the keys and
-    files from before them stay valid."""
+    files from before them stay valid.  rays: the pt_ray records of a ray
+    accumulator — the key then holds "rays", the sha256 of their bytes, and
+    "shape", the shape of the run's arrays ([n] or [H, W]); absent otherwise."""
     key = {"scene": scene_fingerprint(packed), "width": int(width), "height": int(height),
            "bounces": int(bounces), "seed": int(seed), "rr": bool(rr),
            "rr_depth": int(rr_depth), "lanes_per_pixel": int(lanes_per_pixel)}
@@ -385,6 +438,9 @@ def accum_key(packed, width, height, bounces, seed, rr, rr_depth, lanes_per_pixe
         key["aa"] = True
     if lens is not None:
         key["lens"] = [float(lens[0]), float(lens[1])]
+    if rays is not None:
+        key["rays"] = hashlib.sha256(np.ascontiguousarray(rays).tobytes()).hexdigest()
+        key["shape"] = [int(v) for v in (shape if shape is not None else (len(rays),))]
     return key
 
 
@@ -429,20 +485,35 @@ def render_adaptive(renderer, width=None, height=None, max_spp=64, bounces=1, se
     adapt = make_adapt(tol, max_spp, min_spp, step_spp, floor)
     ck = checkpoint if isinstance(checkpoint, AccumCheckpoint) or checkpoint is None \
         else AccumCheckpoint(checkpoint)
-    key = rule = state = None
+    key = None
     if ck is not None:
         key = accum_key(renderer.packed, width, height, bounces, params.seed, rr, rr_depth,
                         lanes_per_pixel, aa, through)
-        rule = {"tol": float(tol), "min_spp": int(min_spp), "max_spp": int(max_spp),
-                "step_spp": int(step_spp), "floor": float(floor)}
+    # (the whole frame; a band only to carry the fixed lane count)
+    kw = dict(band=make_band(height, lanes_per_pixel=lanes_per_pixel)) if lanes_per_pixel else {}
+    return _run(lambda: Accumulator(renderer, width, height, **kw), width, height, params, adapt, ck, key,
+                on_pass, max_passes, checkpoint_every, moments, denoise)
+
+
+def _run(make_acc, width, height, params, adapt, ck, key, on_pass, max_passes, checkpoint_every, moments,
+         denoise, shape=None):
+    """The run of render_adaptive / render_rays_adaptive on the accumulator
+    make_acc() opens: resume from the checkpoint ck (key: accum_key's), the
+    pass loop, the closing read and the denoise.  shape: the shape the
+    result's arrays get in place of (height, width) (a flat ray batch)."""
+    rule = state = None
+    if ck is not None:
+        # (read back from the ctypes record: c_double and int32 fields, so the
+        # values are the callers' arguments; a narrower field type in
+        # make_adapt would change what the file records)
+        rule = {"tol": float(adapt.tol), "min_spp": int(adapt.min_spp), "max_spp": int(adapt.max_spp),
+                "step_spp": int(adapt.step_spp), "floor": float(adapt.floor)}
         state = ck.load(key)
         if state is not None and (state["S"].shape != (height, width, 3) or
                                   state["Q"].shape != (height, width, 3) or
                                   state["n"].shape != (height, width)):
             raise ValueError(f"checkpoint state does not fit the render: {state['S'].shape}")
-    # (the whole frame; a band only to carry the fixed lane count)
-    kw = dict(band=make_band(height, lanes_per_pixel=lanes_per_pixel)) if lanes_per_pixel else {}
-    with Accumulator(renderer, width, height, **kw) as acc:
+    with make_acc() as acc:
         done = []
         if state is not None:
             acc.write(state["S"], state["Q"], state["n"])
@@ -469,10 +540,57 @@ def render_adaptive(renderer, width=None, height=None, max_spp=64, bounces=1, se
         if denoise is not None:
             den, var = acc.denoise(**(denoise if isinstance(denoise, dict) else {}))
             feat = acc.features()
+    if shape is not None:   # (height, width, ...) -> shape + (...)
+        def fit(x):
+            return None if x is None else x.reshape(tuple(shape) + x.shape[2:])
+        d = {k: fit(v) for k, v in d.items()}
+        den, var = fit(den), fit(var)
+        feat = None if feat is None else {k: fit(v) for k, v in feat.items()}
     n = d["n"]
     fb = np.where(n[..., None] > 0, d["S"] / np.maximum(n, 1)[..., None], 0.0)
     return AdaptiveResult(fb, n, d["err"], passes, den, var, feat,
                           *((d["S"], d["Q"]) if moments else ()))
+
+
+def render_rays_adaptive(renderer, o, d, keys=None, shape=None, max_spp=64, bounces=1, tol=0.05, min_spp=8,
+                         step_spp=8, floor=0.01, seed=None, rr=False, rr_depth=3, lanes_per_pixel=0,
+                         denoise=False, checkpoint=None, force_f64=False, on_pass=None, checkpoint_every=1,
+                         max_passes=None, moments=False, **denoise_params):
+    """render_adaptive for caller-supplied rays: every record is sampled until
+    its err <= tol or it has max_spp samples (a RayAccumulator; sample s of a
+    record is Renderer.render_rays' sample s).  o, d (n, 3) f64, keys (n,) u32
+    (None: 0..n-1) as for render_rays; shape=None: a flat batch, the result's
+    fb, counts and err are (n, ...); shape=(H, W): the records of an image in
+    image orientation (cameras.to_image_order), the result's arrays are
+    (H, W, ...).  denoise=True (denoise_params: make_denoise's) also gives the
+    filtered values, their variance and the records' first-hit features —
+    neighbours are neighbours in the shape.  lanes_per_pixel: lanes per record,
+    0 lets the library choose per pass; checkpoint, checkpoint_every,
+    max_passes, moments, on_pass, force_f64: as for render_adaptive (a resumed
+    run continues bit for bit at a fixed lanes_per_pixel).  The passes run the
+    list kernel over ray records on every scene.  Returns an AdaptiveResult."""
+    check_rule(tol, max_spp, min_spp, step_spp, floor)
+    if denoise_params and not denoise:
+        raise ValueError(f"{sorted(denoise_params)}: filter parameters need denoise=True")
+    if int(checkpoint_every) < 1:
+        raise ValueError("checkpoint_every must be >= 1")
+    rec, (H, W) = ray_records(o, d, keys, shape)
+    seed = renderer.scene.seed if seed is None else seed
+    seed = 0 if seed is None else int(seed)
+    flags = (PT_FLAG_RR if rr else 0) | (PT_FLAG_FORCE_F64 if force_f64 else 0)
+    params = make_params(W, H, max_spp, bounces, seed, flags, rr_depth)
+    adapt = make_adapt(tol, max_spp, min_spp, step_spp, floor)
+    ck = checkpoint if isinstance(checkpoint, AccumCheckpoint) or checkpoint is None \
+        else AccumCheckpoint(checkpoint)
+    key = None
+    if ck is not None:
+        key = accum_key(renderer.packed, W, H, bounces, params.seed, rr, rr_depth, lanes_per_pixel,
+                        rays=rec, shape=shape)
+    kw = dict(band=make_band(H, lanes_per_pixel=lanes_per_pixel)) if lanes_per_pixel else {}
+    return _run(lambda: RayAccumulator(renderer, rec["o"], rec["d"], rec["key"], (H, W), **kw), W, H, params,
+                adapt, ck, key, on_pass, max_passes, checkpoint_every, moments,
+                (denoise_params or True) if denoise else None,
+                shape=None if shape is not None else (rec.shape[0],))
 
 
 def transfer_band(src, dst, band):

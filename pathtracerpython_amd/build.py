@@ -33,9 +33,11 @@ UNITS = {"pt_k2.hip": _ILP, "pt_shade.hip": _ILP}
 # pt_shade.hip so that its four kernels stay as they were
 # the ray kernel (pt_rays.hip, pt_radiance): its own unit as well, the same flags;
 # and the ray form's wavefront kernels (pt_shade_rays.hip), apart from the
-# other shade units for the same reason
+# other shade units for the same reason;
+# and a ray accumulator's kernels (pt_rays_list.hip: the list pass over ray
+# records and the records' features), registered as pt_rays.hip is
 AA_UNITS = {"pt_aa.hip": _ILP, "pt_lens.hip": _ILP, "pt_shade_lens.hip": _ILP, "pt_rays.hip": _ILP,
-            "pt_shade_rays.hip": _ILP}
+            "pt_shade_rays.hip": _ILP, "pt_rays_list.hip": _ILP}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 # -ffp-contract=off: every f64 operation rounds separately, as the reference's

@@ -1,7 +1,9 @@
 """Ray generators for Renderer.render_rays (pt_radiance): each returns
 (origins (n, 3) f64, dirs (n, 3) f64, keys (n,) u32) in the reference's list
 order k = ix*H + iy (x outer, y inner, iy upwards — utils.py:64-69), with
-key = k, so `rays_to_image` puts the result into image orientation."""
+key = k, so `rays_to_image` puts the result into image orientation;
+`to_image_order` reorders the rays themselves, for an H x W ray accumulator
+(Renderer.render_rays_adaptive with shape=(H, W))."""
 import numpy as np
 
 
@@ -86,3 +88,26 @@ def rays_to_image(values, W, H):
     top row first (render.from_list_order's placement)."""
     v = np.asarray(values)
     return v.reshape(int(W), int(H), -1).transpose(1, 0, 2)[::-1]
+
+
+def to_image_order(origins, dirs, keys, W, H):
+    """The generators' list-order rays (k = ix*H + iy) as image-order records:
+    (o, d, keys) with record e = (H-1-iy)*W + ix the ray of list index k, keys
+    unchanged per ray — what an H x W ray accumulator takes
+    (render_rays_adaptive(..., shape=(H, W))); its (H, W, ...) results are then
+    images, top row first, as rays_to_image would place them."""
+    W, H = int(W), int(H)
+    o = rays_to_image(np.asarray(origins, dtype=np.float64).reshape(W * H, 3), W, H).reshape(W * H, 3)
+    d = rays_to_image(np.asarray(dirs, dtype=np.float64).reshape(W * H, 3), W, H).reshape(W * H, 3)
+    k = rays_to_image(np.asarray(keys).reshape(W * H, 1), W, H).reshape(W * H)
+    return np.ascontiguousarray(o), np.ascontiguousarray(d), np.ascontiguousarray(k)
+
+
+def from_image_order(values, W, H):
+    """Inverse of to_image_order for any per-record array: image-order values
+    (H*W, ...) or (H, W, ...) back into the generators' list order (W*H, ...)."""
+    W, H = int(W), int(H)
+    v = np.asarray(values)
+    tail = v.shape[2:] if v.shape[:2] == (H, W) else v.shape[1:]
+    v = v.reshape((H, W) + tail)
+    return np.ascontiguousarray(np.swapaxes(v[::-1], 0, 1)).reshape((W * H,) + v.shape[2:])

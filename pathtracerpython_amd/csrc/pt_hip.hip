@@ -46,6 +46,7 @@ static int fail(int code, const std::string& msg) {
 #include "pt_aa.h"   // the antialiasing kernels' launchers (pt_aa.hip)
 #include "pt_lens.h" // the thin-lens kernels' launchers (pt_lens.hip)
 #include "pt_rays.h" // the ray kernel's launcher (pt_rays.hip)
+#include "pt_rays_list.h" // a ray accumulator's kernels' launchers (pt_rays_list.hip)
 #if PT_K2_OWN_TU
 extern template __global__ void k_render<false, false, false>(SceneK, RenderK, void*, StatsDev*);
 #endif
@@ -1770,6 +1771,9 @@ struct pt_accum {
     // yet): a pass with the other value is refused
     int aa = -1;
     int lens = -1;   // PT_FLAG_LENS likewise
+    // a ray accumulator (pt_accum_create_rays): its own copy of the W*H
+    // records, element e's primary ray; null: a frame accumulator
+    RayK* rays = nullptr;
 };
 
 // pt_accum_band -> BandK, or PT_EINVAL
@@ -1820,6 +1824,87 @@ static int accum_end(pt_accum* a, hipStream_t st) {
     return PT_OK;
 }
 
+// pt_accum_render(_stats) on a ray accumulator: one launch of the list kernel
+// over ray records (pt_rays_list.hip) on every scene
+static int accum_render_rays(pt_accum* a, const pt_render_params* p, const pt_adapt_params* ap, void* stream,
+                             pt_stats* stats) {
+    if (!p) return fail(PT_EINVAL, "null params");
+    const uint32_t ok_flags = PT_FLAG_RR | PT_FLAG_FORCE_F64 | PT_FLAG_RAYS_SINGLE;
+    if (p->flags & ~ok_flags) {
+        static const struct { uint32_t bit; const char* name; } kNames[] = {
+            {PT_FLAG_COUNT, "PT_FLAG_COUNT"}, {PT_FLAG_OUT_F64, "PT_FLAG_OUT_F64"},
+            {PT_FLAG_MEGAKERNEL, "PT_FLAG_MEGAKERNEL"}, {PT_FLAG_WALK_COUNT, "PT_FLAG_WALK_COUNT"},
+            {PT_FLAG_KERNEL_TIMES, "PT_FLAG_KERNEL_TIMES"}, {PT_FLAG_AA, "PT_FLAG_AA"}, {PT_FLAG_LENS, "PT_FLAG_LENS"}};
+        std::string bad;
+        uint32_t rest = p->flags & ~ok_flags;
+        for (const auto& f : kNames)
+            if (rest & f.bit) {
+                bad += std::string(bad.empty() ? "" : ", ") + f.name;
+                rest &= ~f.bit;
+            }
+        if (rest) bad += std::string(bad.empty() ? "" : ", ") + "unknown bits";
+        return fail(PT_EINVAL, "unsupported flag bits (" + bad + "): a pass of a ray accumulator takes PT_FLAG_RR, "
+                               "PT_FLAG_FORCE_F64 and PT_FLAG_RAYS_SINGLE only (the ray list kernel does not count, "
+                               "jitter or draw a lens point, and is the single kernel already)");
+    }
+    pt_render_params q = *p;
+    q.flags &= ~(uint32_t)PT_FLAG_RAYS_SINGLE;   // (accepted, no effect yet: reserved for the wavefront form)
+    int rc = validate(&q);
+    if (rc) return rc;
+    AdaptK A;
+    rc = check_adapt(ap, &A);
+    if (rc) return rc;
+    if (p->width != a->W || p->height != a->H)
+        return fail(PT_EINVAL, "width/height are not the accumulator's");
+    if (p->row_begin != 0 || p->row_end != p->height || p->row_step != 1 || p->row_phase != 0 ||
+        p->sample_begin != 0 || p->out_row_stride != 0 || p->lanes_per_pixel != 0)
+        return fail(PT_EINVAL, "an accumulator pass renders the whole frame: row_begin 0, row_end height, "
+                               "row_step 1, sample_begin 0, out_row_stride 0, lanes_per_pixel 0");
+    if (p->spp != ap->max_spp) return fail(PT_EINVAL, "spp must be the budget max_spp");
+    pt_scene* s = a->scene;
+    DeviceGuard g(s->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    rc = pt_accum_select(a, ap, stream, nullptr, nullptr);
+    if (rc) return rc;
+    const AccumMeta m = a->list_meta;
+    if (m.count == 0) return PT_OK;
+    const uint32_t kmin = ~m.nkmin;
+    if (kmin == 0 || kmin > A.step_spp) return fail(PT_EHIP, "select: bad pass size");
+    const bool bvh = s->dev.n_bnode > 0;
+    RaysListK R;
+    R.bounces = p->bounces;
+    R.rr_depth = (p->flags & PT_FLAG_RR) ? std::max(0, p->rr_depth) : -1;
+    R.seed = p->seed;
+    // lanes per record: a frame accumulator's rule (pt_accum_render_stats)
+    if (a->lanes_per_pixel == 0) {
+        R.split = choose_split((uint64_t)a->npix, (uint64_t)m.count, (int32_t)std::min(kmin, 64u), bvh,
+                               min_lanes_of(s->n_cu));
+    } else {
+        uint32_t cap = 1;
+        while (cap * 2u <= std::min(kmin, 64u)) cap *= 2u;
+        R.split = std::min(a->lanes_per_pixel, cap);
+    }
+    R.split_log2 = log2_ceil(R.split);
+    R.n_list = m.count;
+    R.n_rays = a->npix;
+    R.frame_x = s->host.frame_x;
+    R.A = A;
+    const uint64_t threads = (uint64_t)m.count << R.split_log2;
+    const uint64_t blocks = (threads + kRenderBlock - 1) / kRenderBlock;
+    if (blocks * kRenderBlock >= ((uint64_t)1 << 32))
+        return fail(PT_EINVAL, "launch needs 2^32 or more work-items (32-bit lane index)");
+    rc = accum_begin(a, st);
+    if (rc) return rc;
+    a->list_valid = false;   // the pass changes n, S, Q
+    a->aa = 0;
+    a->lens = 0;
+    s->last = pt_launch_info{PT_PATH_SINGLE, 1, (int32_t)R.split, p->flags};
+    pt_rays_render_list((p->flags & PT_FLAG_FORCE_F64) != 0, bvh, dim3((unsigned)blocks), st, s->dev, R, a->rays,
+                        a->list, a->S, a->Q, a->n);
+    return accum_end(a, st);
+}
+
 extern "C" {
 
 void pt_accum_destroy(pt_accum* a) {
@@ -1828,7 +1913,7 @@ void pt_accum_destroy(pt_accum* a) {
         DeviceGuard g(a->scene->device);
         if (a->stream) (void)hipStreamSynchronize(a->stream);
         void* bufs[] = {a->S, a->Q, a->err, a->n, a->list, a->bcount, a->meta, a->home,
-                        a->f_tri, a->f_obj, a->f_N, a->f_P, a->dn[0], a->dn[1], a->dn[2], a->dn[3]};
+                        a->f_tri, a->f_obj, a->f_N, a->f_P, a->dn[0], a->dn[1], a->dn[2], a->dn[3], a->rays};
         for (void* b : bufs)
             if (b) (void)hipFree(b);
         if (a->stream) (void)hipStreamDestroy(a->stream);
@@ -1854,12 +1939,9 @@ int pt_accum_reset(pt_accum* a, void* stream) {
     return accum_end(a, st);
 }
 
-int pt_accum_create(pt_scene* s, int32_t width, int32_t height, pt_accum** out) {
-    if (!out) return fail(PT_EINVAL, "null output handle");
-    *out = nullptr;
-    if (!s) return fail(PT_EINVAL, "null scene");
-    if (width <= 0 || height <= 0) return fail(PT_EINVAL, "width/height must be > 0");
-    if ((int64_t)width * height >= (int64_t)1 << 32) return fail(PT_EINVAL, "image too large for 32-bit pixel keys");
+// rays_dev: null for a frame accumulator, else the width*height records of a
+// ray accumulator in device memory, copied here
+static int accum_create(pt_scene* s, int32_t width, int32_t height, const pt_ray* rays_dev, pt_accum** out) {
     DeviceGuard g(s->device);
     pt_accum* a = new pt_accum();
     a->scene = s;
@@ -1880,10 +1962,41 @@ int pt_accum_create(pt_scene* s, int32_t width, int32_t height, pt_accum** out) 
         pt_accum_destroy(a);
         return fail(PT_EHIP, "stream creation");
     }
+    if (rays_dev) {   // (synchronous: the caller's buffer may go away on return)
+        if (hipMalloc((void**)&a->rays, np * sizeof(RayK)) != hipSuccess) {
+            pt_accum_destroy(a);
+            return fail(PT_ENOMEM, "hipMalloc ray records");
+        }
+        if (hipMemcpyAsync(a->rays, rays_dev, np * sizeof(RayK), hipMemcpyDeviceToDevice, a->stream) != hipSuccess ||
+            hipStreamSynchronize(a->stream) != hipSuccess) {
+            pt_accum_destroy(a);
+            return fail(PT_EHIP, "copying the ray records");
+        }
+    }
     int rc = pt_accum_reset(a, a->stream);
     if (rc) { pt_accum_destroy(a); return rc; }
     *out = a;
     return PT_OK;
+}
+
+int pt_accum_create(pt_scene* s, int32_t width, int32_t height, pt_accum** out) {
+    if (!out) return fail(PT_EINVAL, "null output handle");
+    *out = nullptr;
+    if (!s) return fail(PT_EINVAL, "null scene");
+    if (width <= 0 || height <= 0) return fail(PT_EINVAL, "width/height must be > 0");
+    if ((int64_t)width * height >= (int64_t)1 << 32) return fail(PT_EINVAL, "image too large for 32-bit pixel keys");
+    return accum_create(s, width, height, nullptr, out);
+}
+
+int pt_accum_create_rays(pt_scene* s, const pt_ray* rays_dev, int32_t width, int32_t height, pt_accum** out) {
+    if (!out) return fail(PT_EINVAL, "null output handle");
+    *out = nullptr;
+    if (!s) return fail(PT_EINVAL, "null scene");
+    if (width <= 0 || height <= 0) return fail(PT_EINVAL, "width/height must be > 0: a ray accumulator has 1 <= width*height < 2^30 records");
+    if ((int64_t)width * height >= (int64_t)1 << 30)
+        return fail(PT_EINVAL, "a ray accumulator has 1 <= width*height < 2^30 records");
+    if (!rays_dev) return fail(PT_EINVAL, "null ray array");
+    return accum_create(s, width, height, rays_dev, out);
 }
 
 int pt_accum_select(pt_accum* a, const pt_adapt_params* ap, void* stream, uint32_t* n_active,
@@ -1936,6 +2049,7 @@ int pt_accum_render(pt_accum* a, const pt_render_params* p, const pt_adapt_param
 
 int pt_accum_render_stats(pt_accum* a, const pt_render_params* p, const pt_adapt_params* ap, void* stream,
                           pt_stats* stats) {
+    if (a && a->rays) return accum_render_rays(a, p, ap, stream, stats);
     int rc = validate(p);
     if (rc) return rc;
     if (!a) return fail(PT_EINVAL, "null accumulator");
@@ -2284,7 +2398,10 @@ static int accum_features_launch(pt_accum* a, hipStream_t st) {
     }
     pt_scene* s = a->scene;
     const dim3 grid((a->npix + 255u) / 256u), block(256);
-    if (s->dev.n_bnode > 0)
+    if (a->rays)   // a ray accumulator: each record's own ray (pt_rays_list.hip)
+        pt_rays_features(s->dev.n_bnode > 0, st, s->dev, s->host.frame_x, a->rays, a->npix, a->f_tri, a->f_obj,
+                         a->f_N, a->f_P);
+    else if (s->dev.n_bnode > 0)
         hipLaunchKernelGGL((k_features<true>), grid, block, 0, st, s->dev, a->W, a->H, a->npix, a->f_tri, a->f_obj,
                            a->f_N, a->f_P);
     else

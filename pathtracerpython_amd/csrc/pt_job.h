@@ -169,3 +169,52 @@ PT_HD RayJob rays_job(const RaysK& R, const RayK* __restrict__ rays, uint32_t ti
     }
     return j;
 }
+
+// A pass of a ray accumulator (pt_accum_create_rays, include/pt_capi.h): the
+// launch renders a LIST of ray records; element e of the accumulator belongs
+// to record e.
+struct RaysListK {
+    int32_t bounces, rr_depth;   // rr_depth -1: off
+    uint64_t seed;
+    uint32_t split, split_log2;
+    uint32_t n_list, n_rays;
+    double frame_x;   // rays_in_frame's extent (HostScene::frame_x)
+    AdaptK A;
+};
+// Work-item -> (list entry, sample slice) of such a pass, k_render_rays_list's
+// mapping (pt_rays_list.hip): list_job's with the record rays[e] in the place
+// of pixel e's primary ray — `split` adjacent work-items share the entry's
+// record and stride the k = adapt_k(n[e]) samples the pass adds, from sample
+// n[e] on; the Philox pixel word is the record's key.  An entry that is no
+// record of the accumulator is never dereferenced (ray stays null).
+struct RayListJob {
+    LaneJob J;
+    const RayK* ray;
+    uint32_t e, k;
+    bool valid;
+};
+PT_HD RayListJob rays_list_job(const RaysListK& R, const RayK* __restrict__ rays,
+                               const uint32_t* __restrict__ list, const uint32_t* __restrict__ accN,
+                               uint32_t tid) {
+    RayListJob j;
+    const uint32_t entry = tid >> R.split_log2, c = tid & (R.split - 1u);
+    j.e = entry < R.n_list ? list[entry] : 0xffffffffu;
+    j.valid = j.e < R.n_rays;   // the same for all lanes of an entry
+    j.k = 0;
+    j.ray = nullptr;
+    j.J = LaneJob{};
+    // (the launch's constants outside the branch, as list_job keeps them)
+    j.J.seed = R.seed;
+    j.J.sample_stride = (int32_t)R.split;
+    j.J.bounces = R.bounces;
+    j.J.rr_depth = R.rr_depth;
+    if (j.valid) {
+        const uint32_t n0 = accN[j.e];
+        j.k = adapt_k(n0, R.A);
+        j.ray = rays + j.e;
+        j.J.pixel = j.ray->key;
+        j.J.sample0 = (int32_t)(n0 + c);
+        j.J.n_samples = c < j.k ? (int32_t)((j.k - c + R.split - 1u) >> R.split_log2) : 0;
+    }
+    return j;
+}

@@ -27,7 +27,11 @@ TY TZ [--up UX UY UZ] [--fov DEG] (a pinhole at E looking at T in place of the
 scene's camera: cameras.look_at_rays through Renderer.render_rays,
 pt_radiance, which takes the wavefront kernels on a scene with a BVH and the
 single ray kernel otherwise; with -r, -b, --rr, --seed, --size, --out and
---save-raw only).  The
+--save-raw; with --ray-accum also --noise, --denoise, --save-aov and
+--checkpoint (with --noise): the frame then goes through an H x W ray
+accumulator, Renderer.render_rays_adaptive, whose passes run the list kernel
+over ray records; never with --aa, --aperture, --devices N > 1,
+--local-devices or --chunk-spp).  The
 reference's interactive 3-D viewer flags (--show-scene, --show-normals,
 --show-screen, --show-inter -> plot.py) are accepted and ignored with a
 notice: the pyqtgraph viewer is out of scope.
@@ -64,7 +68,12 @@ def setup(argv=None):
                         help='render through a pinhole at E looking at T instead of the scene\'s '
                              'camera (cameras.look_at_rays through Renderer.render_rays: the '
                              'wavefront kernels on a scene with a BVH, else the single ray kernel); with '
-                             '-r, -b, --rr, --seed, --size, --out and --save-raw only')
+                             '-r, -b, --rr, --seed, --size, --out and --save-raw, and with --ray-accum '
+                             'also --noise, --denoise, --save-aov and --checkpoint')
+    parser.add_argument('--ray-accum', default=False, action='store_true',
+                        help='with --look-at and --noise or --denoise: the frame through a ray accumulator '
+                             '(Renderer.render_rays_adaptive); then also --save-aov and, with --noise, '
+                             '--checkpoint')
     parser.add_argument('--up', type=float, nargs=3, default=None, metavar=('UX', 'UY', 'UZ'),
                         help='with --look-at: the direction towards the top of the image (default 0 1 0)')
     parser.add_argument('--fov', type=float, default=None, metavar='DEG',
@@ -156,19 +165,33 @@ def check_args(args):
         raise SystemExit('--aperture and --focus-z go together')
     if args.look_at is None and (args.up is not None or args.fov is not None):
         raise SystemExit('--up and --fov go with --look-at')
+    if args.look_at is None and args.ray_accum:
+        raise SystemExit('--ray-accum goes with --look-at')
     if args.look_at is not None:
         args.up = [0.0, 1.0, 0.0] if args.up is None else args.up
         args.fov = 40.0 if args.fov is None else args.fov
-        # (a ray batch is one launch on one device: the wavefront kernels on a
-        # scene with a BVH, else the single ray kernel; no jitter, lens or moments)
+        # (a ray batch, or with --ray-accum a ray accumulator, lives on one device
+        # in one process: no jitter, no lens, no sample chunks)
         for on, name in ((args.aa, '--aa'), (args.aperture is not None, '--aperture'),
-                         (args.noise is not None, '--noise'), (args.denoise, '--denoise'),
                          (args.devices > 1, '--devices > 1'), (args.local_devices is not None, '--local-devices'),
-                         (args.chunk_spp, '--chunk-spp'), (args.checkpoint, '--checkpoint'),
-                         (args.save_aov, '--save-aov')):
+                         (args.chunk_spp, '--chunk-spp')):
             if on:
                 raise SystemExit(f'--look-at does not combine with {name}: it takes -r, -b, --rr, --seed, '
-                                 '--size, --out and --save-raw')
+                                 '--size, --out and --save-raw, and with --ray-accum also --noise, --denoise, '
+                                 '--save-aov and --checkpoint')
+        if not args.ray_accum:
+            # without the switch a look-at frame is one render_rays launch, as it
+            # always was: what needs an accumulator is refused by name
+            for on, name in ((args.noise is not None, '--noise'), (args.denoise, '--denoise'),
+                             (args.checkpoint, '--checkpoint'), (args.save_aov, '--save-aov')):
+                if on:
+                    raise SystemExit(f'--look-at does not combine with {name} unless --ray-accum is given (the '
+                                     'frame then goes through a ray accumulator); without it, it takes -r, -b, '
+                                     '--rr, --seed, --size, --out and --save-raw')
+        elif args.noise is None and not args.denoise:
+            raise SystemExit('--look-at --ray-accum goes with --noise or --denoise')
+        elif args.checkpoint and args.noise is None:
+            raise SystemExit('--look-at takes --checkpoint with --noise only (the resumable adaptive run)')
         if not 0.0 < args.fov < 180.0:
             raise SystemExit('--fov: need 0 < DEG < 180')
     if args.aperture is not None and args.devices > 1:
@@ -314,8 +337,10 @@ def main(argv=None):
 
 def render_look_at(scene, args, W, H):
     """The f64 frame of --look-at: cameras.look_at_rays through
-    Renderer.render_rays, the scene prepared for the eye point."""
-    from .cameras import look_at_rays, rays_to_image
+    Renderer.render_rays, the scene prepared for the eye point; with
+    --ray-accum (and --noise or --denoise) through an H x W ray accumulator
+    (Renderer.render_rays_adaptive on the rays in image order)."""
+    from .cameras import look_at_rays, rays_to_image, to_image_order
     from .render import Renderer
     eye = args.look_at[:3]
     try:
@@ -323,6 +348,19 @@ def render_look_at(scene, args, W, H):
     except ValueError as e:
         raise SystemExit(f'--look-at: {e}')
     with Renderer(scene, ray_box=(eye, eye)) as r:
+        if args.ray_accum:
+            kw = adaptive_args(args)
+            kw.pop('aa')
+            dn = kw.pop('denoise')
+            ck = dict(checkpoint=args.checkpoint) if args.checkpoint else {}
+            res = r.render_rays_adaptive(*to_image_order(o, d, keys, W, H), shape=(H, W), max_spp=args.n_rays,
+                                         bounces=args.n_bounces, seed=args.seed, rr=args.rr,
+                                         denoise=dn is not None, **(dn or {}), **kw, **ck)
+            fb = report_adaptive(args, res, W, H)
+            spp = f'up to {args.n_rays}' if args.noise is not None else f'{args.n_rays}'
+            print(f'render: {W}x{H} through --look-at, {spp} spp, {args.n_bounces} bounces, '
+                  f'ray accumulator, last pass {r.last_kernel_ms():.3f} ms')
+            return np.ascontiguousarray(fb)
         rgb = r.render_rays(o, d, keys, spp=args.n_rays, bounces=args.n_bounces, seed=args.seed, rr=args.rr)
         from ._abi import PATH_NAMES
         print(f'render: {W}x{H} through --look-at, {args.n_rays} spp, {args.n_bounces} bounces, '

@@ -199,6 +199,22 @@ class Renderer:
                                             C.c_void_p(Q.ctypes.data) if moments else None), "pt_radiance")
         return (rgb, S, Q) if moments else rgb
 
+    def render_rays_adaptive(self, origins, dirs, keys=None, shape=None, max_spp=64, bounces=1, tol=0.05,
+                             min_spp=8, step_spp=8, floor=0.01, seed=None, rr=False, rr_depth=3,
+                             lanes_per_pixel=0, denoise=False, checkpoint=None, **more):
+        """render_rays to the noise target `tol` within max_spp samples per
+        record (adaptive.render_rays_adaptive, a RayAccumulator): an
+        AdaptiveResult whose fb, counts and err are (n, ...), or (H, W, ...)
+        with shape=(H, W) and the records in image orientation
+        (cameras.to_image_order).  denoise=True: also the filtered values,
+        their variance and the records' first-hit features (more: the filter's
+        parameters).  checkpoint: a resumable run.  more also takes force_f64,
+        on_pass, checkpoint_every, max_passes and moments.  The passes run the
+        list kernel over ray records on every scene (last_launch(): single)."""
+        from .adaptive import render_rays_adaptive
+        return render_rays_adaptive(self, origins, dirs, keys, shape, max_spp, bounces, tol, min_spp, step_spp,
+                                    floor, seed, rr, rr_depth, lanes_per_pixel, denoise, checkpoint, **more)
+
     def last_kernel_ms(self):
         ms = C.c_float(0)
         _native.check(self._lib.pt_last_kernel_ms(self._h, C.byref(ms)), "pt_last_kernel_ms")
