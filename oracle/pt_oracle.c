@@ -302,6 +302,21 @@ void oracle_rotate(const double* n, const double* v, double* out) {
     rotate_y(acos(0.0 * n[0] + 1.0 * n[1] + 0.0 * n[2]), v, out);
 }
 
+/* main.py:242-247: the diffuse direction before its rotation, from the phi
+ * and theta draws.  One function for path_body and for the tests' restatement
+ * of it (oracle_diffuse_dir): the compiler may fuse sin and cos of one angle
+ * into a sincos call, whose last bit is not always sin's and cos's. */
+static __attribute__((noinline)) void diffuse_dir(double u_phi, double u_theta, double* v) {
+    double phi = acos(sqrt(uniform_ab(0.0, 1.0, u_phi)));
+    double theta = TAU * uniform_ab(0.0, 1.0, u_theta);
+    v[0] = sin(phi) * cos(theta);
+    v[1] = sin(phi) * sin(theta);
+    v[2] = cos(phi);
+    normalize3(v);
+}
+
+void oracle_diffuse_dir(double u_phi, double u_theta, double* v) { diffuse_dir(u_phi, u_theta, v); }
+
 /* utils.py:64-69 make_screen_pts: np.linspace semantics */
 static double linspace_at(double a, double b, int n, int i) {
     if (n == 1) return a;
@@ -310,20 +325,20 @@ static double linspace_at(double a, double b, int n, int i) {
     return (double)i * step + a;
 }
 
-/* One path sample of pixel k = ix*H + iy: main.py:186-271 for a single ray. */
-static void path_sample(const oscene* s, const pt_render_params* p, int64_t pixel_k,
-                        int sample, double* rgb, ocount* cnt) {
+/* One path sample of a ray (o0, d0): main.py:186-271 from the ray on.  `eye`
+ * is the point the "specular" term looks back to (main.py:254-257): the
+ * scene's eye for a frame's ray, the ray's own origin for a caller's; `key` is
+ * the pixel word of the sample's draws.  d0 is used as it comes: the first
+ * bounce's reflection reads its sign and length (main.py:250-252). */
+static void path_body(const oscene* s, const pt_render_params* p, const double* o0,
+                      const double* d0, const double* eye, uint32_t key, int sample,
+                      double* rgb, ocount* cnt) {
     const pt_scene_desc* d = s->d;
-    int H = p->height, W = p->width;
-    int ix = (int)(pixel_k / H), iy = (int)(pixel_k % H);
-    double pt[3] = {linspace_at(d->ortho[0], d->ortho[2], W, ix),
-                    linspace_at(d->ortho[1], d->ortho[3], H, iy), 0.0};
-    double o[3] = {d->eye[0], d->eye[1], d->eye[2]};
-    double dir[3];
-    sub3(pt, o, dir);                        /* utils.py:57-58, unnormalised */
+    double o[3] = {o0[0], o0[1], o0[2]};
+    double dir[3] = {d0[0], d0[1], d0[2]};
     double k = 1.0;                          /* accumulated_k, main.py:190 */
     rgb[0] = rgb[1] = rgb[2] = 0.0;
-    rng_ctx rc = {p->seed, (uint32_t)pixel_k, (uint32_t)sample, 0};
+    rng_ctx rc = {p->seed, key, (uint32_t)sample, 0};
     for (int b = 0; b < p->bounces; ++b) {
         double P[3];
         if (cnt) cnt->ray_bounces++;
@@ -347,10 +362,8 @@ static void path_sample(const oscene* s, const pt_render_params* p, int64_t pixe
         double nd[3];
         double xi = uniform_ab(0.0, m[4] + m[5], keyed_u(&rc, 12));
         if (xi <= m[4]) {                    /* diffuse */
-            double phi = acos(sqrt(uniform_ab(0.0, 1.0, keyed_u(&rc, 13))));
-            double theta = TAU * uniform_ab(0.0, 1.0, keyed_u(&rc, 14));
-            double v[3] = {sin(phi) * cos(theta), sin(phi) * sin(theta), cos(phi)};
-            normalize3(v);
+            double v[3];
+            diffuse_dir(keyed_u(&rc, 13), keyed_u(&rc, 14), v);
             oracle_rotate(n, v, nd);
             k *= m[4] * dot3(nd, n);
         } else {                             /* "specular" */
@@ -358,7 +371,7 @@ static void path_sample(const oscene* s, const pt_render_params* p, int64_t pixe
             double r[3], e[3];
             for (int c = 0; c < 3; ++c) r[c] = ndd * 2 * n[c] - dir[c];
             normalize3(r);
-            sub3(d->eye, P, e);
+            sub3(eye, P, e);
             normalize3(e);
             oracle_rotate(n, r, nd);
             k *= m[5] * pow(dot3(e, nd), m[7]);
@@ -372,6 +385,38 @@ static void path_sample(const oscene* s, const pt_render_params* p, int64_t pixe
         o[0] = P[0]; o[1] = P[1]; o[2] = P[2];
         dir[0] = nd[0]; dir[1] = nd[1]; dir[2] = nd[2];
     }
+}
+
+/* One path sample of pixel k = ix*H + iy: the frame's ray (utils.py:52-69)
+ * into path_body. */
+static void path_sample(const oscene* s, const pt_render_params* p, int64_t pixel_k,
+                        int sample, double* rgb, ocount* cnt) {
+    const pt_scene_desc* d = s->d;
+    int H = p->height, W = p->width;
+    int ix = (int)(pixel_k / H), iy = (int)(pixel_k % H);
+    double pt[3] = {linspace_at(d->ortho[0], d->ortho[2], W, ix),
+                    linspace_at(d->ortho[1], d->ortho[3], H, iy), 0.0};
+    double o[3] = {d->eye[0], d->eye[1], d->eye[2]};
+    double dir[3];
+    sub3(pt, o, dir);                        /* utils.py:57-58, unnormalised */
+    path_body(s, p, o, dir, d->eye, (uint32_t)pixel_k, sample, rgb, cnt);
+}
+
+/* Per-sample colours of caller-supplied rays (the rule of pt_radiance,
+ * include/pt_capi.h): record i is (o[i], d[i], keys[i]) with the eye of the
+ * "specular" term at o[i]; out[j][i][3] is its sample p->sample_begin + j,
+ * j < p->spp.  Reads bounces, seed, flags (PT_FLAG_RR) and rr_depth of p. */
+int oracle_radiance(const pt_scene_desc* d, const pt_render_params* p, const double* o,
+                    const double* dir, const uint32_t* keys, int64_t n, double* out) {
+    if (!d || !p || !out || n < 0 || p->spp <= 0) return -1;
+    oscene s;
+    if (oscene_init(&s, d)) return -1;
+    for (int j = 0; j < p->spp; ++j)
+        for (int64_t i = 0; i < n; ++i)
+            path_body(&s, p, o + 3 * i, dir + 3 * i, o + 3 * i, keys[i],
+                      p->sample_begin + j, out + 3 * ((int64_t)j * n + i), NULL);
+    oscene_free(&s);
+    return 0;
 }
 
 /* ------------------------------------------------------------- render -- */

@@ -143,11 +143,16 @@ PT_HD void closest_unit(const SceneK& S, const UnitF& U, const OriginU& O, F3 d3
 }
 
 // BVH helpers (the traversal itself, bvh_pass, follows fused_unit below)
-PT_HD F3 rcp_dir(F3 d) {   // 1/d; a zero component gives +-1e30 (finite: no 0 * inf)
+// 1/d; a zero component gives 1e30 (finite: no 0 * inf), and so does a
+// subnormal one, whose reciprocal is past FLT_MAX (a caller's ray may have a
+// component of 1e-39; over |t| <= R such a line stays in its slab as one with
+// a zero component does)
+PT_HD F3 rcp_dir(F3 d) {
+    const float tiny = 1.17549435e-38f;   // FLT_MIN
     F3 r;
-    r.x = 1.0f / (d.x == 0.0f ? 1e-30f : d.x);
-    r.y = 1.0f / (d.y == 0.0f ? 1e-30f : d.y);
-    r.z = 1.0f / (d.z == 0.0f ? 1e-30f : d.z);
+    r.x = 1.0f / (fabsf(d.x) < tiny ? 1e-30f : d.x);
+    r.y = 1.0f / (fabsf(d.y) < tiny ? 1e-30f : d.y);
+    r.z = 1.0f / (fabsf(d.z) < tiny ? 1e-30f : d.z);
     return r;
 }
 // slab test of the line o + t d against a box given relative to o (lo - o,
@@ -1789,6 +1794,19 @@ PT_HD D3 nee(const SceneK& S, D3 P, D3 n, int obj, int ogrp, const double u[12],
     return shadow_color<COUNT>(S, obj, sh, cnt);
 }
 
+// unit() for a vector of any length.  rsqrt_d takes a normal argument: below
+// 2^-1022 its 0.5 * x rounds and the Newton steps converge on another
+// number's root.  The reference divides by sqrt(v.v) whatever v.v is, so a
+// subnormal sum of squares (|v| about 1e-160: the sum keeps ten bits, and the
+// quotient is that sum's) is scaled by 2^400 into rsqrt_d's range and the
+// root by 2^200 back, both exact; a sum that overflowed gives v / inf = 0.
+PT_HD D3 unit_any(D3 a) {
+    const double s = dot(a, a);
+    if (s < 0x1p-1000 && s > 0.0) return a * (rsqrt_d(s * 0x1p400) * 0x1p200);
+    if (s > 1.7976931348623157e308) return a * 0.0;
+    return a * rsqrt_d(s);
+}
+
 // ---------------------------------------------------------------- bounce --
 // Next-ray generation, main.py:236-268.  d_old is the incoming direction as
 // the reference holds it (unnormalised for primary rays).  Returns the new
@@ -1815,7 +1833,10 @@ PT_HD D3 bounce(const SceneK& S, const TriS& R, const Mat& m, D3 P, D3 d_old,
     }
     // "specular": r = 2 (n.d) n - d, normalised, rotated; k *= ks (e.r)^n
     const double nd2 = dot(n, d_old) * 2;
-    const D3 r = unit(d3(nd2 * n.x - d_old.x, nd2 * n.y - d_old.y, nd2 * n.z - d_old.z));
+    const D3 r0 = d3(nd2 * n.x - d_old.x, nd2 * n.y - d_old.y, nd2 * n.z - d_old.z);
+    D3 r;
+    if constexpr (LENS == 2) r = unit_any(r0);   // (a caller's d is of any length at bounce 0)
+    else r = unit(r0);
     D3 eye;
     if constexpr (LENS == 2) eye = ld3(eye_o);
     else if constexpr (LENS == 1) eye = d3(sp->get(kSpLens), sp->get(kSpLens + 1), S.kd[kKdEye + 2]);

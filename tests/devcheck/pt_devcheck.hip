@@ -79,6 +79,17 @@ __global__ void __launch_bounds__(kBlock) k_math_f64(const double* x, int64_t n,
     o[3] = s;
     o[4] = c;
 }
+// unit_any (pt_path.h: the ray form's reflection of a caller's direction) and
+// unit of v[i]
+__global__ void __launch_bounds__(kBlock) k_unit_any(const double* v, int64_t n, double* out) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const D3 a = d3(v[3 * i], v[3 * i + 1], v[3 * i + 2]);
+    const D3 r = unit_any(a), u = unit(a);
+    double* o = out + 6 * i;
+    o[0] = r.x; o[1] = r.y; o[2] = r.z;
+    o[3] = u.x; o[4] = u.y; o[5] = u.z;
+}
 __global__ void __launch_bounds__(kBlock) k_rcp_weak(const double* x, int64_t n, double* out) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i < n) out[i] = rcp_d_weak(x[i]);
@@ -120,6 +131,20 @@ int dc_math_f64(const double* x, int64_t n, double* out) {
         B.launched();
     }
     B.download(out, dout, (size_t)n * 5);
+    return B.rc();
+}
+
+// out[i][6] = unit_any(v[i]), unit(v[i])
+int dc_unit_any(const double* v, int64_t n, double* out) {
+    if (!v || !out || n < 1) return kBadArg;
+    Bufs B;
+    double* dv = B.upload(v, (size_t)n * 3);
+    double* dout = B.alloc<double>((size_t)n * 6);
+    if (B.err == hipSuccess) {
+        k_unit_any<<<blocks(n), kBlock>>>(dv, n, dout);
+        B.launched();
+    }
+    B.download(out, dout, (size_t)n * 6);
     return B.rc();
 }
 

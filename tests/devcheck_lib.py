@@ -30,7 +30,7 @@ def load():
     if not os.path.exists(LIB):
         subprocess.run(["make", "-s", "-C", DIR], check=True)
     lib = C.CDLL(LIB)
-    for f in ("dc_math_f64", "dc_rcp_weak", "dc_rcpf", "dc_minmax", "dc_filter"):
+    for f in ("dc_math_f64", "dc_unit_any", "dc_rcp_weak", "dc_rcpf", "dc_minmax", "dc_filter"):
         getattr(lib, f).restype = C.c_int
     return lib
 
@@ -53,6 +53,15 @@ def math_f64(lib, x):
     rc = lib.dc_math_f64(_p(x, C.c_double), C.c_int64(x.size), _p(out, C.c_double))
     assert rc == 0, rc
     return out
+
+
+def unit_any(lib, v):
+    """(unit_any(v), unit(v)), (n, 3) each, of the device."""
+    v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1, 3)
+    out = np.empty((v.shape[0], 6), dtype=np.float64)
+    rc = lib.dc_unit_any(_p(v, C.c_double), C.c_int64(v.shape[0]), _p(out, C.c_double))
+    assert rc == 0, rc
+    return out[:, :3], out[:, 3:]
 
 
 def rcp_weak(lib, x):

@@ -17,9 +17,13 @@ What it does (SURVEY.md §8c "Deterministic harness"):
     check at main.py:227 still holds;
   * replaces `main.make_image` (main.py:288) to capture the averaged colour list
     before min-max normalisation, and also keeps the real make_image output;
-  * overrides the SDL `size` (scene_reader.py:153-155) via a Scene subclass.
+  * overrides the SDL `size` (scene_reader.py:153-155) via a Scene subclass;
+  * `rays` mode: renders caller-chosen rays from one origin — the Scene
+    subclass also moves the eye to the origin, `main.make_rays` (main.py:8,
+    :191) returns (origin, d_i) for list index i, and make_image only captures
+    (render_reference_rays; tests/rays_any_ref.py names the rays).
 
-Usage:  python gen_golden.py [all|scene|kat|mesh|meshkat|k5mini|scenes|materials|render W H SPP B SEED]
+Usage:  python gen_golden.py [all|scene|kat|mesh|meshkat|k5mini|scenes|materials|rays|render W H SPP B SEED]
 """
 import contextlib
 import io
@@ -366,6 +370,72 @@ def gen_materials():
               float(np.nanmax(colors)))
 
 
+def render_reference_rays(origin, dirs, spp, bounces, seed, scene=None):
+    """Run the unmodified reference main() on caller-chosen rays from one
+    origin: a Scene subclass puts the eye at `origin` (the specular term's
+    eye, main.py:258) and makes the frame len(dirs) x 1, and `main.make_rays`
+    (bound at import, main.py:8) returns (origin, dirs[i]) for list index i,
+    so ray i has the pixel word i.  make_image is a capture-only stand-in: the
+    reference's own needs a square frame.  Returns the averaged colours."""
+    ref_main, ref_utils, ref_scene = import_reference()
+    rng = KeyedRNG(seed, ref_main.main.__code__)
+    ref_main.uniform = rng.uniform
+    ref_utils.uniform = rng.uniform
+    ref_main.Pool = make_sync_pool(ref_main, rng)
+    ref_main.tqdm = lambda it, *a, **k: it
+    origin = [float(v) for v in origin]
+    dirs = np.asarray(dirs, dtype=np.float64).reshape(-1, 3)
+
+    class RayScene(ref_scene.Scene):
+        def __init__(self, path):
+            super().__init__(path)
+            self.eye = list(origin)
+            self.width, self.height = len(dirs), 1
+
+    def rays_of(start_pt, pts):
+        assert len(pts) == len(dirs)
+        return [(np.array(origin), np.array(d)) for d in dirs]
+
+    captured = {}
+
+    def capture(x1, y1, x2, y2, w, h, intersections):
+        captured["colors"] = np.array([np.asarray(c, dtype=np.float64) for c, _ in intersections])
+
+    saved = ref_main.Scene, ref_main.make_rays, ref_main.make_image
+    ref_main.Scene, ref_main.make_rays, ref_main.make_image = RayScene, rays_of, capture
+    argv = sys.argv
+    sys.argv = ["main.py", scene or SCENE, "-r", str(spp), "-b", str(bounces)]
+    try:
+        with contextlib.redirect_stdout(io.StringIO()), np.errstate(all="ignore"):
+            ref_main.main()
+    finally:
+        sys.argv = argv
+        ref_main.Scene, ref_main.make_rays, ref_main.make_image = saved
+    return captured["colors"]
+
+
+def gen_rays():
+    """The reference on rays of any direction (tests/rays_any_ref.py GOLDENS):
+    rays_<scene>_<camera>.npz with o, d, keys and the averaged colours."""
+    import tempfile
+    sys.path.insert(0, os.path.dirname(HERE))
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    import mesh_scene as ms
+    import rays_any_ref as ra
+    spp, B, seed = ra.GOLDEN_FRAME
+    for name, scene, camera in ra.GOLDENS:
+        sdl = None
+        if scene == "mesh":
+            sdl = ms.write_mesh_scene(tempfile.mkdtemp(prefix="pt_rays_"), os.path.join(REF, "objs"))
+        o, d = ra.golden_rays(camera)
+        colors = render_reference_rays(o, d, spp, B, seed, scene=sdl)
+        assert colors.shape == (len(d), 3) and np.isfinite(colors).all()
+        save_npz_fixed(os.path.join(HERE, name), o=np.broadcast_to(o, d.shape).copy(), d=d,
+                       keys=np.arange(len(d), dtype=np.uint32), spp=spp, bounces=B, seed=seed, colors=colors)
+        print("wrote", name, colors.shape, int((colors == 0).all(axis=1).sum()), "escapes",
+              float(colors.min()), float(colors.max()))
+
+
 def gen_scene():
     """Scene dump: what scene_reader.Scene produces (scene_reader.py:49-188)."""
     _, _, ref_scene = import_reference()
@@ -568,6 +638,8 @@ if __name__ == "__main__":
         gen_scene_goldens()
     if what in ("all", "materials"):
         gen_materials()
+    if what in ("all", "rays"):
+        gen_rays()
     if what == "render":
         gen_render(*[int(x) for x in sys.argv[2:7]])
     if what == "all":

@@ -56,29 +56,43 @@ def aimed_batch(pk, tail_seed=7):
 
 
 class Batch:
-    """A scene's 192 records, its ray box, the oracle's samples (lazily, per
-    Russian-roulette depth) and the simulated runs."""
+    """A scene's records, their ray box, the oracle's samples (lazily, per
+    Russian-roulette depth) and the simulated runs.  By default the 192 records
+    of aimed_batch with rays_ref.ray_samples as the source of the samples;
+    `records` = (o, d, keys, box) and `source` = f(rr_depth, ns) -> [ns, n, 3]
+    give any other records and reference (tests/rays_any_ref.py: rays that
+    cross no screen plane, through oracle.radiance)."""
 
-    def __init__(self, scene):
+    def __init__(self, scene, records=None, source=None):
         from pathtracerpython_amd.pack import pack_scene
         self.scene = scene
         self.pk = pack_scene(scene)
-        self.o, self.p, self.d, self.keys = aimed_batch(self.pk)
-        inb = ~np.all(self.o == np.array(rays_ref.OFF_AXIS[1]), axis=1)
-        self.box = np.concatenate([self.o[inb].min(axis=0), self.o[inb].max(axis=0)])
-        self.outside = ~inb
+        if records is None:
+            self.o, self.p, self.d, self.keys = aimed_batch(self.pk)
+            inb = ~np.all(self.o == np.array(rays_ref.OFF_AXIS[1]), axis=1)
+            self.box = np.concatenate([self.o[inb].min(axis=0), self.o[inb].max(axis=0)])
+            self.outside = ~inb
+        else:
+            assert source is not None
+            self.o, self.d, self.keys, self.box = records
+            self.p = None
+            self.outside = ~np.all((self.o >= self.box[:3]) & (self.o <= self.box[3:]), axis=1)
+        self.source = source
         self.n = len(self.o)
         self._samples = {}
         self._sim = {}
 
     def samples(self, rr_depth=None, ns=MAX_SPP):
-        """[ns, 192, 3]: the oracle's colour of samples 0 .. ns-1 of every record."""
+        """[ns, n, 3]: the reference's colour of samples 0 .. ns-1 of every record."""
         from pathtracerpython_amd._abi import PT_FLAG_RR
         key = (rr_depth, ns)
         if key not in self._samples:
-            self._samples[key] = rays_ref.ray_samples(
-                self.scene, self.o, self.p, self.keys, BOUNCES, SEED, ns,
-                flags=0 if rr_depth is None else PT_FLAG_RR, rr_depth=3 if rr_depth is None else rr_depth)
+            if self.source is not None:
+                self._samples[key] = self.source(rr_depth, ns)
+            else:
+                self._samples[key] = rays_ref.ray_samples(
+                    self.scene, self.o, self.p, self.keys, BOUNCES, SEED, ns,
+                    flags=0 if rr_depth is None else PT_FLAG_RR, rr_depth=3 if rr_depth is None else rr_depth)
         return self._samples[key]
 
     def simulate(self, rule, rr_depth=None):
