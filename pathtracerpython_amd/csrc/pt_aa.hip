@@ -122,15 +122,12 @@ __global__ __launch_bounds__(kRenderBlock, PT_RENDER_WAVES) void k_render_list_a
 
 void pt_aa_render(bool f64, bool bvh, dim3 grid, hipStream_t st, const SceneK& S, const RenderK& R, void* out) {
     const dim3 block(kRenderBlock);
-    if (f64) hipLaunchKernelGGL((k_render_aa<true, true>), grid, block, 0, st, S, R, out);
-    else if (bvh) hipLaunchKernelGGL((k_render_aa<false, true>), grid, block, 0, st, S, R, out);
-    else hipLaunchKernelGGL((k_render_aa<false, false>), grid, block, 0, st, S, R, out);
+    hipLaunchKernelGGL(PT_KERNEL_F64_BVH(f64, bvh, k_render_aa), grid, block, 0, st, S, R, out);
 }
 
 void pt_aa_render_list(bool f64, bool bvh, dim3 grid, hipStream_t st, const SceneK& S, const ListK& R,
                        const uint32_t* list, double* accS, double* accQ, uint32_t* accN) {
     const dim3 block(kRenderBlock);
-    if (f64) hipLaunchKernelGGL((k_render_list_aa<true, true>), grid, block, 0, st, S, R, list, accS, accQ, accN);
-    else if (bvh) hipLaunchKernelGGL((k_render_list_aa<false, true>), grid, block, 0, st, S, R, list, accS, accQ, accN);
-    else hipLaunchKernelGGL((k_render_list_aa<false, false>), grid, block, 0, st, S, R, list, accS, accQ, accN);
+    hipLaunchKernelGGL(PT_KERNEL_F64_BVH(f64, bvh, k_render_list_aa), grid, block, 0, st, S, R, list, accS, accQ,
+                       accN);
 }

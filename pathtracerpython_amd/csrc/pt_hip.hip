@@ -33,6 +33,7 @@ static int fail(int code, const std::string& msg) {
     g_err = msg;
     return code;
 }
+#define RCCHK(expr) do { const int rc_ = (expr); if (rc_) return rc_; } while (0)   // a callee's error is ours
 #define HIPCHK(expr)                                                              \
     do {                                                                          \
         hipError_t e_ = (expr);                                                   \
@@ -43,6 +44,7 @@ static int fail(int code, const std::string& msg) {
 // ------------------------------------------------------------- kernels --
 // k_render and its launch records: pt_render.h
 #include "pt_render.h"
+#include "pt_plan.h"   // the launch rules, without the HIP runtime
 #include "pt_aa.h"   // the antialiasing kernels' launchers (pt_aa.hip)
 #include "pt_lens.h" // the thin-lens kernels' launchers (pt_lens.hip)
 #include "pt_rays.h" // the ray kernel's launcher (pt_rays.hip)
@@ -729,8 +731,8 @@ __global__ __launch_bounds__(256) void k_color(SceneK S, const int32_t* __restri
 }
 
 // ------------------------------- wavefront, list form (pt_accum) --
-// The list form of the wavefront render (BVH scenes, render_wavefront with a
-// WfList): k_wf_shade_list (pt_shade.h) for k_wf_shade, and the two kernels
+// The list form of the wavefront render (BVH scenes, render_wavefront from
+// pt_accum_render_stats): k_wf_shade_list (pt_shade.h) for k_wf_shade, and the two kernels
 // below for k_wf_primary and k_wf_final; the walk kernels and the sort only
 // see the path slots, the query records and the lists.
 // The primary rays, one work-item per list entry (the entry's `split` slots
@@ -1065,123 +1067,27 @@ int pt_band_rows(const pt_render_params* p, int32_t* rows) {
     return PT_OK;
 }
 
-constexpr uint32_t kKnownFlags = PT_FLAG_RR | PT_FLAG_FORCE_F64 | PT_FLAG_COUNT | PT_FLAG_OUT_F64 |
-                                 PT_FLAG_MEGAKERNEL | PT_FLAG_WALK_COUNT | PT_FLAG_KERNEL_TIMES |
-                                 PT_FLAG_AA | PT_FLAG_LENS;
-static const char kLensNoCount[] = "PT_FLAG_LENS does not combine with PT_FLAG_COUNT, PT_FLAG_WALK_COUNT or "
-                                   "PT_FLAG_KERNEL_TIMES: the lens kernels do not count";
-static const char kLensNoScene[] = "PT_FLAG_LENS needs a scene created with a lens (pt_scene_create_lens)";
-static const char kAaNoCount[] = "PT_FLAG_AA does not combine with PT_FLAG_COUNT, PT_FLAG_WALK_COUNT or "
-                                 "PT_FLAG_KERNEL_TIMES: the antialiasing kernels do not count";
-// An antialiased launch that takes the single kernel (pt_aa.hip) has nothing
-// to fill pt_stats with; through the wavefront kernels the walk counts and the
-// kernel times are a centre-ray launch's.
-static bool aa_stats_refused(uint32_t flags) {
-    return (flags & PT_FLAG_AA) && (flags & (PT_FLAG_WALK_COUNT | PT_FLAG_KERNEL_TIMES));
+// The launch rules — the argument checks, the lanes per pixel (choose_split),
+// the launch records, the work-items and the route — are pt_plan.h's; here
+// they meet the handles.  PLANCHK: a check's message is a PT_EINVAL.
+#define PLANCHK(expr) do { const std::string m_ = (expr); if (!m_.empty()) return fail(PT_EINVAL, m_); } while (0)
+static PlanScene plan_scene(const pt_scene* s) {
+    return PlanScene{s->dev.n_bnode > 0, s->dev.n_qnode > 0 && s->dev.qstack <= kWalkStack, s->n_cu, s->has_lens,
+                     s->host.frame_x};
 }
-// What the scene and the flags alone say about the path: false — the launch
-// takes the single kernel whatever its size (pt_render_device's condition
-// without the slot count).
-static bool wf_scene_ok(const pt_scene* s, uint32_t flags) {
-    return s->dev.n_bnode > 0 &&
-           !(flags & (PT_FLAG_COUNT | PT_FLAG_FORCE_F64 | PT_FLAG_MEGAKERNEL)) &&
-           s->dev.n_qnode > 0 && s->dev.qstack <= kWalkStack;
-}
-// (PT_FLAG_LENS does not decide it: the lens has its wavefront form,
-// pt_shade_lens.hip.)
-// This launch takes the wavefront kernels: BVH scenes, unless the caller asks
-// for the single kernel, or for counting / forced f64, which only the single
-// kernel implements (wf_scene_ok), or the launch has 2^29 or more path slots,
-// beyond the shadow lists' (slot << 2) | ray entries.  The single kernel's
-// result is the same bit for bit.
-static bool wf_route(const pt_scene* s, uint32_t flags, uint64_t slots) {
-    return wf_scene_ok(s, flags) && slots < ((uint64_t)1 << 29);
-}
-static int validate(const pt_render_params* p) {
-    if (!p) return fail(PT_EINVAL, "null params");
-    if (p->width <= 0 || p->height <= 0) return fail(PT_EINVAL, "width/height must be > 0");
-    // pixel keys k = ix*H + iy and the launch's pixel counts are 32-bit
-    if ((int64_t)p->width * p->height >= (int64_t)1 << 32) return fail(PT_EINVAL, "image too large for 32-bit pixel keys");
-    if (p->spp <= 0) return fail(PT_EINVAL, "spp must be > 0");
-    if (p->bounces < 0) return fail(PT_EINVAL, "bounces must be >= 0");
-    if (p->sample_begin < 0) return fail(PT_EINVAL, "sample_begin must be >= 0");
-    if (p->row_step <= 0 || p->row_phase < 0 || p->row_phase >= p->row_step)
-        return fail(PT_EINVAL, "need row_step > 0 and 0 <= row_phase < row_step");
-    if (p->flags & ~kKnownFlags)
-        return fail(PT_EINVAL, "unknown flag bits (bit 7, v4's PT_FLAG_TREE_WALK, is retired)");
-    // (with PT_FLAG_WALK_COUNT / PT_FLAG_KERNEL_TIMES: aa_stats_refused, once the launch's path is known)
-    if ((p->flags & PT_FLAG_LENS) && (p->flags & (PT_FLAG_COUNT | PT_FLAG_WALK_COUNT | PT_FLAG_KERNEL_TIMES)))
-        return fail(PT_EINVAL, kLensNoCount);
-    if ((p->flags & PT_FLAG_AA) && (p->flags & PT_FLAG_COUNT)) return fail(PT_EINVAL, kAaNoCount);
-    if (p->out_row_stride != 0 && (int64_t)p->out_row_stride < (int64_t)p->width * 3)
-        return fail(PT_EINVAL, "out_row_stride must be 0 or >= width*3");
-    if (p->lanes_per_pixel != 0) {
-        uint32_t cap = 64;
-        while (cap > 1 && (int32_t)cap > p->spp) cap >>= 1;
-        const int32_t l = p->lanes_per_pixel;
-        if (l < 0 || (l & (l - 1)) != 0 || l > (int32_t)cap)
-            return fail(PT_EINVAL, "lanes_per_pixel must be 0 or a power of two <= min(64, spp)");
-    }
+// Launches on one handle share its scratch (wavefront state, counters,
+// events): every launch is ordered after the previous one, whatever stream
+// that one ran on, and bracketed by ev0 / ev1 (pt_last_kernel_ms).
+static int launch_begin(pt_scene* s, hipStream_t st) {
+    if (s->timed) HIPCHK(hipStreamWaitEvent(st, s->ev1, 0));
+    HIPCHK(hipEventRecord(s->ev0, st));
     return PT_OK;
 }
-
-// Lanes (wavefront: path slots) per pixel: a power of two <= min(64, spp).
-//
-// Single kernel (scenes without a BVH): >= 8 samples per lane where the
-// launch is large (K2 512^2 x 64 spp: 8 lanes per pixel; K3 and K4: 64), at
-// most 2^30 lanes over the full image — but at least `min_lanes` lanes in the
-// launch, i.e. ~4 dispatch rounds of the device's resident waves (n_cu x 4
-// SIMDs x 4 waves x 64 lanes x 4 rounds = 2^20 on MI355X).  A launch of one
-// round is as long as its slowest wave (~0.7 ms at K2) however little work
-// the band holds: one rank's band of an N-GPU strong-scaling split of the K2
-// frame, per-band kernel ms at 8 / 16 / 32 / 64 lanes per
-// pixel: N=4 1.592 / 1.450 / 1.480 / 1.566, N=8 0.882 / 0.816 / 0.767 / 0.809
-// (N=1 5.584 / 5.674 / 5.792 / 6.136: each lane traces its pixel's primary
-// ray once).  A pixel's samples are summed in an order that depends on its
-// lane count, so bands of different sizes round differently in the last
-// bits (all within 1e-12 of the oracle); bands of equal launch size agree bit
-// for bit.
-// Wavefront (BVH scenes): path slots hold ~420 B of state each, so at most
-// 64M slots (28 GB) over the full image (K5 512^2 x 64 spp: 2M slots 161.6
-// ms, 4M 147.1, 8M 140.5, 16M 139.3 (round 1); 1024^2 x 256 spp with the
-// one-ray walks: 16M 1419 ms, 32M 1392, 64M 1378 — fewer shade / walk steps,
-// each with its drain); an N-way band gets 1/N of them.  The single kernel
-// uses the same split on BVH scenes (min_lanes does not apply), so its
-// framebuffer stays bitwise equal to the wavefront one.
-//
-// PT_SPLIT_FIXED (compile-time, tuning builds only) pins the split.
-// PT_MIN_SPL: samples per lane the whole-image split keeps at least (round 6:
-// 4, i.e. 16 lanes per pixel at K2 — 4.669-4.693 vs 4.741-4.744 ms at 8 samples
-// per lane; round 5's kernel was flat between 8 and 16 lanes)
-#ifndef PT_MIN_SPL
-#define PT_MIN_SPL 4
-#endif
-static uint32_t choose_split(uint64_t image_pixels, uint64_t launch_pixels, int32_t spp, bool bvh,
-                             uint64_t min_lanes) {
-    uint32_t cap = 64;
-    while (cap > 1 && (int32_t)cap > spp) cap >>= 1;
-#ifdef PT_SPLIT_FIXED
-    uint32_t f = 1;
-    while (f * 2 <= (uint32_t)PT_SPLIT_FIXED && f * 2 <= cap) f *= 2;
-    (void)image_pixels; (void)launch_pixels; (void)bvh; (void)min_lanes;
-    return f;
-#else
-    uint32_t s = 1;
-    const uint64_t target = (uint64_t)1 << (bvh ? 26 : 30);
-    while (s < cap && image_pixels * s * 2 <= target && (bvh || spp / (int32_t)(s * 2) >= PT_MIN_SPL)) s *= 2;
-    if (!bvh)
-        while (s < cap && launch_pixels * s < min_lanes) s *= 2;
-    return s;
-#endif
-}
-// lanes of a single-kernel launch below which it gets more lanes per pixel:
-// PT_MIN_ROUNDS dispatch rounds of the device's resident waves (4 per SIMD,
-// k_render's __launch_bounds__)
-#ifndef PT_MIN_ROUNDS
-#define PT_MIN_ROUNDS 4
-#endif
-static uint64_t min_lanes_of(int n_cu) {
-    return (uint64_t)n_cu * 4u * (uint64_t)PT_RENDER_WAVES * 64u * (uint64_t)PT_MIN_ROUNDS;
+static int launch_end(pt_scene* s, hipStream_t st) {
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(s->ev1, st));
+    s->timed = true;
+    return PT_OK;
 }
 
 // Walk kernels: node-phase exit threshold (lanes still descending) and
@@ -1216,20 +1122,7 @@ static uint64_t min_lanes_of(int n_cu) {
 // launch over the path slots, then the two persistent walk launches over the
 // queries it appended.  A slot runs at most n_samples x bounces bounces plus
 // the primary ray, so that many steps (+1 to finish the last bounce) drain
-// every slot; steps after that would find no work.  An antialiased launch
-// (PT_FLAG_AA in `flags`) has no shared primary query: k_wf_shade_aa starts a
-// query per sample, so a sample takes bounces + 1 steps, step 0's closest
-// walk is over the slots' own records, and CQP stays unused.  A thin-lens
-// launch (PT_FLAG_LENS) is of that form with or without PT_FLAG_AA — every
-// sample has its own origin — through the kernels of pt_shade_lens.hip.
-//
-// The list form (L, an accumulator pass: pt_accum_render): the same loop over
-// the slots of the active list's entries, with the list kernels for the
-// shade, primary and final steps and the slots' moment home [6][slots] beside
-// the path records.  The host knows the pass's smallest k only, so the steps
-// come from the largest k the rule allows.  Every pass initialises every slot
-// it launches (k_wf_shade_list's step 0): s->wf holds whatever the previous
-// pass or render left.
+// every slot; steps after that would find no work.
 // The walk launches: the <UC, COUNT> instantiation for a scene whose BVH units
 // have the 64-B form (SceneK::bunitc) and for a PT_FLAG_WALK_COUNT launch.
 static void launch_wf_closest(bool uc, bool count, unsigned blocks, hipStream_t on, const SceneK& S, WfPath* W,
@@ -1247,36 +1140,29 @@ static void launch_wf_shadow(bool uc, bool count, unsigned blocks, hipStream_t o
                       : (count ? k_wf_shadow<false, true> : k_wf_shadow<false, false>);
     hipLaunchKernelGGL(k, dim3(blocks), dim3(256), 0, on, S, W, SQ, list, counters, PT_WF_THR_SHADOW, wc, ovf);
 }
-struct WfList {
-    ListK R;
-    const uint32_t* list;
-    double *S, *Q;
-    uint32_t* n;
-    int32_t max_k;   // the most samples the pass adds to a pixel
+}  // extern "C"
+
+// What the loop reads of a pass.  Its three launches (the shade step, step 0's
+// primary queries where the slots do not start their own, the final reduction)
+// come from the caller, who knows the form (pt_render_device, pt_radiance_device,
+// pt_accum_render_stats); each is called with the launch's buffers (B below).
+struct WfPass {
+    uint32_t n_prim;       // primary queries (one per pixel / list entry / record)
+    uint32_t split_log2;   // slots per query
+    int32_t max_k;         // the most samples the pass adds to a query
+    int32_t bounces;
+    bool own;              // a primary query per sample, in the slots' own records: no primary launch
+    bool moments;          // the slots' moment home [6][slots]
 };
-// The ray form (Y, pt_radiance_device): the same loop over the slots of the
-// batch's records — a centre-ray launch with the record in the place of the
-// pixel — through the kernels of pt_shade_rays.hip for the shade, primary and
-// final steps; with S and Q the slots' moment home as in the list form.
-// Bytes in s->wf: ~440 per slot (WfPath 256, WfShadowQ 96, WfClosestQ 48, the
-// lists, keys and sorted list 34), + 48 with S and Q, and 48 per record.
-struct WfRayBatch {
-    RaysK R;
-    const RayK* rays;
-    double *S, *Q;   // both or neither
-};
-static int render_wavefront(pt_scene* s, const RenderK& R, const WfList* L, dim3 grid, void* out_dev,
-                            hipStream_t st, uint32_t flags, pt_stats* stats, const WfRayBatch* Y = nullptr) {
+template <class Shade, class Primary, class Finish>
+static int render_wavefront(pt_scene* s, const WfPass& P, dim3 grid, hipStream_t st, uint32_t flags, pt_stats* stats,
+                            const Shade& shade, const Primary& primary, const Finish& finish) {
     const size_t slots = (size_t)grid.x * 256;
-    // primary queries (one per pixel / list entry / record), slots per query, samples per slot
-    const uint32_t n_prim = Y ? Y->R.n_rays : L ? L->R.n_list : R.npix;
-    const uint32_t split_log2 = Y ? Y->R.split_log2 : L ? L->R.split_log2 : R.split_log2;
+    const uint32_t n_prim = P.n_prim, split_log2 = P.split_log2;
     const int32_t split = (int32_t)(1u << split_log2);
-    const int32_t per_slot = ((Y ? Y->R.spp : L ? L->max_k : R.spp) + split - 1) / split;
-    const bool aa = (flags & PT_FLAG_AA) != 0, lens = (flags & PT_FLAG_LENS) != 0;
-    const bool own = aa || lens;   // a primary query per sample, in the slots' own records
-    const int32_t steps = per_slot * ((Y ? Y->R.bounces : L ? L->R.bounces : R.bounces) + (own ? 1 : 0)) + 2;
-    const bool moments = L || (Y && Y->S);   // the slots' moment home [6][slots]
+    const int32_t per_slot = (P.max_k + split - 1) / split;   // samples per slot
+    const bool own = P.own, moments = P.moments;
+    const int32_t steps = per_slot * (P.bounces + (own ? 1 : 0)) + 2;
     const unsigned sh_blocks =
         std::max(1u, std::min<unsigned>(grid.x, (unsigned)PT_WF_SHADOW_BLOCKS_PER_CU * (unsigned)s->n_cu));
     const unsigned cl_blocks =
@@ -1296,6 +1182,8 @@ static int render_wavefront(pt_scene* s, const RenderK& R, const WfList* L, dim3
         uint32_t *bin_hist, *bin_rowsum, *bin_base;   // the sort's count matrix (its rows' prefix sums in
                                                       // place), the row totals and their scan
         double* home;                // the moment home [6][slots] (the list form; rays with S, Q)
+        uint32_t slots;              // (for the pass's launches)
+        int32_t* closest_list;       // the closest list: lists + 3 slots
     } B;
     auto carve = [&](char* base) -> size_t {   // returns the bytes carved
         Bump m{base};
@@ -1331,7 +1219,8 @@ static int render_wavefront(pt_scene* s, const RenderK& R, const WfList* L, dim3
         HIPCHK(hipEventCreateWithFlags(&s->wf_ev_walk, hipEventDisableTiming));
     }
     carve((char*)s->wf);
-    int32_t* const closest_list = B.lists + 3 * slots;
+    int32_t* const closest_list = B.closest_list = B.lists + 3 * slots;
+    B.slots = (uint32_t)slots;
     bool sorted = false;   // this step's shadow list is in lists_o
     auto bin_sort = [&]() -> hipError_t {   // (the device reads the list's length: no host wait)
         hipLaunchKernelGGL(k_bin_hist, dim3(kBinBlocks), dim3(256), 0, st, (const uint16_t*)B.keys,
@@ -1348,7 +1237,6 @@ static int render_wavefront(pt_scene* s, const RenderK& R, const WfList* L, dim3
     const bool wcount = (flags & PT_FLAG_WALK_COUNT) != 0 && stats;
     const bool times = (flags & PT_FLAG_KERNEL_TIMES) != 0 && stats;
     unsigned long long* wc = (unsigned long long*)s->stats;   // [0..2] shadow, [3..5] closest
-    if (wcount) HIPCHK(hipMemsetAsync(s->stats, 0, sizeof(StatsDev), st));
     // per-kernel HIP events (PT_FLAG_KERNEL_TIMES): shade, shadow, closest, the
     // shadow list's sort x (start, end) per step
     constexpr int kEv = 8;
@@ -1363,46 +1251,15 @@ static int render_wavefront(pt_scene* s, const RenderK& R, const WfList* L, dim3
     auto mark = [&](int32_t step, int k, int end, hipStream_t on) -> hipError_t {
         return times ? hipEventRecord(s->prof_ev[(size_t)step * kEv + k * 2 + end], on) : hipSuccess;
     };
+    RCCHK(launch_begin(s, st));
+    if (wcount) HIPCHK(hipMemsetAsync(s->stats, 0, sizeof(StatsDev), st));
     s->last = pt_launch_info{PT_PATH_WAVEFRONT, steps, split, flags};
-    HIPCHK(hipEventRecord(s->ev0, st));
     for (int32_t step = 0; step < steps; ++step) {
         HIPCHK(hipMemsetAsync(B.counters, 0, 4 * sizeof(int32_t), st));
         HIPCHK(mark(step, 0, 0, st));
         const dim3 sgrid((unsigned)((slots + kShadeBlock - 1) / kShadeBlock)), pgrid((n_prim + 255) / 256);
-        if (Y) {   // (a record per entry; pt_radiance_device: no AA, lens or stats flags)
-            pt_wf_shade_rays(sgrid, st, s->dev, Y->R, step, Y->rays, B.W, B.SQ, B.CQ, (const WfClosestQ*)B.CQP,
-                             B.lists, B.counters, (uint32_t)slots, B.keys, moments ? B.home : nullptr);
-            if (step == 0)
-                pt_wf_primary_rays(pgrid, st, s->dev, Y->R, Y->rays, B.W, B.CQP, closest_list, B.counters + 2);
-        } else if (lens) {   // (a lens point per sample; validate: never with the stats flags)
-            if (L)
-                pt_wf_shade_list_lens(aa, sgrid, st, s->dev, L->R, step, L->list, (const uint32_t*)L->n, B.W, B.SQ,
-                                      B.CQ, B.lists, B.counters, (uint32_t)slots, B.keys, B.home);
-            else
-                pt_wf_shade_lens(aa, sgrid, st, s->dev, R, step, B.W, B.SQ, B.CQ, B.lists, B.counters,
-                                 (uint32_t)slots, B.keys);
-        } else if (aa) {   // (the slots start their own primary queries)
-            if (L)
-                hipLaunchKernelGGL(k_wf_shade_list_aa, sgrid, dim3(kShadeBlock), 0, st, s->dev, L->R, step,
-                                   L->list, (const uint32_t*)L->n, B.W, B.SQ, B.CQ, B.lists, B.counters,
-                                   (uint32_t)slots, B.keys, B.home);
-            else
-                hipLaunchKernelGGL(k_wf_shade_aa, sgrid, dim3(kShadeBlock), 0, st, s->dev, R, step, B.W, B.SQ,
-                                   B.CQ, B.lists, B.counters, (uint32_t)slots, B.keys);
-        } else if (L) {
-            hipLaunchKernelGGL(k_wf_shade_list, sgrid, dim3(kShadeBlock), 0, st, s->dev, L->R, step, L->list,
-                               (const uint32_t*)L->n, B.W, B.SQ, B.CQ, (const WfClosestQ*)B.CQP, B.lists,
-                               B.counters, (uint32_t)slots, B.keys, B.home);
-            if (step == 0)
-                hipLaunchKernelGGL(k_wf_primary_list, pgrid, dim3(256), 0, st, s->dev, L->R, L->list,
-                                   (const uint32_t*)L->n, B.W, B.CQP, closest_list, B.counters + 2);
-        } else {
-            hipLaunchKernelGGL(k_wf_shade, sgrid, dim3(kShadeBlock), 0, st, s->dev, R, step, B.W, B.SQ, B.CQ,
-                               (const WfClosestQ*)B.CQP, B.lists, B.counters, (uint32_t)slots, B.keys);
-            if (step == 0)
-                hipLaunchKernelGGL(k_wf_primary, pgrid, dim3(256), 0, st, s->dev, R, B.W, B.CQP, closest_list,
-                                   B.counters + 2);
-        }
+        shade(B, step, sgrid);
+        if (step == 0 && !own) primary(B, pgrid);
         HIPCHK(mark(step, 0, 1, st));
         sorted = false;
         if (step + 1 < steps) {
@@ -1439,17 +1296,8 @@ static int render_wavefront(pt_scene* s, const RenderK& R, const WfList* L, dim3
             if (side) HIPCHK(hipStreamWaitEvent(st, s->wf_ev_walk, 0));
         }
     }
-    if (Y)
-        pt_wf_final_rays(grid, st, Y->R, (const WfPath*)B.W, moments ? (const double*)B.home : nullptr,
-                         (uint32_t)slots, out_dev, Y->S, Y->Q);
-    else if (L)
-        hipLaunchKernelGGL(k_wf_final_list, grid, dim3(256), 0, st, L->R, L->list, (const double*)B.home,
-                           (uint32_t)slots, L->S, L->Q, L->n);
-    else
-        hipLaunchKernelGGL(k_wf_final, grid, dim3(256), 0, st, s->dev, R, (const WfPath*)B.W, out_dev);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(s->ev1, st));
-    s->timed = true;
+    finish(B);
+    RCCHK(launch_end(s, st));
     if (stats) {
         memset(stats, 0, sizeof(*stats));
         if (wcount || times) HIPCHK(hipStreamSynchronize(st));
@@ -1484,13 +1332,14 @@ static int render_wavefront(pt_scene* s, const RenderK& R, const WfList* L, dim3
     return PT_OK;
 }
 
+extern "C" {
+
 int pt_render_device(pt_scene* s, const pt_render_params* p, void* out_dev, void* stream,
                      pt_stats* stats) {
-    int rc = validate(p);
-    if (rc) return rc;
+    PLANCHK(validate(p));
     if (!s) return fail(PT_EINVAL, "null scene");
-    if ((p->flags & PT_FLAG_LENS) && !s->has_lens) return fail(PT_EINVAL, kLensNoScene);
-    if (aa_stats_refused(p->flags) && !wf_scene_ok(s, p->flags)) return fail(PT_EINVAL, kAaNoCount);
+    const PlanScene ps = plan_scene(s);
+    PLANCHK(check_scene(p->flags, ps));
     int32_t first = 0, rows = 0;
     band_layout(p, &first, &rows);
     if (rows == 0) return PT_OK;
@@ -1498,87 +1347,56 @@ int pt_render_device(pt_scene* s, const pt_render_params* p, void* out_dev, void
     DeviceGuard g(s->device);
     hipStream_t st = (hipStream_t)stream;
     RenderK R;
-    R.W = p->width; R.H = p->height; R.spp = p->spp; R.bounces = p->bounces;
-    R.seed = p->seed;
-    R.rr_depth = (p->flags & PT_FLAG_RR) ? std::max(0, p->rr_depth) : -1;
-    R.first_row = first; R.row_step = p->row_step; R.n_rows = rows;
-    R.sample_begin = p->sample_begin;
-    R.out_f64 = (p->flags & PT_FLAG_OUT_F64) ? 1 : 0;
-    R.npix = (uint32_t)rows * (uint32_t)p->width;
-    R.out_stride = p->out_row_stride ? (uint32_t)p->out_row_stride : (uint32_t)p->width * 3u;
-    R.split = p->lanes_per_pixel > 0
-                  ? (uint32_t)p->lanes_per_pixel
-                  : choose_split((uint64_t)p->width * (uint64_t)p->height, (uint64_t)R.npix, p->spp,
-                                 s->dev.n_bnode > 0, min_lanes_of(s->n_cu));
-    R.split_log2 = log2_ceil(R.split);
-    R.tail_pix = R.npix;
-    R.tail_lane = R.npix * R.split;
-    R.tail_log2 = R.split_log2;
-    if (s->dev.n_bnode == 0) {
-        // The launch drains for about one wave lifetime (~1 ms at K2: 7% of
-        // its wave-slots idle).  The image's top sixteenth of
-        // rows (iy >= H - ceil(H/16), dispatched last, also in every
-        // interleaved band) gets 8x the lanes per pixel, so the last dispatch
-        // round is short waves.  K2 6.70 -> 6.49 ms; sixteenth / eighth /
-        // quarter of the rows at 2x / 4x / 8x lanes all land within 6.49-6.54.
-#ifndef PT_TAIL_FRAC
-#define PT_TAIL_FRAC 16
-#endif
-#ifndef PT_TAIL_MUL
-#define PT_TAIL_MUL 3
-#endif
-        constexpr int kTailFrac = PT_TAIL_FRAC;
-        constexpr uint32_t kTailMul = PT_TAIL_MUL;   // log2 of the lane multiplier
-        uint32_t cap = 64;
-        while (cap > 1 && (int32_t)cap > p->spp) cap >>= 1;
-        const uint32_t tl = std::min(R.split_log2 + kTailMul, (uint32_t)__builtin_ctz(cap));
-        const int32_t thresh = p->height - (p->height + kTailFrac - 1) / kTailFrac;
-        int32_t ra = 0;   // band rows below the threshold (a prefix: rows ascend)
-        while (ra < rows && first + ra * p->row_step < thresh) ++ra;
-        // (no tail when this launch's lanes would overflow the 32-bit lane index)
-        const uint64_t lanes = (uint64_t)ra * p->width * R.split + 64 +
-                               (((uint64_t)(rows - ra) * (uint64_t)p->width) << tl);
-        if (tl > R.split_log2 && ra < rows && lanes < ((uint64_t)1 << 32)) {
-            R.tail_pix = (uint32_t)ra * (uint32_t)p->width;
-            R.tail_lane = (R.tail_pix * R.split + 63u) & ~63u;
-            R.tail_log2 = tl;
-        }
-    }
-    const uint64_t threads = (uint64_t)R.tail_lane + ((uint64_t)(R.npix - R.tail_pix) << R.tail_log2);
-    if ((uint64_t)R.npix * R.split >= ((uint64_t)1 << 32) || threads >= ((uint64_t)1 << 32))
-        return fail(PT_EINVAL, "launch needs 2^32 or more work-items (32-bit lane index)");
-    // launches on one handle share its scratch (wavefront state, counters,
-    // events): order this one after the previous launch, whatever stream
-    // that one ran on
-    if (s->timed) HIPCHK(hipStreamWaitEvent(st, s->ev1, 0));
-    const dim3 grid((unsigned)((threads + 255) / 256));   // (the wavefront's slots)
-    const dim3 rgrid((unsigned)((threads + kRenderBlock - 1) / kRenderBlock)), rblock(kRenderBlock);
+    LaunchPlan L;
+    PLANCHK(plan_frame(p, ps, first, rows, &R, &L));
     const bool count = (p->flags & PT_FLAG_COUNT) != 0;
-    const bool f64 = (p->flags & PT_FLAG_FORCE_F64) != 0;
-    const bool aa = (p->flags & PT_FLAG_AA) != 0;
-    if (wf_route(s, p->flags, (uint64_t)grid.x * 256u))
-        return render_wavefront(s, R, nullptr, grid, out_dev, st, p->flags, stats);
-    if (aa_stats_refused(p->flags)) return fail(PT_EINVAL, kAaNoCount);
-    if (count) HIPCHK(hipMemsetAsync(s->stats, 0, sizeof(StatsDev), st));
-    HIPCHK(hipEventRecord(s->ev0, st));
-    s->last = pt_launch_info{PT_PATH_SINGLE, 1, (int32_t)R.split, p->flags};
-    if (p->flags & PT_FLAG_LENS) {   // (validate: never with count)
-        pt_lens_render(f64, s->dev.n_bnode > 0, aa, rgrid, st, s->dev, R, out_dev);
-    } else if (aa) {   // (validate: never with count)
-        pt_aa_render(f64, s->dev.n_bnode > 0, rgrid, st, s->dev, R, out_dev);
-    } else if (f64) {
-        if (count) hipLaunchKernelGGL((k_render<true, true, true>), rgrid, rblock, 0, st, s->dev, R, out_dev, s->stats);
-        else hipLaunchKernelGGL((k_render<true, false, true>), rgrid, rblock, 0, st, s->dev, R, out_dev, s->stats);
-    } else if (s->dev.n_bnode > 0) {   // scenes with meshes: the BVH instantiation
-        if (count) hipLaunchKernelGGL((k_render<false, true, true>), rgrid, rblock, 0, st, s->dev, R, out_dev, s->stats);
-        else hipLaunchKernelGGL((k_render<false, false, true>), rgrid, rblock, 0, st, s->dev, R, out_dev, s->stats);
-    } else {
-        if (count) hipLaunchKernelGGL((k_render<false, true, false>), rgrid, rblock, 0, st, s->dev, R, out_dev, s->stats);
-        else hipLaunchKernelGGL((k_render<false, false, false>), rgrid, rblock, 0, st, s->dev, R, out_dev, s->stats);
+    const bool f64 = (p->flags & PT_FLAG_FORCE_F64) != 0, bvh = ps.bvh;
+    const bool aa = (p->flags & PT_FLAG_AA) != 0, lens = (p->flags & PT_FLAG_LENS) != 0;
+    if (L.wavefront) {
+        // The frame form of render_wavefront.  An antialiased launch has no
+        // shared primary query: k_wf_shade_aa starts a query per sample, so a
+        // sample takes bounces + 1 steps, step 0's closest walk is over the
+        // slots' own records, and CQP stays unused.  A thin-lens launch is of
+        // that form with or without PT_FLAG_AA — every sample has its own
+        // origin — through the kernels of pt_shade_lens.hip.
+        const dim3 grid((unsigned)L.wf_blocks);
+        const WfPass P{R.npix, R.split_log2, R.spp, R.bounces, aa || lens, false};
+        return render_wavefront(
+            s, P, grid, st, p->flags, stats,
+            [&](const auto& B, int32_t step, dim3 sgrid) {
+                if (lens)   // (a lens point per sample; validate: never with the stats flags)
+                    pt_wf_shade_lens(aa, sgrid, st, s->dev, R, step, B.W, B.SQ, B.CQ, B.lists, B.counters, B.slots,
+                                     B.keys);
+                else if (aa)   // (the slots start their own primary queries)
+                    hipLaunchKernelGGL(k_wf_shade_aa, sgrid, dim3(kShadeBlock), 0, st, s->dev, R, step, B.W, B.SQ,
+                                       B.CQ, B.lists, B.counters, B.slots, B.keys);
+                else
+                    hipLaunchKernelGGL(k_wf_shade, sgrid, dim3(kShadeBlock), 0, st, s->dev, R, step, B.W, B.SQ, B.CQ,
+                                       (const WfClosestQ*)B.CQP, B.lists, B.counters, B.slots, B.keys);
+            },
+            [&](const auto& B, dim3 pgrid) {
+                hipLaunchKernelGGL(k_wf_primary, pgrid, dim3(256), 0, st, s->dev, R, B.W, B.CQP, B.closest_list,
+                                   B.counters + 2);
+            },
+            [&](const auto& B) {
+                hipLaunchKernelGGL(k_wf_final, grid, dim3(256), 0, st, s->dev, R, (const WfPath*)B.W, out_dev);
+            });
     }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(s->ev1, st));
-    s->timed = true;
+    const dim3 rgrid((unsigned)L.blocks), rblock(kRenderBlock);
+    RCCHK(launch_begin(s, st));
+    if (count) HIPCHK(hipMemsetAsync(s->stats, 0, sizeof(StatsDev), st));
+    s->last = pt_launch_info{PT_PATH_SINGLE, 1, (int32_t)R.split, p->flags};
+    if (lens) {   // (validate: never with count)
+        pt_lens_render(f64, bvh, aa, rgrid, st, s->dev, R, out_dev);
+    } else if (aa) {   // (validate: never with count)
+        pt_aa_render(f64, bvh, rgrid, st, s->dev, R, out_dev);
+    } else {   // (forced f64, and scenes with meshes: the BVH instantiation)
+        const auto k = f64   ? (count ? k_render<true, true, true> : k_render<true, false, true>)
+                       : bvh ? (count ? k_render<false, true, true> : k_render<false, false, true>)
+                             : (count ? k_render<false, true, false> : k_render<false, false, false>);
+        hipLaunchKernelGGL(k, rgrid, rblock, 0, st, s->dev, R, out_dev, s->stats);
+    }
+    RCCHK(launch_end(s, st));
     if (stats) {
         memset(stats, 0, sizeof(*stats));
         if (count) {
@@ -1599,70 +1417,55 @@ int pt_render_device(pt_scene* s, const pt_render_params* p, void* out_dev, void
 }
 
 // pt_radiance (include/pt_capi.h): on a BVH scene the wavefront kernels'
-// ray form (render_wavefront with a WfRayBatch), by the frames' rule
-// (wf_route); else, or with PT_FLAG_RAYS_SINGLE, one launch of k_render_rays
-// (pt_rays.hip).  The lanes per record are chosen before the route, so both
-// paths deal a record's samples alike and agree bit for bit.
+// ray form, by the frames' rule (wf_route); else, or with
+// PT_FLAG_RAYS_SINGLE, one launch of k_render_rays (pt_rays.hip).
 static_assert(sizeof(pt_ray) == sizeof(RayK) && offsetof(pt_ray, d) == offsetof(RayK, d) &&
                   offsetof(pt_ray, key) == offsetof(RayK, key),
               "pt_ray is the kernels' RayK");
 int pt_radiance_device(pt_scene* s, const pt_ray* rays_dev, int64_t n_rays, const pt_render_params* p,
                        void* out_rgb_dev, double* out_S_dev, double* out_Q_dev, void* stream) {
-    if (!p) return fail(PT_EINVAL, "null params");
-    if (!s) return fail(PT_EINVAL, "null scene");
-    if (p->flags & ~(uint32_t)(PT_FLAG_RR | PT_FLAG_FORCE_F64 | PT_FLAG_OUT_F64 | PT_FLAG_RAYS_SINGLE))
-        return fail(PT_EINVAL, "unsupported flag bits: pt_radiance takes PT_FLAG_RR, PT_FLAG_FORCE_F64, "
-                               "PT_FLAG_OUT_F64 and PT_FLAG_RAYS_SINGLE only (the ray kernels do not count, jitter "
-                               "or draw a lens point)");
-    if (p->spp <= 0) return fail(PT_EINVAL, "spp must be > 0");
-    if (p->bounces < 0) return fail(PT_EINVAL, "bounces must be >= 0");
-    if (p->sample_begin < 0) return fail(PT_EINVAL, "sample_begin must be >= 0");
-    uint32_t cap = 64;
-    while (cap > 1 && (int32_t)cap > p->spp) cap >>= 1;
-    if (p->lanes_per_pixel != 0) {
-        const int32_t l = p->lanes_per_pixel;
-        if (l < 0 || (l & (l - 1)) != 0 || l > (int32_t)cap)
-            return fail(PT_EINVAL, "lanes_per_pixel must be 0 or a power of two <= min(64, spp)");
-    }
-    if (n_rays < 0 || n_rays >= ((int64_t)1 << 30)) return fail(PT_EINVAL, "need 0 <= n_rays < 2^30");
-    if ((out_S_dev == nullptr) != (out_Q_dev == nullptr)) return fail(PT_EINVAL, "out_S and out_Q: both or neither");
+    PLANCHK(check_rays(p, s != nullptr, n_rays, out_S_dev != nullptr, out_Q_dev != nullptr));
     if (n_rays == 0) return PT_OK;
     if (!rays_dev) return fail(PT_EINVAL, "null ray array");
     if (!out_rgb_dev) return fail(PT_EINVAL, "null output");
     DeviceGuard g(s->device);
     hipStream_t st = (hipStream_t)stream;
-    const bool bvh = s->dev.n_bnode > 0;
+    const PlanScene ps = plan_scene(s);
     RaysK R;
-    R.spp = p->spp; R.bounces = p->bounces;
-    R.seed = p->seed;
-    R.rr_depth = (p->flags & PT_FLAG_RR) ? std::max(0, p->rr_depth) : -1;
-    R.sample_begin = p->sample_begin;
-    R.n_rays = (uint32_t)n_rays;
-    R.out_f64 = (p->flags & PT_FLAG_OUT_F64) ? 1 : 0;
-    R.frame_x = s->host.frame_x;
-    // lanes per record: the rule of a launch of n_rays pixels
-    R.split = p->lanes_per_pixel > 0 ? (uint32_t)p->lanes_per_pixel
-                                     : choose_split((uint64_t)n_rays, (uint64_t)n_rays, p->spp, bvh,
-                                                    min_lanes_of(s->n_cu));
-    R.split_log2 = log2_ceil(R.split);
-    const uint64_t threads = (uint64_t)n_rays << R.split_log2;
-    if (threads >= ((uint64_t)1 << 32))
-        return fail(PT_EINVAL, "launch needs 2^32 or more work-items (32-bit lane index)");
-    if (s->timed) HIPCHK(hipStreamWaitEvent(st, s->ev1, 0));
-    const dim3 wgrid((unsigned)((threads + 255) / 256));   // (the wavefront's slots)
-    if (!(p->flags & PT_FLAG_RAYS_SINGLE) && wf_route(s, p->flags, (uint64_t)wgrid.x * 256u)) {
-        const WfRayBatch Y{R, (const RayK*)rays_dev, out_S_dev, out_Q_dev};
-        return render_wavefront(s, RenderK{}, nullptr, wgrid, out_rgb_dev, st, p->flags, nullptr, &Y);
+    LaunchPlan L;
+    PLANCHK(plan_rays(p, n_rays, ps, &R, &L));
+    const RayK* rays = (const RayK*)rays_dev;
+    if (L.wavefront) {
+        // The ray form of render_wavefront: the loop over the slots of the
+        // batch's records — a centre-ray launch with the record in the place
+        // of the pixel — through the kernels of pt_shade_rays.hip for the
+        // shade, primary and final steps; with S and Q (both or neither) the
+        // slots' moment home as in the list form.
+        // Bytes in s->wf: ~440 per slot (WfPath 256, WfShadowQ 96, WfClosestQ
+        // 48, the lists, keys and sorted list 34), + 48 with S and Q, and 48
+        // per record.
+        const bool moments = out_S_dev != nullptr;
+        const dim3 grid((unsigned)L.wf_blocks);
+        const WfPass P{R.n_rays, R.split_log2, R.spp, R.bounces, false, moments};
+        return render_wavefront(
+            s, P, grid, st, p->flags, nullptr,
+            [&](const auto& B, int32_t step, dim3 sgrid) {
+                pt_wf_shade_rays(sgrid, st, s->dev, R, step, rays, B.W, B.SQ, B.CQ, (const WfClosestQ*)B.CQP, B.lists,
+                                 B.counters, B.slots, B.keys, moments ? B.home : nullptr);
+            },
+            [&](const auto& B, dim3 pgrid) {
+                pt_wf_primary_rays(pgrid, st, s->dev, R, rays, B.W, B.CQP, B.closest_list, B.counters + 2);
+            },
+            [&](const auto& B) {
+                pt_wf_final_rays(grid, st, R, (const WfPath*)B.W, moments ? (const double*)B.home : nullptr, B.slots,
+                                 out_rgb_dev, out_S_dev, out_Q_dev);
+            });
     }
-    const dim3 grid((unsigned)((threads + kRenderBlock - 1) / kRenderBlock));
-    HIPCHK(hipEventRecord(s->ev0, st));
+    RCCHK(launch_begin(s, st));
     s->last = pt_launch_info{PT_PATH_SINGLE, 1, (int32_t)R.split, p->flags};
-    pt_rays_render((p->flags & PT_FLAG_FORCE_F64) != 0, bvh, grid, st, s->dev, R, (const RayK*)rays_dev,
+    pt_rays_render((p->flags & PT_FLAG_FORCE_F64) != 0, ps.bvh, dim3((unsigned)L.blocks), st, s->dev, R, rays,
                    out_rgb_dev, out_S_dev, out_Q_dev);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(s->ev1, st));
-    s->timed = true;
-    return PT_OK;
+    return launch_end(s, st);
 }
 
 int pt_radiance(pt_scene* s, const pt_ray* rays, int64_t n_rays, const pt_render_params* p, void* out_rgb,
@@ -1707,8 +1510,7 @@ int pt_radiance(pt_scene* s, const pt_ray* rays, int64_t n_rays, const pt_render
 }
 
 int pt_render(pt_scene* s, const pt_render_params* p, void* out_host, pt_stats* stats) {
-    int rc = validate(p);
-    if (rc) return rc;
+    PLANCHK(validate(p));
     if (!s) return fail(PT_EINVAL, "null scene");
     int32_t first = 0, rows = 0;
     band_layout(p, &first, &rows);
@@ -1727,8 +1529,7 @@ int pt_render(pt_scene* s, const pt_render_params* p, void* out_host, pt_stats* 
     }
     pt_render_params q = *p;   // packed in the staging buffer, strided on the host
     q.out_row_stride = 0;
-    rc = pt_render_device(s, &q, s->out_dev, s->stream, stats);
-    if (rc) return rc;
+    RCCHK(pt_render_device(s, &q, s->out_dev, s->stream, stats));
     if (p->out_row_stride == 0 || (size_t)p->out_row_stride * elem == row_bytes)
         HIPCHK(hipMemcpyAsync(out_host, s->out_dev, bytes, hipMemcpyDeviceToHost, s->stream));
     else
@@ -1783,8 +1584,7 @@ static int check_band(const pt_accum* a, const pt_accum_band* b, BandK* B) {
     if (b->row_phase < 0 || b->row_phase >= b->row_step) return fail(PT_EINVAL, "band: need 0 <= row_phase < row_step");
     if (b->row_begin < 0 || b->row_end > a->H || b->row_begin > b->row_end)
         return fail(PT_EINVAL, "band: need 0 <= row_begin <= row_end <= height");
-    const int32_t L = b->lanes_per_pixel;
-    if (L < 0 || L > 64 || (L & (L - 1)) != 0) return fail(PT_EINVAL, "band: lanes_per_pixel must be 0 or a power of two <= 64");
+    if (!lanes_ok(b->lanes_per_pixel, 64)) return fail(PT_EINVAL, "band: lanes_per_pixel must be 0 or a power of two <= 64");
     if (b->reserved != 0) return fail(PT_EINVAL, "band: reserved must be 0");
     *B = band_make(a->W, a->H, b->row_begin, b->row_end, b->row_step, b->row_phase);
     return PT_OK;
@@ -1795,114 +1595,20 @@ static int check_whole(const pt_accum* a, const char* what) {
                                                "(pt_accum_set_band with the default band first)");
 }
 
-static int check_adapt(const pt_adapt_params* a, AdaptK* A) {
-    if (!a) return fail(PT_EINVAL, "null adapt params");
-    if (a->min_spp < 2 || a->max_spp < a->min_spp) return fail(PT_EINVAL, "need 2 <= min_spp <= max_spp");
-    if (a->step_spp < 1) return fail(PT_EINVAL, "step_spp must be >= 1");
-    if (!(a->tol >= 0.0)) return fail(PT_EINVAL, "tol must be >= 0");
-    if (!(a->floor > 0.0)) return fail(PT_EINVAL, "floor must be > 0");
-    A->tol = a->tol; A->floor = a->floor;
-    A->min_spp = (uint32_t)a->min_spp; A->max_spp = (uint32_t)a->max_spp;
-    A->step_spp = (uint32_t)a->step_spp;
-    return PT_OK;
-}
+// (check_adapt: pt_plan.h)
 static bool same_adapt(const pt_adapt_params& x, const pt_adapt_params& y) {
     return x.tol == y.tol && x.floor == y.floor && x.min_spp == y.min_spp && x.max_spp == y.max_spp &&
            x.step_spp == y.step_spp;
 }
-// accumulator launches are ordered on the scene handle as pt_render_device's
-static int accum_begin(pt_accum* a, hipStream_t st) {
-    pt_scene* s = a->scene;
-    if (s->timed) HIPCHK(hipStreamWaitEvent(st, s->ev1, 0));
-    HIPCHK(hipEventRecord(s->ev0, st));
-    return PT_OK;
+static PlanAccum plan_accum(const pt_accum* a) {
+    return PlanAccum{a->W, a->H, a->npix, a->lanes_per_pixel, a->rays != nullptr, a->aa, a->lens};
 }
-static int accum_end(pt_accum* a, hipStream_t st) {
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(a->scene->ev1, st));
-    a->scene->timed = true;
-    return PT_OK;
-}
-
-// pt_accum_render(_stats) on a ray accumulator: one launch of the list kernel
-// over ray records (pt_rays_list.hip) on every scene
-static int accum_render_rays(pt_accum* a, const pt_render_params* p, const pt_adapt_params* ap, void* stream,
-                             pt_stats* stats) {
-    if (!p) return fail(PT_EINVAL, "null params");
-    const uint32_t ok_flags = PT_FLAG_RR | PT_FLAG_FORCE_F64 | PT_FLAG_RAYS_SINGLE;
-    if (p->flags & ~ok_flags) {
-        static const struct { uint32_t bit; const char* name; } kNames[] = {
-            {PT_FLAG_COUNT, "PT_FLAG_COUNT"}, {PT_FLAG_OUT_F64, "PT_FLAG_OUT_F64"},
-            {PT_FLAG_MEGAKERNEL, "PT_FLAG_MEGAKERNEL"}, {PT_FLAG_WALK_COUNT, "PT_FLAG_WALK_COUNT"},
-            {PT_FLAG_KERNEL_TIMES, "PT_FLAG_KERNEL_TIMES"}, {PT_FLAG_AA, "PT_FLAG_AA"}, {PT_FLAG_LENS, "PT_FLAG_LENS"}};
-        std::string bad;
-        uint32_t rest = p->flags & ~ok_flags;
-        for (const auto& f : kNames)
-            if (rest & f.bit) {
-                bad += std::string(bad.empty() ? "" : ", ") + f.name;
-                rest &= ~f.bit;
-            }
-        if (rest) bad += std::string(bad.empty() ? "" : ", ") + "unknown bits";
-        return fail(PT_EINVAL, "unsupported flag bits (" + bad + "): a pass of a ray accumulator takes PT_FLAG_RR, "
-                               "PT_FLAG_FORCE_F64 and PT_FLAG_RAYS_SINGLE only (the ray list kernel does not count, "
-                               "jitter or draw a lens point, and is the single kernel already)");
-    }
-    pt_render_params q = *p;
-    q.flags &= ~(uint32_t)PT_FLAG_RAYS_SINGLE;   // (accepted, no effect yet: reserved for the wavefront form)
-    int rc = validate(&q);
-    if (rc) return rc;
-    AdaptK A;
-    rc = check_adapt(ap, &A);
-    if (rc) return rc;
-    if (p->width != a->W || p->height != a->H)
-        return fail(PT_EINVAL, "width/height are not the accumulator's");
-    if (p->row_begin != 0 || p->row_end != p->height || p->row_step != 1 || p->row_phase != 0 ||
-        p->sample_begin != 0 || p->out_row_stride != 0 || p->lanes_per_pixel != 0)
-        return fail(PT_EINVAL, "an accumulator pass renders the whole frame: row_begin 0, row_end height, "
-                               "row_step 1, sample_begin 0, out_row_stride 0, lanes_per_pixel 0");
-    if (p->spp != ap->max_spp) return fail(PT_EINVAL, "spp must be the budget max_spp");
-    pt_scene* s = a->scene;
-    DeviceGuard g(s->device);
-    hipStream_t st = (hipStream_t)stream;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    rc = pt_accum_select(a, ap, stream, nullptr, nullptr);
-    if (rc) return rc;
-    const AccumMeta m = a->list_meta;
-    if (m.count == 0) return PT_OK;
-    const uint32_t kmin = ~m.nkmin;
-    if (kmin == 0 || kmin > A.step_spp) return fail(PT_EHIP, "select: bad pass size");
-    const bool bvh = s->dev.n_bnode > 0;
-    RaysListK R;
-    R.bounces = p->bounces;
-    R.rr_depth = (p->flags & PT_FLAG_RR) ? std::max(0, p->rr_depth) : -1;
-    R.seed = p->seed;
-    // lanes per record: a frame accumulator's rule (pt_accum_render_stats)
-    if (a->lanes_per_pixel == 0) {
-        R.split = choose_split((uint64_t)a->npix, (uint64_t)m.count, (int32_t)std::min(kmin, 64u), bvh,
-                               min_lanes_of(s->n_cu));
-    } else {
-        uint32_t cap = 1;
-        while (cap * 2u <= std::min(kmin, 64u)) cap *= 2u;
-        R.split = std::min(a->lanes_per_pixel, cap);
-    }
-    R.split_log2 = log2_ceil(R.split);
-    R.n_list = m.count;
-    R.n_rays = a->npix;
-    R.frame_x = s->host.frame_x;
-    R.A = A;
-    const uint64_t threads = (uint64_t)m.count << R.split_log2;
-    const uint64_t blocks = (threads + kRenderBlock - 1) / kRenderBlock;
-    if (blocks * kRenderBlock >= ((uint64_t)1 << 32))
-        return fail(PT_EINVAL, "launch needs 2^32 or more work-items (32-bit lane index)");
-    rc = accum_begin(a, st);
-    if (rc) return rc;
-    a->list_valid = false;   // the pass changes n, S, Q
-    a->aa = 0;
-    a->lens = 0;
-    s->last = pt_launch_info{PT_PATH_SINGLE, 1, (int32_t)R.split, p->flags};
-    pt_rays_render_list((p->flags & PT_FLAG_FORCE_F64) != 0, bvh, dim3((unsigned)blocks), st, s->dev, R, a->rays,
-                        a->list, a->S, a->Q, a->n);
-    return accum_end(a, st);
+// a pass changes n, S, Q (the last select's list is stale), and the
+// accumulator remembers the pass's PT_FLAG_AA and PT_FLAG_LENS
+static void accum_touch(pt_accum* a, bool aa, bool lens) {
+    a->list_valid = false;
+    a->aa = aa ? 1 : 0;
+    a->lens = lens ? 1 : 0;
 }
 
 extern "C" {
@@ -1925,8 +1631,7 @@ int pt_accum_reset(pt_accum* a, void* stream) {
     if (!a) return fail(PT_EINVAL, "null accumulator");
     DeviceGuard g(a->scene->device);
     hipStream_t st = (hipStream_t)stream;
-    int rc = accum_begin(a, st);
-    if (rc) return rc;
+    RCCHK(launch_begin(a->scene, st));
     a->list_valid = false;
     a->list_meta = AccumMeta{};
     a->aa = -1;
@@ -1936,7 +1641,7 @@ int pt_accum_reset(pt_accum* a, void* stream) {
     HIPCHK(hipMemsetAsync(a->n, 0, (size_t)a->npix * sizeof(uint32_t), st));
     HIPCHK(hipMemsetAsync(a->meta, 0, sizeof(AccumMeta), st));
     hipLaunchKernelGGL(k_accum_reset, dim3((a->npix + 255u) / 256u), dim3(256), 0, st, a->err, a->npix);
-    return accum_end(a, st);
+    return launch_end(a->scene, st);
 }
 
 // rays_dev: null for a frame accumulator, else the width*height records of a
@@ -2003,13 +1708,11 @@ int pt_accum_select(pt_accum* a, const pt_adapt_params* ap, void* stream, uint32
                     uint64_t* pass_samples) {
     if (!a) return fail(PT_EINVAL, "null accumulator");
     AdaptK A;
-    int rc = check_adapt(ap, &A);
-    if (rc) return rc;
+    PLANCHK(check_adapt(ap, &A));
     DeviceGuard g(a->scene->device);
     hipStream_t st = (hipStream_t)stream;
     if (!(a->list_valid && same_adapt(a->list_params, *ap))) {
-        rc = accum_begin(a, st);
-        if (rc) return rc;
+        RCCHK(launch_begin(a->scene, st));
         a->list_valid = false;
         HIPCHK(hipMemsetAsync(a->meta, 0, sizeof(AccumMeta), st));
         // the grid: the frame's blocks, or the band's (<= the frame's: bcount fits)
@@ -2028,8 +1731,7 @@ int pt_accum_select(pt_accum* a, const pt_adapt_params* ap, void* stream, uint32
             hipLaunchKernelGGL(k_accum_select_scatter<true>, grid, block, 0, st, a->err, a->n, a->npix, a->band,
                                A, a->bcount, a->list);
         }
-        rc = accum_end(a, st);
-        if (rc) return rc;
+        RCCHK(launch_end(a->scene, st));
         // the pass's one host synchronisation: the list's length (with the
         // smallest k and the pass's samples, 16 bytes)
         HIPCHK(hipMemcpyAsync(&a->list_meta, a->meta, sizeof(AccumMeta), hipMemcpyDeviceToHost, st));
@@ -2049,90 +1751,67 @@ int pt_accum_render(pt_accum* a, const pt_render_params* p, const pt_adapt_param
 
 int pt_accum_render_stats(pt_accum* a, const pt_render_params* p, const pt_adapt_params* ap, void* stream,
                           pt_stats* stats) {
-    if (a && a->rays) return accum_render_rays(a, p, ap, stream, stats);
-    int rc = validate(p);
-    if (rc) return rc;
-    if (!a) return fail(PT_EINVAL, "null accumulator");
+    PlanAccum pa{};
+    PlanScene ps{};
+    if (a) {
+        pa = plan_accum(a);
+        ps = plan_scene(a->scene);
+    }
     AdaptK A;
-    rc = check_adapt(ap, &A);
-    if (rc) return rc;
-    if (p->width != a->W || p->height != a->H)
-        return fail(PT_EINVAL, "width/height are not the accumulator's");
-    if (p->row_begin != 0 || p->row_end != p->height || p->row_step != 1 || p->row_phase != 0 ||
-        p->sample_begin != 0 || p->out_row_stride != 0 || p->lanes_per_pixel != 0)
-        return fail(PT_EINVAL, "an accumulator pass renders the whole frame: row_begin 0, row_end height, "
-                               "row_step 1, sample_begin 0, out_row_stride 0, lanes_per_pixel 0");
-    if (p->flags & ~(uint32_t)(PT_FLAG_RR | PT_FLAG_FORCE_F64 | PT_FLAG_MEGAKERNEL | PT_FLAG_WALK_COUNT |
-                               PT_FLAG_KERNEL_TIMES | PT_FLAG_AA | PT_FLAG_LENS))
-        return fail(PT_EINVAL, "unsupported flag bits: an accumulator pass takes PT_FLAG_RR, PT_FLAG_FORCE_F64, "
-                               "PT_FLAG_MEGAKERNEL, PT_FLAG_WALK_COUNT, PT_FLAG_KERNEL_TIMES, PT_FLAG_AA and "
-                               "PT_FLAG_LENS only");
-    if (p->spp != ap->max_spp) return fail(PT_EINVAL, "spp must be the budget max_spp");
-    const bool aa = (p->flags & PT_FLAG_AA) != 0;
-    if (a->aa >= 0 && a->aa != (aa ? 1 : 0))
-        return fail(PT_EINVAL, "this accumulator's passes so far were made with the other value of PT_FLAG_AA: "
-                               "sample s would have two definitions (pt_accum_reset first)");
-    const bool lens = (p->flags & PT_FLAG_LENS) != 0;
-    if (a->lens >= 0 && a->lens != (lens ? 1 : 0))
-        return fail(PT_EINVAL, "this accumulator's passes so far were made with the other value of PT_FLAG_LENS: "
-                               "sample s would have two definitions (pt_accum_reset first)");
+    PLANCHK(check_pass(p, ap, a ? &pa : nullptr, a ? &ps : nullptr, &A));
     pt_scene* s = a->scene;
-    if (lens && !s->has_lens) return fail(PT_EINVAL, kLensNoScene);
-    if (aa_stats_refused(p->flags) && !wf_scene_ok(s, p->flags)) return fail(PT_EINVAL, kAaNoCount);
     DeviceGuard g(s->device);
     hipStream_t st = (hipStream_t)stream;
     if (stats) memset(stats, 0, sizeof(*stats));
-    rc = pt_accum_select(a, ap, stream, nullptr, nullptr);
-    if (rc) return rc;
+    RCCHK(pt_accum_select(a, ap, stream, nullptr, nullptr));
     const AccumMeta m = a->list_meta;
     if (m.count == 0) return PT_OK;
     const uint32_t kmin = ~m.nkmin;
     if (kmin == 0 || kmin > A.step_spp) return fail(PT_EHIP, "select: bad pass size");
-    const bool bvh = s->dev.n_bnode > 0;
-    ListK R;
-    R.W = a->W; R.H = a->H; R.bounces = p->bounces;
-    R.rr_depth = (p->flags & PT_FLAG_RR) ? std::max(0, p->rr_depth) : -1;
-    R.seed = p->seed;
-    // lanes per pixel: choose_split's rule for a launch of the list's pixels
-    // whose pixels take at least kmin samples
-    if (a->lanes_per_pixel == 0) {
-        R.split = choose_split((uint64_t)a->npix, (uint64_t)m.count, (int32_t)std::min(kmin, 64u), bvh,
-                               min_lanes_of(s->n_cu));
-    } else {   // the band's fixed count, capped at the pass's samples (pt_accum_band)
-        uint32_t cap = 1;
-        while (cap * 2u <= std::min(kmin, 64u)) cap *= 2u;
-        R.split = std::min(a->lanes_per_pixel, cap);
+    uint32_t split;
+    LaunchPlan L;
+    PLANCHK(plan_pass(pa, ps, p->flags, m.count, kmin, &split, &L));
+    const bool f64 = (p->flags & PT_FLAG_FORCE_F64) != 0, bvh = ps.bvh;
+    const bool aa = (p->flags & PT_FLAG_AA) != 0, lens = (p->flags & PT_FLAG_LENS) != 0;
+    const dim3 grid((unsigned)L.blocks), block(kRenderBlock);
+    const ListK R = list_record(p, pa, A, m.count, split, L);
+    if (L.wavefront) {
+        // The list form of render_wavefront: the loop over the slots of the
+        // active list's entries, with the list kernels for the shade, primary
+        // and final steps and the slots' moment home [6][slots] beside the
+        // path records.  The host knows the pass's smallest k only, so the
+        // steps come from the largest k the rule allows.  Every pass
+        // initialises every slot it launches (k_wf_shade_list's step 0): s->wf
+        // holds whatever the previous pass or render left.
+        accum_touch(a, aa, lens);
+        const uint32_t* list = a->list;
+        const uint32_t* n = a->n;
+        const WfPass P{R.n_list, R.split_log2, (int32_t)std::min(A.step_spp, A.max_spp), R.bounces, aa || lens, true};
+        return render_wavefront(
+            s, P, dim3((unsigned)L.wf_blocks), st, p->flags, stats,
+            [&](const auto& B, int32_t step, dim3 sgrid) {
+                if (lens)   // (a lens point per sample; validate: never with the stats flags)
+                    pt_wf_shade_list_lens(aa, sgrid, st, s->dev, R, step, list, n, B.W, B.SQ, B.CQ, B.lists,
+                                          B.counters, B.slots, B.keys, B.home);
+                else if (aa)   // (the slots start their own primary queries)
+                    hipLaunchKernelGGL(k_wf_shade_list_aa, sgrid, dim3(kShadeBlock), 0, st, s->dev, R, step, list, n,
+                                       B.W, B.SQ, B.CQ, B.lists, B.counters, B.slots, B.keys, B.home);
+                else
+                    hipLaunchKernelGGL(k_wf_shade_list, sgrid, dim3(kShadeBlock), 0, st, s->dev, R, step, list, n,
+                                       B.W, B.SQ, B.CQ, (const WfClosestQ*)B.CQP, B.lists, B.counters, B.slots,
+                                       B.keys, B.home);
+            },
+            [&](const auto& B, dim3 pgrid) {
+                hipLaunchKernelGGL(k_wf_primary_list, pgrid, dim3(256), 0, st, s->dev, R, list, n, B.W, B.CQP,
+                                   B.closest_list, B.counters + 2);
+            },
+            [&](const auto& B) {
+                hipLaunchKernelGGL(k_wf_final_list, dim3((unsigned)L.wf_blocks), dim3(256), 0, st, R, list,
+                                   (const double*)B.home, B.slots, a->S, a->Q, a->n);
+            });
     }
-    R.split_log2 = log2_ceil(R.split);
-    R.n_list = m.count;
-    R.npix = a->npix;
-    R.A = A;
-    const uint64_t threads = (uint64_t)m.count << R.split_log2;
-    const uint64_t blocks = (threads + kRenderBlock - 1) / kRenderBlock;
-    R.lanes = blocks * kRenderBlock;
-    if (R.lanes >= ((uint64_t)1 << 32)) return fail(PT_EINVAL, "launch needs 2^32 or more work-items (32-bit lane index)");
-    const bool f64 = (p->flags & PT_FLAG_FORCE_F64) != 0;
-    // BVH scenes take the pass through the wavefront kernels (render_wavefront's
-    // list form) under pt_render_device's condition; the same split, so S, Q
-    // and n are the single kernel's bit for bit
-    const uint64_t wf_blocks = (threads + 255) / 256;
-    if (wf_route(s, p->flags, wf_blocks * 256u)) {
-        rc = accum_begin(a, st);
-        if (rc) return rc;
-        a->list_valid = false;   // the pass changes n, S, Q
-        a->aa = aa ? 1 : 0;
-        a->lens = lens ? 1 : 0;
-        WfList L;
-        L.R = R;
-        L.R.lanes = wf_blocks * 256u;
-        L.list = a->list;
-        L.S = a->S; L.Q = a->Q; L.n = a->n;
-        L.max_k = (int32_t)std::min(A.step_spp, A.max_spp);
-        return render_wavefront(s, RenderK{}, &L, dim3((unsigned)wf_blocks), nullptr, st, p->flags, stats);
-    }
-    if (aa_stats_refused(p->flags)) return fail(PT_EINVAL, kAaNoCount);
 #if PT_MOMENT_HOME
-    if (R.lanes > a->home_lanes) {   // (the previous pass may still read the old one: ordered by the free)
+    if (!a->rays && R.lanes > a->home_lanes) {   // (the previous pass may still read the old one: ordered by the free)
         if (a->home) HIPCHK(hipFree(a->home));
         a->home = nullptr;
         a->home_lanes = 0;
@@ -2141,25 +1820,20 @@ int pt_accum_render_stats(pt_accum* a, const pt_render_params* p, const pt_adapt
         a->home_lanes = R.lanes;
     }
 #endif
-    rc = accum_begin(a, st);
-    if (rc) return rc;
-    a->list_valid = false;   // the pass changes n, S, Q
-    a->aa = aa ? 1 : 0;
-    a->lens = lens ? 1 : 0;
-    s->last = pt_launch_info{PT_PATH_SINGLE, 1, (int32_t)R.split, p->flags};
-    const dim3 grid((unsigned)blocks), block(kRenderBlock);
-    if (lens) {
+    RCCHK(launch_begin(s, st));
+    accum_touch(a, aa, lens);
+    s->last = pt_launch_info{PT_PATH_SINGLE, 1, (int32_t)split, p->flags};
+    if (a->rays)   // the list kernel over ray records (pt_rays_list.hip), on every scene
+        pt_rays_render_list(f64, bvh, grid, st, s->dev, rays_list_record(p, pa, ps, A, m.count, split), a->rays,
+                            a->list, a->S, a->Q, a->n);
+    else if (lens)
         pt_lens_render_list(f64, bvh, aa, grid, st, s->dev, R, a->list, a->S, a->Q, a->n);
-    } else if (aa) {
+    else if (aa)
         pt_aa_render_list(f64, bvh, grid, st, s->dev, R, a->list, a->S, a->Q, a->n);
-    } else if (f64) {
-        hipLaunchKernelGGL((k_render_list<true, true>), grid, block, 0, st, s->dev, R, a->list, a->S, a->Q, a->n, a->home);
-    } else if (bvh) {
-        hipLaunchKernelGGL((k_render_list<false, true>), grid, block, 0, st, s->dev, R, a->list, a->S, a->Q, a->n, a->home);
-    } else {
-        hipLaunchKernelGGL((k_render_list<false, false>), grid, block, 0, st, s->dev, R, a->list, a->S, a->Q, a->n, a->home);
-    }
-    return accum_end(a, st);
+    else
+        hipLaunchKernelGGL(PT_KERNEL_F64_BVH(f64, bvh, k_render_list), grid, block, 0, st, s->dev, R, a->list, a->S,
+                           a->Q, a->n, a->home);
+    return launch_end(s, st);
 }
 
 int pt_accum_resolve_device(pt_accum* a, uint32_t flags, void* out_dev, void* stream) {
@@ -2168,11 +1842,10 @@ int pt_accum_resolve_device(pt_accum* a, uint32_t flags, void* out_dev, void* st
     if (flags & ~(uint32_t)PT_FLAG_OUT_F64) return fail(PT_EINVAL, "resolve takes PT_FLAG_OUT_F64 only");
     DeviceGuard g(a->scene->device);
     hipStream_t st = (hipStream_t)stream;
-    int rc = accum_begin(a, st);
-    if (rc) return rc;
+    RCCHK(launch_begin(a->scene, st));
     hipLaunchKernelGGL(k_accum_resolve, dim3((a->npix + 255u) / 256u), dim3(256), 0, st, a->S, a->n, a->npix,
                        (flags & PT_FLAG_OUT_F64) ? 1 : 0, out_dev);
-    return accum_end(a, st);
+    return launch_end(a->scene, st);
 }
 
 int pt_accum_read(pt_accum* a, double* S, double* Q, uint32_t* n, double* err, uint32_t* list,
@@ -2206,8 +1879,7 @@ int pt_accum_read(pt_accum* a, double* S, double* Q, uint32_t* n, double* err, u
 int pt_accum_set_band(pt_accum* a, const pt_accum_band* band) {
     if (!a) return fail(PT_EINVAL, "null accumulator");
     BandK B;
-    int rc = check_band(a, band, &B);
-    if (rc) return rc;
+    RCCHK(check_band(a, band, &B));
     a->band = B;
     a->whole = B.npix == a->npix;   // every row: begin 0, end height, step 1
     a->lanes_per_pixel = (uint32_t)band->lanes_per_pixel;
@@ -2239,28 +1911,25 @@ int pt_accum_export_band_device(pt_accum* a, void* tile_dev, void* stream) {
     if (!tile_dev || ((uintptr_t)tile_dev & 7u)) return fail(PT_EINVAL, "tile: need 8-byte aligned device memory");
     DeviceGuard g(a->scene->device);
     hipStream_t st = (hipStream_t)stream;
-    int rc = accum_begin(a, st);
-    if (rc) return rc;
+    RCCHK(launch_begin(a->scene, st));
     double *tS, *tQ, *tE;
     uint32_t* tN;
     tile_sections(tile_dev, B.npix, &tS, &tQ, &tE, &tN);
     const uint64_t blocks = (3u * (uint64_t)B.npix + 255u) / 256u;
     hipLaunchKernelGGL(k_accum_export_band, dim3((unsigned)blocks), dim3(256), 0, st, a->S, a->Q, a->err, a->n, B,
                        tS, tQ, tE, tN);
-    return accum_end(a, st);
+    return launch_end(a->scene, st);
 }
 
 int pt_accum_import_band_device(pt_accum* a, const pt_accum_band* band, const void* tile_dev, void* stream) {
     if (!a) return fail(PT_EINVAL, "null accumulator");
     BandK B;
-    int rc = check_band(a, band, &B);
-    if (rc) return rc;
+    RCCHK(check_band(a, band, &B));
     if (B.npix == 0) return PT_OK;
     if (!tile_dev || ((uintptr_t)tile_dev & 7u)) return fail(PT_EINVAL, "tile: need 8-byte aligned device memory");
     DeviceGuard g(a->scene->device);
     hipStream_t st = (hipStream_t)stream;
-    rc = accum_begin(a, st);
-    if (rc) return rc;
+    RCCHK(launch_begin(a->scene, st));
     a->list_valid = false;   // n, S, Q change
     a->list_meta = AccumMeta{};
     a->aa = -1;              // (the caller vouches for the tile's samples)
@@ -2271,7 +1940,7 @@ int pt_accum_import_band_device(pt_accum* a, const pt_accum_band* band, const vo
     const uint64_t blocks = (3u * (uint64_t)B.npix + 255u) / 256u;
     hipLaunchKernelGGL(k_accum_import_band, dim3((unsigned)blocks), dim3(256), 0, st, tS, tQ, tE, tN, B, a->S, a->Q,
                        a->err, a->n);
-    return accum_end(a, st);
+    return launch_end(a->scene, st);
 }
 
 int pt_accum_write(pt_accum* a, const double* S, const double* Q, const uint32_t* n) {
@@ -2279,8 +1948,7 @@ int pt_accum_write(pt_accum* a, const double* S, const double* Q, const uint32_t
     if (!S || !Q || !n) return fail(PT_EINVAL, "write needs S, Q and n");
     DeviceGuard g(a->scene->device);
     hipStream_t st = a->stream;
-    int rc = accum_begin(a, st);
-    if (rc) return rc;
+    RCCHK(launch_begin(a->scene, st));
     a->list_valid = false;
     a->list_meta = AccumMeta{};
     a->aa = -1;   // (the caller vouches for the state it writes)
@@ -2291,8 +1959,7 @@ int pt_accum_write(pt_accum* a, const double* S, const double* Q, const uint32_t
     HIPCHK(hipMemcpyAsync(a->n, n, np * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(a->meta, 0, sizeof(AccumMeta), st));
     hipLaunchKernelGGL(k_accum_reset, dim3((a->npix + 255u) / 256u), dim3(256), 0, st, a->err, a->npix);
-    rc = accum_end(a, st);
-    if (rc) return rc;
+    RCCHK(launch_end(a->scene, st));
     HIPCHK(hipStreamSynchronize(st));
     return PT_OK;
 }
@@ -2379,7 +2046,7 @@ static int check_frame(int32_t width, int32_t height) {
     if ((int64_t)width * height >= (int64_t)1 << 30) return fail(PT_EINVAL, "frame too large (2^30 pixels or more)");
     return PT_OK;
 }
-// the features of the accumulator's frame, once (accum_begin was called)
+// the features of the accumulator's frame, once (launch_begin was called)
 static int accum_features_launch(pt_accum* a, hipStream_t st) {
     if (a->features_valid) return PT_OK;
     const size_t np = a->npix;
@@ -2420,8 +2087,7 @@ int pt_denoise_device(int32_t width, int32_t height, const pt_denoise_params* pa
     int rc = check_frame(width, height);
     if (rc) return rc;
     DenoiseK K;
-    rc = check_denoise(params, &K);
-    if (rc) return rc;
+    RCCHK(check_denoise(params, &K));
     if (!c || !v || !obj || !N || !P || !out_rgb) return fail(PT_EINVAL, "null buffer");
     if (flags & ~(uint32_t)PT_FLAG_OUT_F64) return fail(PT_EINVAL, "denoise takes PT_FLAG_OUT_F64 only");
     hipStream_t st = (hipStream_t)stream;
@@ -2451,8 +2117,7 @@ int pt_denoise(int32_t width, int32_t height, const pt_denoise_params* params, c
     int rc = check_frame(width, height);
     if (rc) return rc;
     DenoiseK K;
-    rc = check_denoise(params, &K);
-    if (rc) return rc;
+    RCCHK(check_denoise(params, &K));
     if (!c || !v || !obj || !N || !P || !out_rgb) return fail(PT_EINVAL, "null buffer");
     if (flags & ~(uint32_t)PT_FLAG_OUT_F64) return fail(PT_EINVAL, "denoise takes PT_FLAG_OUT_F64 only");
     int ndev = 0;
@@ -2496,11 +2161,9 @@ int pt_accum_features(pt_accum* a, void* stream) {
     if (a->features_valid) return PT_OK;
     DeviceGuard g(a->scene->device);
     hipStream_t st = (hipStream_t)stream;
-    int rc = accum_begin(a, st);
-    if (rc) return rc;
-    rc = accum_features_launch(a, st);
-    if (rc) return rc;
-    return accum_end(a, st);
+    RCCHK(launch_begin(a->scene, st));
+    RCCHK(accum_features_launch(a, st));
+    return launch_end(a->scene, st);
 }
 
 int pt_accum_read_features(pt_accum* a, int32_t* tri, int32_t* obj, double* N, double* P) {
@@ -2509,8 +2172,7 @@ int pt_accum_read_features(pt_accum* a, int32_t* tri, int32_t* obj, double* N, d
     pt_scene* s = a->scene;
     DeviceGuard g(s->device);
     hipStream_t st = a->stream;
-    int rc = pt_accum_features(a, st);
-    if (rc) return rc;
+    RCCHK(pt_accum_features(a, st));
     if (s->timed) HIPCHK(hipStreamWaitEvent(st, s->ev1, 0));
     const size_t np = a->npix;
     if (tri) HIPCHK(hipMemcpyAsync(tri, a->f_tri, np * sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -2530,8 +2192,7 @@ int pt_accum_denoise_device(pt_accum* a, const pt_denoise_params* params, uint32
     if (rc) return rc;
     if (!out_rgb_dev) return fail(PT_EINVAL, "null output");
     if (flags & ~(uint32_t)PT_FLAG_OUT_F64) return fail(PT_EINVAL, "denoise takes PT_FLAG_OUT_F64 only");
-    rc = check_frame(a->W, a->H);
-    if (rc) return rc;
+    RCCHK(check_frame(a->W, a->H));
     DeviceGuard g(a->scene->device);
     hipStream_t st = (hipStream_t)stream;
     if (!a->dn[0]) {
@@ -2546,10 +2207,8 @@ int pt_accum_denoise_device(pt_accum* a, const pt_denoise_params* params, uint32
             return fail(PT_ENOMEM, "hipMalloc denoise scratch");
         }
     }
-    rc = accum_begin(a, st);
-    if (rc) return rc;
-    rc = accum_features_launch(a, st);
-    if (rc) return rc;
+    RCCHK(launch_begin(a->scene, st));
+    RCCHK(accum_features_launch(a, st));
     {
         DnTimer tm(st);
         hipLaunchKernelGGL(k_accum_moments, dim3((a->npix + kDnBlock - 1u) / kDnBlock), dim3(kDnBlock), 0, st, a->S,
@@ -2559,7 +2218,7 @@ int pt_accum_denoise_device(pt_accum* a, const pt_denoise_params* params, uint32
                             flags, out_rgb_dev, out_var_dev, st, &tm);
     }
     if (rc) return rc;
-    return accum_end(a, st);
+    return launch_end(a->scene, st);
 }
 
 }  // extern "C"
@@ -2599,8 +2258,7 @@ int pt_render_multi(pt_scene* const* scenes, int32_t n, const pt_render_params* 
         if (scenes[i]->fingerprint != scenes[0]->fingerprint)
             return fail(PT_EINVAL, "handle " + std::to_string(i) + " holds another scene than handle 0");
     }
-    int rc = validate(p);
-    if (rc) return rc;
+    PLANCHK(validate(p));
     // fault injection for the tests of the error path (pt_test_fault_inject):
     // dealing band i fails after bands 0..i-1 were launched
     const int32_t fail_at = g_fault_multi.load();

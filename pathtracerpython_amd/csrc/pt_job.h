@@ -22,6 +22,22 @@ struct RenderK {
     uint32_t tail_pix, tail_lane, tail_log2;
 };
 
+// Work-items per k_render block: one wave.  Nothing in the kernel is shared
+// beyond a wave (a pixel's lanes reduce with shuffles), and the spill home
+// is LDS allocated per block: with 4-wave blocks a wave's slot stayed idle
+// until the block's slowest wave ended (its 40 KB held), with 1-wave blocks
+// it is refilled as soon as the wave ends.
+#ifndef PT_RENDER_BLOCK
+#define PT_RENDER_BLOCK 64
+#endif
+constexpr uint32_t kRenderBlock = PT_RENDER_BLOCK;
+// k_render's waves per SIMD: 4 (<= 128 VGPRs, a little scratch spill outside
+// the triangle loops): 9.5 ms vs 10.8 ms at 3 waves and 15.3 ms at 2 on the
+// 512^2 x 64spp bench (MI355X), see DESIGN.md §5.
+#ifndef PT_RENDER_WAVES
+#define PT_RENDER_WAVES 4
+#endif
+
 // ceil(log2(x)): the shift of a power-of-two lane count (RenderK / ListK split_log2)
 inline uint32_t log2_ceil(uint32_t x) {
     uint32_t l = 0;

@@ -97,9 +97,7 @@ __global__ __launch_bounds__(kRenderBlock, PT_RENDER_WAVES) void k_render_list_l
 template <bool AA>
 static void lens_render(bool f64, bool bvh, dim3 grid, hipStream_t st, const SceneK& S, const RenderK& R, void* out) {
     const dim3 block(kRenderBlock);
-    if (f64) hipLaunchKernelGGL((k_render_lens<true, true, AA>), grid, block, 0, st, S, R, out);
-    else if (bvh) hipLaunchKernelGGL((k_render_lens<false, true, AA>), grid, block, 0, st, S, R, out);
-    else hipLaunchKernelGGL((k_render_lens<false, false, AA>), grid, block, 0, st, S, R, out);
+    hipLaunchKernelGGL(PT_KERNEL_F64_BVH(f64, bvh, k_render_lens, AA), grid, block, 0, st, S, R, out);
 }
 void pt_lens_render(bool f64, bool bvh, bool aa, dim3 grid, hipStream_t st, const SceneK& S, const RenderK& R,
                     void* out) {
@@ -111,9 +109,8 @@ template <bool AA>
 static void lens_render_list(bool f64, bool bvh, dim3 grid, hipStream_t st, const SceneK& S, const ListK& R,
                              const uint32_t* list, double* accS, double* accQ, uint32_t* accN) {
     const dim3 block(kRenderBlock);
-    if (f64) hipLaunchKernelGGL((k_render_list_lens<true, true, AA>), grid, block, 0, st, S, R, list, accS, accQ, accN);
-    else if (bvh) hipLaunchKernelGGL((k_render_list_lens<false, true, AA>), grid, block, 0, st, S, R, list, accS, accQ, accN);
-    else hipLaunchKernelGGL((k_render_list_lens<false, false, AA>), grid, block, 0, st, S, R, list, accS, accQ, accN);
+    hipLaunchKernelGGL(PT_KERNEL_F64_BVH(f64, bvh, k_render_list_lens, AA), grid, block, 0, st, S, R, list, accS,
+                       accQ, accN);
 }
 void pt_lens_render_list(bool f64, bool bvh, bool aa, dim3 grid, hipStream_t st, const SceneK& S,
                          const ListK& R, const uint32_t* list, double* accS, double* accQ, uint32_t* accN) {

@@ -73,9 +73,8 @@ template <bool MOM>
 static void rays_render(bool f64, bool bvh, dim3 grid, hipStream_t st, const SceneK& S, const RaysK& R,
                         const RayK* rays, void* out, double* outS, double* outQ) {
     const dim3 block(kRenderBlock);
-    if (f64) hipLaunchKernelGGL((k_render_rays<true, true, MOM>), grid, block, 0, st, S, R, rays, out, outS, outQ);
-    else if (bvh) hipLaunchKernelGGL((k_render_rays<false, true, MOM>), grid, block, 0, st, S, R, rays, out, outS, outQ);
-    else hipLaunchKernelGGL((k_render_rays<false, false, MOM>), grid, block, 0, st, S, R, rays, out, outS, outQ);
+    hipLaunchKernelGGL(PT_KERNEL_F64_BVH(f64, bvh, k_render_rays, MOM), grid, block, 0, st, S, R, rays, out, outS,
+                       outQ);
 }
 void pt_rays_render(bool f64, bool bvh, dim3 grid, hipStream_t st, const SceneK& S, const RaysK& R,
                     const RayK* rays, void* out, double* outS, double* outQ) {

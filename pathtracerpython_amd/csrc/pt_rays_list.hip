@@ -81,9 +81,8 @@ __global__ __launch_bounds__(256) void k_features_rays(SceneK S, double frame_x,
 void pt_rays_render_list(bool f64, bool bvh, dim3 grid, hipStream_t st, const SceneK& S, const RaysListK& R,
                          const RayK* rays, const uint32_t* list, double* accS, double* accQ, uint32_t* accN) {
     const dim3 block(kRenderBlock);
-    if (f64) hipLaunchKernelGGL((k_render_rays_list<true, true>), grid, block, 0, st, S, R, rays, list, accS, accQ, accN);
-    else if (bvh) hipLaunchKernelGGL((k_render_rays_list<false, true>), grid, block, 0, st, S, R, rays, list, accS, accQ, accN);
-    else hipLaunchKernelGGL((k_render_rays_list<false, false>), grid, block, 0, st, S, R, rays, list, accS, accQ, accN);
+    hipLaunchKernelGGL(PT_KERNEL_F64_BVH(f64, bvh, k_render_rays_list), grid, block, 0, st, S, R, rays, list, accS,
+                       accQ, accN);
 }
 
 void pt_rays_features(bool bvh, hipStream_t st, const SceneK& S, double frame_x, const RayK* rays, uint32_t n,

@@ -18,6 +18,17 @@
 #endif
 #endif
 
+// The <FORCE64, BVH> instantiation of kernel template K (further template
+// arguments after it) that a launch takes: forced f64 runs the BVH
+// instantiation on every scene.  (Three arguments of a call, not a nested
+// conditional: the instantiations are emitted in the order they are named.)
+template <class K>
+inline K pick_f64_bvh(bool f64, bool bvh, K tt, K ft, K ff) {
+    return f64 ? tt : bvh ? ft : ff;
+}
+#define PT_KERNEL_F64_BVH(f64, bvh, K, ...) \
+    pick_f64_bvh(f64, bvh, K<true, true, ##__VA_ARGS__>, K<false, true, ##__VA_ARGS__>, K<false, false, ##__VA_ARGS__>)
+
 // ------------------------------------------------------------- kernels --
 struct StatsDev { unsigned long long v[8]; };
 
@@ -105,22 +116,8 @@ __device__ __forceinline__ int primary_shared(const SceneK& S, D3 eye, D3 d0, ui
 #define PT_PRIMARY_SHARED 16
 #endif
 
-// Work-items per k_render block: one wave.  Nothing in the kernel is shared
-// beyond a wave (a pixel's lanes reduce with shuffles), and the spill home
-// is LDS allocated per block: with 4-wave blocks a wave's slot stayed idle
-// until the block's slowest wave ended (its 40 KB held), with 1-wave blocks
-// it is refilled as soon as the wave ends.
-#ifndef PT_RENDER_BLOCK
-#define PT_RENDER_BLOCK 64
-#endif
-constexpr uint32_t kRenderBlock = PT_RENDER_BLOCK;
+// (kRenderBlock, PT_RENDER_WAVES: pt_job.h, where the host's launch rules read them too)
 template <bool FORCE64, bool COUNT, bool BVH>
-// 4 waves/SIMD (<= 128 VGPRs, a little scratch spill outside the triangle
-// loops): 9.5 ms vs 10.8 ms at 3 waves and 15.3 ms at 2 on the 512^2 x 64spp
-// bench (MI355X), see DESIGN.md §5.
-#ifndef PT_RENDER_WAVES
-#define PT_RENDER_WAVES 4
-#endif
 __global__ __launch_bounds__(kRenderBlock, PT_RENDER_WAVES) void k_render(SceneK S, RenderK R, void* __restrict__ out,
                                                          StatsDev* __restrict__ st) {
     __shared__ double spill[kSpillSlots][kRenderBlock];

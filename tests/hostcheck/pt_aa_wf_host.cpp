@@ -69,8 +69,6 @@ int32_t aa_wf_loop(const SceneK& K, const Src& src, size_t slots, size_t home_st
     return worked;
 }
 
-int32_t rr_of(const pt_render_params* p) { return (p->flags & PT_FLAG_RR) ? std::max(0, p->rr_depth) : -1; }
-
 }  // namespace
 
 extern "C" {
@@ -85,7 +83,7 @@ int hc_aa_wf_render(const pt_scene_desc* d, const pt_render_params* p, uint32_t 
     if (!prepare_scene(d, &H).empty()) return -1;
     bind_host(&H);
     if (H.k.n_bnode == 0 || H.k.n_qnode == 0 || H.k.qstack > kBvhStack) return -3;
-    const RenderK R = host_frame(p, 0, 1, p->height, split, rr_of(p));
+    const RenderK R = host_frame(p, 0, 1, p->height, split);
     const uint32_t npix = R.npix, slog = R.split_log2;
     const int32_t worked = aa_wf_loop(H.k, WfFrame{R}, (size_t)npix << slog, 0, fresh, busy, busy_cap);
     for (uint32_t pl = 0; pl < npix; ++pl) {   // k_wf_final

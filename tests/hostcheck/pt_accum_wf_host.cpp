@@ -61,18 +61,12 @@ void run_walks(const SceneK& K, const std::vector<uint32_t>& want, WfPath* W, Wf
 }
 
 // The launch record of a pass over n_list entries of p's frame under the rule
-// A with `split` slots per entry, as pt_accum_render fills it.
+// A with `split` slots per entry, as pt_accum_render fills it (list_record);
+// lanes: the host loop's slots, with no blocks to round up to.
 ListK host_list(const pt_render_params* p, uint32_t n_list, const AdaptK& A, uint32_t split) {
-    ListK R{};
-    R.W = p->width; R.H = p->height; R.bounces = p->bounces;
-    R.rr_depth = (p->flags & PT_FLAG_RR) ? std::max(0, p->rr_depth) : -1;
-    R.seed = p->seed;
-    R.split = split;
-    R.split_log2 = log2_ceil(split);
-    R.n_list = n_list;
-    R.npix = (uint32_t)p->width * (uint32_t)p->height;
+    const PlanAccum acc{p->width, p->height, (uint32_t)p->width * (uint32_t)p->height, split, false, -1, -1};
+    ListK R = list_record(p, acc, A, n_list, split, LaunchPlan{});
     R.lanes = (uint64_t)n_list << R.split_log2;
-    R.A = A;
     return R;
 }
 

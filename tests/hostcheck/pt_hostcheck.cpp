@@ -9,6 +9,7 @@
 #include <cstddef>
 #include <math.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
@@ -18,24 +19,23 @@
 #include "../../pathtracerpython_amd/csrc/pt_path.h"
 #include "../../pathtracerpython_amd/csrc/pt_wavefront.h"
 #include "../../pathtracerpython_amd/csrc/pt_prepare.h"
+#include "../../pathtracerpython_amd/csrc/pt_plan.h"
 #include "../devcheck/filter_eval.h"
 
 using namespace pt;
 
 // The launch record of the rows first, first + row_step, ... (n_rows of them)
-// of p's frame with `split` slots per pixel, as pt_render_device fills it
-// (the fields the wavefront kernels read).
+// of p's frame with `split` slots per pixel, as pt_render_device fills it:
+// plan_frame's, on a BVH scene (no tail rows), with lanes_per_pixel = split.
+static const PlanScene kHostBvhScene{true, true, 256, false, 0.0};
 static RenderK host_frame(const pt_render_params* p, int32_t first, int32_t row_step, int32_t n_rows,
-                          uint32_t split, int32_t rr_depth) {
-    RenderK R{};
-    R.W = p->width; R.H = p->height; R.spp = p->spp; R.bounces = p->bounces;
-    R.seed = p->seed;
-    R.rr_depth = rr_depth;
-    R.first_row = first; R.row_step = row_step; R.n_rows = n_rows;
-    R.sample_begin = p->sample_begin;
-    R.split = split;
-    R.split_log2 = log2_ceil(split);
-    R.npix = (uint32_t)n_rows * (uint32_t)p->width;
+                          uint32_t split) {
+    pt_render_params q = *p;
+    q.row_step = row_step;
+    q.lanes_per_pixel = (int32_t)split;
+    RenderK R;
+    LaunchPlan L;
+    (void)plan_frame(&q, kHostBvhScene, first, n_rows, &R, &L);
     return R;
 }
 
@@ -197,7 +197,7 @@ int hc_render_wavefront3(const pt_scene_desc* d, const pt_render_params* p, doub
     int32_t first, rows;
     if (!band_layout(p, &first, &rows)) return -2;
     const size_t n = (size_t)rows * p->width;
-    const RenderK R = host_frame(p, first, p->row_step, rows, 1, (p->flags & PT_FLAG_RR) ? p->rr_depth : -1);
+    const RenderK R = host_frame(p, first, p->row_step, rows, 1);
     const WfFrame src{R};
     // (split = 1: a pixel's primary query is its one slot's own, CQP = CQ)
     std::vector<WfPath> W(n);
@@ -734,6 +734,83 @@ int hc_lane_iters(const pt_scene_desc* d, const pt_render_params* p, int32_t spl
         }
     }
     return 0;
+}
+
+}  // extern "C"
+
+// ---- the launch rules (pt_plan.h), for tests/test_plan_host.py ----
+// scene[4]: bvh, walkable, n_cu, has_lens.  acc[6]: W, H, the band's fixed
+// lanes per pixel, rays, aa, lens.  A check's message goes to msg[cap]; the
+// functions return 0, or -1 with the message.
+static PlanScene plan_scene_of(const int32_t* sc) { return PlanScene{sc[0] != 0, sc[1] != 0, sc[2], sc[3] != 0, 2.5}; }
+static PlanAccum plan_accum_of(const int32_t* a) {
+    return PlanAccum{a[0], a[1], (uint32_t)a[0] * (uint32_t)a[1], (uint32_t)a[2], a[3] != 0, a[4], a[5]};
+}
+static int plan_ret(const std::string& m, char* msg, int cap) {
+    if (msg && cap > 0) snprintf(msg, (size_t)cap, "%s", m.c_str());
+    return m.empty() ? 0 : -1;
+}
+
+extern "C" {
+
+uint32_t hc_plan_lane_cap(int32_t spp) { return lane_cap(spp); }
+
+// pt_render_device up to its first HIP call.  out[12]: split, split_log2,
+// npix, tail_pix, tail_lane, tail_log2, work-items, wavefront, rr_depth,
+// out_stride, first_row, n_rows.  Returns 1 for a band without rows.
+int hc_plan_frame(const pt_render_params* p, const int32_t* scene, int64_t* out, char* msg, int cap) {
+    std::string m = validate(p);
+    const PlanScene sc = plan_scene_of(scene);
+    if (m.empty()) m = check_scene(p->flags, sc);
+    if (!m.empty()) return plan_ret(m, msg, cap);
+    int32_t first = 0, rows = 0;
+    band_layout(p, &first, &rows);
+    if (rows == 0) return 1;
+    RenderK R;
+    LaunchPlan L{};
+    m = plan_frame(p, sc, first, rows, &R, &L);
+    if (!m.empty()) return plan_ret(m, msg, cap);
+    const int64_t v[12] = {R.split, R.split_log2, R.npix, R.tail_pix, R.tail_lane, R.tail_log2, (int64_t)L.work_items,
+                           L.wavefront, R.rr_depth, R.out_stride, R.first_row, R.n_rows};
+    memcpy(out, v, sizeof(v));
+    return plan_ret(m, msg, cap);
+}
+
+// pt_radiance_device likewise, n_rays > 0.  out[4]: split, split_log2, work-items, wavefront.
+int hc_plan_rays(const pt_render_params* p, int64_t n_rays, int has_S, int has_Q, const int32_t* scene, int64_t* out,
+                 char* msg, int cap) {
+    std::string m = check_rays(p, true, n_rays, has_S != 0, has_Q != 0);
+    RaysK R;
+    LaunchPlan L{};
+    if (m.empty()) m = plan_rays(p, n_rays, plan_scene_of(scene), &R, &L);
+    if (m.empty()) {
+        const int64_t v[4] = {R.split, R.split_log2, (int64_t)L.work_items, L.wavefront};
+        memcpy(out, v, sizeof(v));
+    }
+    return plan_ret(m, msg, cap);
+}
+
+// An accumulator pass before the select (acc: may be null) ...
+int hc_plan_check_pass(const pt_render_params* p, const pt_adapt_params* ap, const int32_t* acc, const int32_t* scene,
+                       char* msg, int cap) {
+    PlanAccum pa{};
+    if (acc) pa = plan_accum_of(acc);
+    const PlanScene sc = plan_scene_of(scene);
+    AdaptK A;
+    return plan_ret(check_pass(p, ap, acc ? &pa : nullptr, &sc, &A), msg, cap);
+}
+// ... and after it: count list entries of at least kmin samples.  out[5]:
+// split, work-items, the single kernel's blocks, the wavefront's, wavefront.
+int hc_plan_pass(const int32_t* acc, const int32_t* scene, uint32_t flags, uint32_t count, uint32_t kmin, int64_t* out,
+                 char* msg, int cap) {
+    uint32_t split = 0;
+    LaunchPlan L{};
+    const std::string m = plan_pass(plan_accum_of(acc), plan_scene_of(scene), flags, count, kmin, &split, &L);
+    if (m.empty()) {
+        const int64_t v[5] = {split, (int64_t)L.work_items, (int64_t)L.blocks, (int64_t)L.wf_blocks, L.wavefront};
+        memcpy(out, v, sizeof(v));
+    }
+    return plan_ret(m, msg, cap);
 }
 
 }  // extern "C"

@@ -70,7 +70,7 @@ int hc_lens_wf_render(const pt_scene_desc* d, const pt_lens* L, const pt_render_
     if (!L || !prepare_scene(d, &H, L).empty()) return -1;
     bind_host(&H);
     if (H.k.n_bnode == 0 || H.k.n_qnode == 0 || H.k.qstack > kBvhStack) return -3;
-    const RenderK R = host_frame(p, 0, 1, p->height, split, rr_of(p));
+    const RenderK R = host_frame(p, 0, 1, p->height, split);
     const uint32_t npix = R.npix, slog = R.split_log2;
     const size_t slots = (size_t)npix << slog;
     const int32_t worked = (p->flags & PT_FLAG_AA)

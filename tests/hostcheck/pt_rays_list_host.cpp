@@ -6,24 +6,15 @@
 // Built by tests/test_rays_adaptive_host.py into a temporary directory with
 // the hostcheck Makefile's g++ flags (rays_list.mk).
 #include "pt_rays_host.cpp"
-#include "../../pathtracerpython_amd/csrc/pt_job.h"
 
 namespace {
+// the pass's record as pt_accum_render fills it (rays_list_record), with `split` lanes per record
 RaysListK list_record(const pt_render_params* p, const pt_adapt_params* ap, uint32_t split, uint32_t n_list,
                       uint32_t n_rays, double frame_x) {
-    RaysListK R;
-    R.bounces = p->bounces;
-    R.rr_depth = (p->flags & PT_FLAG_RR) ? std::max(0, p->rr_depth) : -1;
-    R.seed = p->seed;
-    R.split = split;
-    R.split_log2 = log2_ceil(split);
-    R.n_list = n_list;
-    R.n_rays = n_rays;
-    R.frame_x = frame_x;
-    R.A.tol = ap->tol; R.A.floor = ap->floor;
-    R.A.min_spp = (uint32_t)ap->min_spp; R.A.max_spp = (uint32_t)ap->max_spp;
-    R.A.step_spp = (uint32_t)ap->step_spp;
-    return R;
+    const PlanAccum acc{(int32_t)n_rays, 1, n_rays, split, true, -1, -1};
+    const PlanScene sc{false, false, 256, false, frame_x};
+    const AdaptK A{ap->tol, ap->floor, (uint32_t)ap->min_spp, (uint32_t)ap->max_spp, (uint32_t)ap->step_spp};
+    return rays_list_record(p, acc, sc, A, n_list, split);
 }
 }  // namespace
 

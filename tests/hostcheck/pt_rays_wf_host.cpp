@@ -112,16 +112,12 @@ int hc_rays_wf(const pt_scene_desc* d, const double* box, const RayK* rays, int6
     if (!prepare_scene(d, &H, nullptr, box).empty()) return -1;
     bind_host(&H);
     if (H.k.n_bnode == 0 || H.k.n_qnode == 0 || H.k.qstack > kBvhStack) return -3;
-    RaysK R{};
-    R.spp = p->spp; R.bounces = p->bounces;
-    R.seed = p->seed;
-    R.rr_depth = rr_of(p);
-    R.sample_begin = p->sample_begin;
-    R.split = split;
-    R.split_log2 = log2_ceil(split);
-    R.n_rays = (uint32_t)n;
-    R.out_f64 = 1;
-    R.frame_x = H.frame_x;
+    pt_render_params q = *p;   // the launch record as pt_radiance_device fills it, f64 out
+    q.lanes_per_pixel = (int32_t)split;
+    q.flags |= PT_FLAG_OUT_F64;
+    RaysK R;
+    LaunchPlan L;
+    (void)plan_rays(&q, n, PlanScene{true, true, 256, false, H.frame_x}, &R, &L);
     const WfRays src{R, rays};
     const size_t slots = ((((size_t)n << R.split_log2) + 255) / 256) * 256;
     int64_t pk[2] = {0, 0};

@@ -7,7 +7,7 @@ CXX ?= g++
 BUILD := $(dir $(abspath $(lastword $(MAKEFILE_LIST))))build
 CSRC := ../../pathtracerpython_amd/csrc
 DEPS := $(CSRC)/pt_core.h $(CSRC)/pt_path.h $(CSRC)/pt_wavefront.h $(CSRC)/pt_prepare.h $(CSRC)/pt_job.h \
-        ../../include/pt_capi.h ../devcheck/filter_eval.h
+        $(CSRC)/pt_plan.h ../../include/pt_capi.h ../devcheck/filter_eval.h
 rays_list: $(BUILD)/librayslist.so
 $(BUILD)/librayslist.so: pt_rays_list_host.cpp pt_rays_host.cpp pt_lens_host.cpp pt_aa_host.cpp pt_hostcheck.cpp \
         $(DEPS) rays_list.mk

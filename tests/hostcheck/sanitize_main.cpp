@@ -285,6 +285,47 @@ int main(int argc, char** argv) {
             CHECK(pk[0] == pk0[0] && pk[1] == pk0[1] && pk[2] == pk0[2] && pk[3] == pk0[3]);
         }
     }
+    // 6. the launch rules (pt_plan.h): integer edge cases of the sizes, the
+    // lane counts and the 2^32 / 2^29 / 2^30 guards, on both kinds of scene
+    {
+        const int32_t dims[] = {1, 7, 512, 49152, 65536, 1 << 24, 0x7fffffff};
+        const int32_t spps[] = {1, 3, 5, 64, 65, 0x7fffffff};
+        const int32_t lanes[] = {0, 1, 3, 8, 64, 128, -2, (int32_t)0x80000000};
+        const uint32_t flagset[] = {0, PT_FLAG_RR, PT_FLAG_COUNT, PT_FLAG_AA | PT_FLAG_WALK_COUNT, PT_FLAG_LENS, 1u << 7,
+                                    PT_FLAG_AA | PT_FLAG_COUNT, PT_FLAG_RAYS_SINGLE, ~0u};
+        const int32_t scenes[][4] = {{0, 0, 256, 0}, {1, 1, 256, 1}, {1, 0, 1, 0}, {0, 0, 0x7fffffff, 0}};
+        int64_t out[12];
+        char msg[512];
+        long accepted = 0, refused = 0;
+        const int32_t heights[] = {1, 7, 512, 8192};   // (the tail rows' prefix is a loop over the band's rows)
+        for (int32_t w : dims) for (int32_t h : heights) for (int32_t spp : spps) for (int32_t l : lanes)
+            for (uint32_t fl : flagset) for (const auto& sc : scenes) {
+                pt_render_params p{};
+                p.width = w; p.height = h; p.spp = spp; p.bounces = 3; p.flags = fl; p.rr_depth = -3;
+                p.row_end = h; p.row_step = 1 + (w & 1); p.lanes_per_pixel = l;
+                const int rc = hc_plan_frame(&p, sc, out, msg, sizeof msg);
+                CHECK(rc == 0 || rc == 1 || (rc == -1 && msg[0]));
+                if (rc == 0) CHECK(out[6] > 0 && out[6] < ((int64_t)1 << 32) && out[3] <= out[2]);
+                (rc == 0 ? accepted : refused)++;
+                const int64_t n = (int64_t)w * (h & 0xff);
+                const int rr = hc_plan_rays(&p, n ? n : 1, l & 1, l & 1, sc, out, msg, sizeof msg);
+                CHECK(rr == 0 || (rr == -1 && msg[0]));
+                if (rr == 0) CHECK(out[2] > 0 && out[2] < ((int64_t)1 << 32));
+                const int32_t acc[6] = {w, h & 0xffff, l < 0 ? 0 : l, (int32_t)(fl & 1), (spp % 3) - 1, (h % 3) - 1};
+                pt_adapt_params ap{0.01, 0.01, 2, spp, 1 + (spp & 7), 0};
+                (void)hc_plan_check_pass(&p, &ap, w & 2 ? acc : nullptr, sc, msg, sizeof msg);
+                const uint32_t kmins[] = {1, 3, 64, 0xffffffffu};
+                if (acc[1] > 0 && l >= 0 && (int64_t)acc[0] * acc[1] < ((int64_t)1 << 32))
+                    for (uint32_t kmin : kmins) {
+                        const int rp = hc_plan_pass(acc, sc, fl & 0x7ffu, (uint32_t)acc[0] * (uint32_t)acc[1], kmin, out, msg,
+                                                    sizeof msg);
+                        CHECK(rp == 0 || (rp == -1 && msg[0]));
+                        if (rp == 0) CHECK(out[0] >= 1 && out[0] <= 64 && out[2] * 64 < ((int64_t)1 << 32));
+                    }
+            }
+        printf("plan: %ld frames accepted, %ld refused\n", accepted, refused);
+        CHECK(accepted > 0 && refused > 0);
+    }
     printf("sanitize: OK\n");
     return 0;
 }

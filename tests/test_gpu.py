@@ -152,8 +152,9 @@ def test_k2_full_size(R, k2_oracle):
 @pytest.mark.parametrize("world", [2, 4, 8])
 def test_k2_bands_vs_oracle(R, k2_oracle, world):
     """One rank's interleaved band of an N-GPU strong-scaling K2 render (the
-    bench's multi-GPU step): the band's lanes per pixel follow its size (8 /
-    8 / 16 / 32 at N = 1 / 2 / 4 / 8, choose_split), so every band, first and
+    bench's multi-GPU step): the band's lanes per pixel follow its size (16 /
+    16 / 16 / 32 at N = 1 / 2 / 4 / 8, choose_split in pt_plan.h;
+    tests/test_plan_host.py), so every band, first and
     last phase, is checked against the oracle's whole frame: f64 <= 1e-12,
     f32 <= 1e-6."""
     from pathtracerpython_amd.distributed import band_rows_of

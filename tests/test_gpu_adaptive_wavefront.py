@@ -1,6 +1,6 @@
 """Adaptive sampling on BVH scenes through the wavefront kernels (the list
 form: pt_shade.h k_wf_shade_list, pt_hip.hip k_wf_primary_list /
-k_wf_final_list, render_wavefront with a WfList): which path a pass takes,
+k_wf_final_list, render_wavefront's list form): which path a pass takes,
 whole runs and single passes against the single-kernel list pass
 (megakernel=True) bit for bit and against the oracle's per-sample colours,
 wide splits and ragged launches, the spilled walk stacks, and the buffers a

@@ -69,8 +69,8 @@ def moment_gaps(S, Q, frames):
 
 
 # A ------------------------------------- 16, 32, 64 lanes per pixel (Cornell) --
-# Lanes per pixel of these passes, by choose_split (pt_hip.hip) as
-# pt_accum_render calls it: spp' = min(kmin, 64) with kmin the pass's smallest
+# Lanes per pixel of these passes, by choose_split (pt_plan.h) as
+# plan_pass calls it for pt_accum_render (tests/test_plan_host.py holds the numbers): spp' = min(kmin, 64) with kmin the pass's smallest
 # k (= spp here: one pass from n = 0), cap = the largest power of two <= spp';
 # the scene has no BVH and the launch (35 pixels) is far below min_lanes, so
 # the second loop doubles the split up to the cap whatever the first left:
