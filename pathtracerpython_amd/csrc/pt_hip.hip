@@ -425,7 +425,7 @@ __global__ __launch_bounds__(256) void k_wf_final(SceneK S, RenderK R, const WfP
 
 // ------------------------------------ adaptive sampling (pt_accum) --
 // Per-pixel moments S, Q and counts n on the device (include/pt_capi.h,
-// pt_accum; the rule and the lane code: pt_path.h MomentSched, moment_err).
+// pt_accum; the rule and the lane code: pt_path.h MomentSink, moment_err).
 // A pass renders a LIST of pixels: k_accum_select_* build it (err, the active
 // predicate, an ordered compaction), k_render_list adds k samples to each
 // listed pixel, k_accum_resolve writes S / n as a framebuffer (ListK:
@@ -444,6 +444,10 @@ __global__ __launch_bounds__(256) void k_wf_final(SceneK S, RenderK R, const WfP
 // entry's pixel e and stride the k samples its pass adds, from sample n[e] on.
 // The pixel's lanes reduce S and Q in store_pixel's xor order and lane 0 adds
 // them to the accumulator with plain loads and stores (the list is unique).
+// (The four list kernels each write this reduce and commit out: as one
+// helper, the sums by value, by reference, or with the store's condition
+// inside it, every unit's code moved: this one -1024 B, pt_aa.hip -1688 B,
+// pt_lens.hip +1340 B, pt_rays_list.hip +1280 B.)
 template <bool FORCE64, bool BVH>
 __global__ __launch_bounds__(kRenderBlock, PT_LIST_WAVES) void k_render_list(
     SceneK S, ListK R, const uint32_t* __restrict__ list, double* __restrict__ accS,
@@ -490,7 +494,7 @@ __global__ __launch_bounds__(kRenderBlock, PT_LIST_WAVES) void k_render_list(
         } else if (J.n_samples > 0 && R.bounces > 0) {
             tri0 = closest<FORCE64, false, BVH>(S, eye, d0, -1, sp, &P0, &cnt, true);
         }
-        render_lane_moments<FORCE64, false, BVH>(S, J, d0, tri0, P0, sp, &cnt, M);
+        render_lane_cached<FORCE64, false, BVH>(S, J, FrameHit{tri0, d0}, P0, sp, &cnt, MomentSink<decltype(M)>{M});
     }
     D3 s = valid ? M.sum() : d3(0, 0, 0), q = valid ? M.sumsq() : d3(0, 0, 0);
     for (uint32_t m = 1; m < R.split; m <<= 1) {

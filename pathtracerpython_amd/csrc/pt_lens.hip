@@ -1,7 +1,7 @@
 // pt_lens.hip — the thin-lens kernels (PT_FLAG_LENS, include/pt_capi.h;
 // DESIGN.md §4.3): k_render_aa and k_render_list_aa with a lens point per
-// sample (pt_path.h LensSched / LensMomentSched).  Every sample's primary ray
-// starts at its own origin eye', so there is no wave-shared table of the eye's
+// sample (pt_path.h LensRay; SumSink / MomentSink).  Every sample's primary
+// ray starts at its own origin eye', so there is no wave-shared table of the eye's
 // origin terms (pt_aa.hip aa_eye_fill): each lane computes origin_q for its
 // origin, and the first two spill rows the table used carry eye' for the
 // sample's bounces.  A translation unit of its own (build.py AA_UNITS), so
@@ -18,35 +18,30 @@ __global__ __launch_bounds__(kRenderBlock, PT_RENDER_WAVES) void k_render_lens(S
     __shared__ double spill[kSpillSlots][kRenderBlock];
     const Spill sp{&spill[0][threadIdx.x], (int)kRenderBlock};
     const uint32_t tid = blockIdx.x * kRenderBlock + threadIdx.x;
-    const bool tail = tid >= R.tail_lane;   // wave-uniform
-    const uint32_t slog = tail ? R.tail_log2 : R.split_log2, split = 1u << slog;
-    const uint32_t lt = tail ? tid - R.tail_lane : tid;
-    const uint32_t pl = (tail ? R.tail_pix : 0u) + (lt >> slog);
-    const uint32_t c = lt & (split - 1u);
-    const bool valid = pl < (tail ? R.npix : R.tail_pix);
+    const PixelMap m = pixel_map(R, tid);
     D3 acc = d3(0, 0, 0);
     int32_t row_local = 0, ix = 0;
-    if (valid) {
-        row_local = (int32_t)(pl / (uint32_t)R.W);
-        ix = (int32_t)pl - row_local * R.W;
+    if (m.valid) {
+        row_local = (int32_t)(m.pl / (uint32_t)R.W);
+        ix = (int32_t)m.pl - row_local * R.W;
         const int32_t iy = R.first_row + row_local * R.row_step;
         LaneJob J;
         J.seed = R.seed;
         J.pixel = (uint32_t)ix * (uint32_t)R.H + (uint32_t)iy;
-        J.sample0 = R.sample_begin + (int32_t)c;
-        J.sample_stride = (int32_t)split;
-        J.n_samples = ((int32_t)c < R.spp) ? (R.spp - (int32_t)c + (int32_t)split - 1) / (int32_t)split : 0;
+        J.sample0 = R.sample_begin + (int32_t)m.c;
+        J.sample_stride = (int32_t)m.split;
+        J.n_samples = ((int32_t)m.c < R.spp) ? (R.spp - (int32_t)m.c + (int32_t)m.split - 1) / (int32_t)m.split : 0;
         J.bounces = R.bounces;
         J.rr_depth = R.rr_depth;
         Counters cnt = {};
-        acc = render_lane_lens<FORCE64, BVH, AA>(S, J, AaPixel{R.W, R.H, ix, iy}, sp, &cnt);
+        acc = render_lane_sampled<FORCE64, BVH>(S, J, LensRay<FORCE64, BVH, AA>{{R.W, R.H, ix, iy}}, sp, &cnt, SumSink{});
     }
     SlotJob j;
-    j.valid = valid;
-    j.c = c;
+    j.valid = m.valid;
+    j.c = m.c;
     j.row_local = row_local;
     j.ix = ix;
-    store_pixel(R, j, acc, out, split);
+    store_pixel(R, j, acc, out, m.split);
 }
 
 // k_render_list_aa's mapping and reduction
@@ -78,7 +73,8 @@ __global__ __launch_bounds__(kRenderBlock, PT_RENDER_WAVES) void k_render_list_l
         J.bounces = R.bounces;
         J.rr_depth = R.rr_depth;
         Counters cnt = {};
-        render_lane_moments_lens<FORCE64, BVH, AA>(S, J, AaPixel{R.W, R.H, ix, iy}, sp, &cnt, M);
+        render_lane_sampled<FORCE64, BVH>(S, J, LensRay<FORCE64, BVH, AA>{{R.W, R.H, ix, iy}}, sp, &cnt,
+                                          MomentSink<MomentRegs>{M});
     }
     D3 s = valid ? M.sum() : d3(0, 0, 0), q = valid ? M.sumsq() : d3(0, 0, 0);
     for (uint32_t m = 1; m < R.split; m <<= 1) {

@@ -1918,23 +1918,100 @@ __device__ inline void pt_phase_flush_sum(int i, uint64_t v) {
 #endif
 
 // Sample scheduling of the bounce loop (render_loop): which sample a lane
-// traces next once its path ends.  LaneSched: the lane's own samples
-// sample0, sample0 + stride, ... (the host build, counting launches, BVH
-// scenes, the wavefront kernels' order); pt_hip.hip's WavePool: the samples
-// of a wave's pixels, handed out as lanes free up.
-struct LaneSched {
+// traces next once its path ends.  Every scheduler hands out the lane's own
+// samples sample0, sample0 + stride, ... (the host build, the counting
+// launches, BVH scenes and the wavefront kernels keep this order); one differs
+// from another in two things, each a policy of Sched:
+//   Primary: where a sample's primary ray comes from.  A hit traced once and
+//     cached, which every sample of the lane restarts from (kCached: FrameHit,
+//     the frame's; RayHit, a ray record's), or a ray traced per sample (AaRay,
+//     jittered; LensRay, from the sample's lens point).  kEye is the specular
+//     term's eye (bounce<kEye>): 0 the scene's, 1 the sample's lens point in
+//     the home rows kSpLens, 2 the three doubles at the source's eye_o().
+//   Sink: what becomes of a complete sample's colour.  SumSink: it stays in
+//     render_loop's running acc.  MomentSink: it goes to the lane's moment
+//     home (MomentRegs / MomentMem below) and acc restarts at 0.
+struct SumSink {
+    static constexpr bool kMoments = false;
+    PT_HD void add(D3 c, D3* acc) const { *acc = *acc + c; }   // a sample that is complete without a path
+    PT_HD void end(D3*) const {}                               // a path's end: *acc has its colour
+};
+template <class Home>
+struct MomentSink {
+    static constexpr bool kMoments = true;
+    Home& home;
+    PT_HD void add(D3 c, D3*) const { home.add(c); }
+    PT_HD void end(D3* acc) const {
+        home.add(*acc);
+        *acc = d3(0, 0, 0);
+    }
+};
+
+template <class Primary, class Sink>
+struct Sched {
+    static constexpr int kEye = Primary::kEye;
     const LaneJob& J;
-    int tri0;
+    Primary prim;
     int si;
+    Sink sink;
     PT_HD uint32_t sample() const { return (uint32_t)(J.sample0 + si * J.sample_stride); }
     PT_HD uint32_t pixel() const { return J.pixel; }
+    PT_HD const double* eye_o() const {
+        if constexpr (kEye == 2) return prim.eye_o();
+        else return nullptr;
+    }
+    // A primary ray per sample: every sample of the lane from si on, its first
+    // included, starts by tracing its own ray.  A sample whose primary ray
+    // escapes (0) or hits the light (light_rgb, main.py:214-215) is complete at
+    // once, and start() goes on to the next one until a sample lands on an
+    // object or the lane's samples run out.  (The sum adds nothing for an
+    // escape; a home gets its 0.)
+    PT_HD bool start(const SceneK& S, const Spill& sp, int* tri, D3* acc, Counters* cnt) {
+        for (; si < J.n_samples; ++si) {
+            const int t = prim.primary(S, J, sample(), sp, cnt);
+            if (t >= 0 && t < S.n_obj_tri) {
+                *tri = t;
+                return true;
+            }
+            if (Sink::kMoments || t >= 0) sink.add(t < 0 ? d3(0, 0, 0) : ld3(S.kd + kKdLightRgb), acc);
+        }
+        return false;
+    }
     // after an iteration; `done`: this lane's path ended.  Starts the lane's
-    // next sample from the cached primary hit (primary rays are identical for
-    // every sample, main.py:191); false when it has none left.
+    // next sample, from the cached primary hit or with start(); false when it
+    // has none left.
     template <bool COUNT>
-    PT_HD bool advance(const SceneK& S, bool done, const Spill& sp, int* tri, D3*, Counters* cnt) {
+    PT_HD bool advance(const SceneK& S, bool done, const Spill& sp, int* tri, D3* acc, Counters* cnt) {
         if (!done) return true;
-        if (++si >= J.n_samples) return false;
+        sink.end(acc);
+        ++si;
+        if constexpr (Primary::kCached) {
+            if (si >= J.n_samples) return false;
+            prim.template restart<COUNT>(S, sp, tri, cnt);
+            return true;
+        } else {
+            return start(S, sp, tri, acc, cnt);
+        }
+    }
+};
+
+// The frame's cached primary hit: primary rays are identical for every sample
+// (main.py:191), so a restart rebuilds the origin from kSpP0 and the incoming
+// direction from the two rows kSpD0 and the eye's z.
+struct FrameHit {
+    static constexpr bool kCached = true;
+    static constexpr int kEye = 0;
+    int tri0;
+    D3 d0;   // the incoming direction of bounce 0 (main.py:191)
+    PT_HD void begin(const Spill& sp, D3 P0) const {
+        sp.put(kSpD0, d0.x);
+        sp.put(kSpD0 + 1, d0.y);
+        sp.put3(kSpP0, P0);
+        sp.put3(kSpP, P0);
+        sp.put3(kSpNd, d0);
+    }
+    template <bool COUNT>
+    PT_HD void restart(const SceneK& S, const Spill& sp, int* tri, Counters* cnt) const {
         *tri = tri0;
         sp.put3(kSpP, sp.get3(kSpP0));
         sp.put3(kSpNd, d3(sp.get(kSpD0), sp.get(kSpD0 + 1), 0.0 - S.kd[kKdEye + 2]));
@@ -1942,27 +2019,7 @@ struct LaneSched {
             bump<COUNT>(cnt, &Counters::closest_tests, (uint32_t)S.n_tri);
             bump<COUNT>(cnt, &Counters::ray_bounces, 1);
         }
-        return true;
     }
-};
-
-// A scheduler of the lens kernels declares kLens: its samples read their own
-// eye' (bounce<true>); every other scheduler's loop is as it was.
-template <class Sched, class = void>
-struct sched_lens { static constexpr bool value = false; };
-template <class Sched>
-struct sched_lens<Sched, decltype((void)Sched::kLens)> { static constexpr bool value = Sched::kLens; };
-// A scheduler of the ray kernels (pt_rays.hip) declares kRays and eye_o(): the
-// origin of its lane's ray record is the specular term's eye (bounce<2>).
-template <class Sched, class = void>
-struct sched_rays {
-    static constexpr bool value = false;
-    PT_HD static const double* eye_o(const Sched&) { return nullptr; }
-};
-template <class Sched>
-struct sched_rays<Sched, decltype((void)Sched::kRays)> {
-    static constexpr bool value = Sched::kRays;
-    PT_HD static const double* eye_o(const Sched& q) { return q.eye_o(); }
 };
 
 // The bounce loop: paths are regenerated in place (Sched::advance), so a
@@ -2023,9 +2080,8 @@ PT_HD void render_loop(const SceneK& S, const LaneJob& J, int tri, const Spill& 
 #endif
         // next ray (main.py:236-268): it does not depend on the colour
         double kf;
-        const D3 nd = bounce<sched_rays<Sched>::value ? 2 : sched_lens<Sched>::value ? 1 : 0>(
-            S, R, m, P, sp.get3(kSpNd), u_of(w[12]), u_of(w[13]), u_of(w[14]), &kf, &sp,
-            sched_rays<Sched>::eye_o(q));
+        const D3 nd = bounce<Sched::kEye>(S, R, m, P, sp.get3(kSpNd), u_of(w[12]), u_of(w[13]), u_of(w[14]),
+                                          &kf, &sp, q.eye_o());
         const double kn = k * kf;
         bool trace = (b + 1 < J.bounces);
         double kk = kn;
@@ -2141,38 +2197,71 @@ PT_HD void render_loop(const SceneK& S, const LaneJob& J, int tri, const Spill& 
     *accp = acc;
 }
 
-// All samples of one lane for one pixel (LaneSched); returns the SUM of
-// sample colours.
-template <bool FORCE64, bool COUNT, bool BVH = true>
-PT_HD D3 render_lane(const SceneK& S, const LaneJob& J, D3 d0, int tri0, D3 P0,
-                     const Spill& sp, Counters* cnt) {
+// All samples of one lane: the two prologues of render_loop, each over the
+// sink.  With a SumSink they return the SUM of the lane's sample colours; with
+// a MomentSink they return nothing, the J.n_samples colours went to the home
+// one by one.  No bounces: main.py:192 never runs, the sum is 0 and a home
+// gets samples of 0.  The kernels call these two directly, the policies as
+// temporaries: through a forwarding function per pair every kernel's code
+// moved.  The eight forwards render_lane, render_lane_moments, ..._aa,
+// ..._lens, ..._rays below keep the earlier signatures for the host checks
+// (tests/hostcheck), where an inlining level changes nothing.
+//
+// A cached primary hit (prim.tri0, P0): a primary ray that escapes or hits
+// the light gives constant samples, added one by one.  The counters take the
+// cached trace once per sample, in the sum form only (the counting launches').
+template <bool FORCE64, bool COUNT, bool BVH, class Primary, class Sink>
+PT_HD auto render_lane_cached(const SceneK& S, const LaneJob& J, Primary prim, D3 P0, const Spill& sp,
+                              Counters* cnt, Sink sink) {
+    constexpr bool kCount = COUNT && !Sink::kMoments;
+    const int tri0 = prim.tri0;
     D3 acc = d3(0, 0, 0);
-    if (J.n_samples <= 0 || J.bounces <= 0) return acc;   // main.py:192 never runs
-    if (tri0 < 0 || tri0 >= S.n_obj_tri) {   // primary ray escapes or hits the light
-        const D3 v = tri0 < 0 ? d3(0, 0, 0) : ld3(S.kd + kKdLightRgb);
+    if (J.n_samples <= 0 || (!Sink::kMoments && J.bounces <= 0)) {
+        // nothing to add
+    } else if (J.bounces <= 0 || tri0 < 0 || tri0 >= S.n_obj_tri) {
+        const D3 v = (J.bounces <= 0 || tri0 < 0) ? d3(0, 0, 0) : ld3(S.kd + kKdLightRgb);
         for (int i = 0; i < J.n_samples; ++i) {
-            acc = acc + v;
-            if (COUNT) {
-                bump<COUNT>(cnt, &Counters::closest_tests, (uint32_t)S.n_tri);
-                bump<COUNT>(cnt, &Counters::ray_bounces, 1);
-                bump<COUNT>(cnt, &Counters::escapes, tri0 < 0 ? 1u : 0u);
-                bump<COUNT>(cnt, &Counters::light_hits, tri0 < 0 ? 0u : 1u);
+            sink.add(v, &acc);
+            if (kCount) {
+                bump<kCount>(cnt, &Counters::closest_tests, (uint32_t)S.n_tri);
+                bump<kCount>(cnt, &Counters::ray_bounces, 1);
+                bump<kCount>(cnt, &Counters::escapes, tri0 < 0 ? 1u : 0u);
+                bump<kCount>(cnt, &Counters::light_hits, tri0 < 0 ? 0u : 1u);
             }
         }
-        return acc;
+    } else {
+        prim.begin(sp, P0);
+        if (kCount) {
+            bump<kCount>(cnt, &Counters::closest_tests, (uint32_t)S.n_tri);
+            bump<kCount>(cnt, &Counters::ray_bounces, 1);
+        }
+        Sched<Primary, Sink> q{J, prim, 0, sink};
+        render_loop<FORCE64, COUNT, BVH>(S, J, tri0, sp, cnt, q, &acc);
     }
-    sp.put(kSpD0, d0.x);
-    sp.put(kSpD0 + 1, d0.y);
-    sp.put3(kSpP0, P0);
-    sp.put3(kSpP, P0);
-    sp.put3(kSpNd, d0);   // incoming direction of bounce 0 (main.py:191)
-    if (COUNT) {   // the cached primary trace, counted per sample
-        bump<COUNT>(cnt, &Counters::closest_tests, (uint32_t)S.n_tri);
-        bump<COUNT>(cnt, &Counters::ray_bounces, 1);
+    if constexpr (!Sink::kMoments) return acc;
+}
+// A primary ray per sample (Sched::start).
+template <bool FORCE64, bool BVH, class Primary, class Sink>
+PT_HD auto render_lane_sampled(const SceneK& S, const LaneJob& J, Primary prim, const Spill& sp, Counters* cnt,
+                               Sink sink) {
+    D3 acc = d3(0, 0, 0);
+    if (J.n_samples <= 0 || (!Sink::kMoments && J.bounces <= 0)) {
+        // nothing to add
+    } else if (J.bounces <= 0) {
+        for (int i = 0; i < J.n_samples; ++i) sink.add(d3(0, 0, 0), &acc);
+    } else {
+        Sched<Primary, Sink> q{J, prim, 0, sink};
+        int tri = -1;
+        if (q.start(S, sp, &tri, &acc, cnt)) render_loop<FORCE64, false, BVH>(S, J, tri, sp, cnt, q, &acc);
     }
-    LaneSched q{J, tri0, 0};
-    render_loop<FORCE64, COUNT, BVH>(S, J, tri0, sp, cnt, q, &acc);
-    return acc;
+    if constexpr (!Sink::kMoments) return acc;
+}
+
+// All samples of one lane for one pixel (FrameHit); returns the SUM of sample
+// colours.
+template <bool FORCE64, bool COUNT, bool BVH = true>
+PT_HD D3 render_lane(const SceneK& S, const LaneJob& J, D3 d0, int tri0, D3 P0, const Spill& sp, Counters* cnt) {
+    return render_lane_cached<FORCE64, COUNT, BVH>(S, J, FrameHit{tri0, d0}, P0, sp, cnt, SumSink{});
 }
 
 // ------------------------------------------------- per-pixel moments --
@@ -2209,53 +2298,11 @@ struct MomentMem {
     PT_HD D3 sumsq() const { return d3(base[3 * stride], base[4 * stride], base[5 * stride]); }
 };
 
-// LaneSched's sample order plus the moments: when a path ends its colour
-// (render_loop's running acc, which then restarts at 0) goes to the home.
-template <class Home>
-struct MomentSched {
-    const LaneJob& J;
-    int tri0;
-    int si;
-    Home& home;
-    PT_HD uint32_t sample() const { return (uint32_t)(J.sample0 + si * J.sample_stride); }
-    PT_HD uint32_t pixel() const { return J.pixel; }
-    template <bool COUNT>
-    PT_HD bool advance(const SceneK& S, bool done, const Spill& sp, int* tri, D3* acc, Counters* cnt) {
-        if (!done) return true;
-        home.add(*acc);
-        *acc = d3(0, 0, 0);
-        if (++si >= J.n_samples) return false;
-        *tri = tri0;
-        sp.put3(kSpP, sp.get3(kSpP0));
-        sp.put3(kSpNd, d3(sp.get(kSpD0), sp.get(kSpD0 + 1), 0.0 - S.kd[kKdEye + 2]));
-        if (COUNT) {
-            bump<COUNT>(cnt, &Counters::closest_tests, (uint32_t)S.n_tri);
-            bump<COUNT>(cnt, &Counters::ray_bounces, 1);
-        }
-        return true;
-    }
-};
-
-// render_lane with the moments: the lane's J.n_samples sample colours are
-// added to `home` one by one (a primary ray that escapes or hits the light
-// gives constant samples; no bounces: samples of 0, main.py:192 never runs).
+// render_lane with the moments: the lane's sample colours into `home`.
 template <bool FORCE64, bool COUNT, bool BVH, class Home>
-PT_HD void render_lane_moments(const SceneK& S, const LaneJob& J, D3 d0, int tri0, D3 P0,
-                               const Spill& sp, Counters* cnt, Home& home) {
-    if (J.n_samples <= 0) return;
-    if (J.bounces <= 0 || tri0 < 0 || tri0 >= S.n_obj_tri) {
-        const D3 v = (J.bounces <= 0 || tri0 < 0) ? d3(0, 0, 0) : ld3(S.kd + kKdLightRgb);
-        for (int i = 0; i < J.n_samples; ++i) home.add(v);
-        return;
-    }
-    sp.put(kSpD0, d0.x);
-    sp.put(kSpD0 + 1, d0.y);
-    sp.put3(kSpP0, P0);
-    sp.put3(kSpP, P0);
-    sp.put3(kSpNd, d0);   // incoming direction of bounce 0 (main.py:191)
-    D3 acc = d3(0, 0, 0);
-    MomentSched<Home> q{J, tri0, 0, home};
-    render_loop<FORCE64, COUNT, BVH>(S, J, tri0, sp, cnt, q, &acc);
+PT_HD void render_lane_moments(const SceneK& S, const LaneJob& J, D3 d0, int tri0, D3 P0, const Spill& sp,
+                               Counters* cnt, Home& home) {
+    render_lane_cached<FORCE64, COUNT, BVH>(S, J, FrameHit{tri0, d0}, P0, sp, cnt, MomentSink<Home>{home});
 }
 
 // The stop rule of an adaptive run.  Every operation is f64, in this order
@@ -2382,11 +2429,18 @@ PT_HD OriginU aa_origin(const AaEye& E, const UnitF& U, int u, F3 o32) {
     }
     return origin_q(U, o32);
 }
-template <bool FORCE64, bool BVH>
-PT_HD int aa_closest(const SceneK& S, const AaEye& E, D3 d0, const Spill& sp, D3* P, Counters* cnt) {
+// The query itself, one body for the three primary sources that trace from
+// the eye frame.  TABLE (the antialiasing kernels): `eye` is the scene's eye
+// and *E the wave's table.  Without it (the lens's point, a ray record's
+// origin inside the frame: unit_eye's bounds hold on the whole disc and frame,
+// prepare_scene's "all" box) every lane has its own origin, computes origin_q
+// for it, and E is null.  (E as a pointer: by reference or by value the lens
+// kernels' code moved, same size.  The f64 query of a TABLE build reads the
+// scene record's eye, as it always did.)
+template <bool FORCE64, bool BVH, bool TABLE>
+PT_HD int eye_closest(const SceneK& S, const AaEye* E, D3 eye, D3 d0, const Spill& sp, D3* P, Counters* cnt) {
 #if PT_AA_PRIMARY_M && PT_LIGHT_QUAD && PT_QUAD && PT_MARGIN
     if (!FORCE64) {
-        const D3 eye = ld3(S.kd + kKdEye);
         const D3 dn = unit(d0);
         sp.put3(kSpP, eye);
         sp.put3(kSpNd, d0);
@@ -2395,7 +2449,9 @@ PT_HD int aa_closest(const SceneK& S, const AaEye& E, D3 d0, const Spill& sp, D3
         ClosestAcc acc = closest_init();
         for (int u = 0; u < S.n_unit; ++u) {
             const UnitF U = S.unit_eye[u];
-            const OriginU O = aa_origin(E, U, u, o32);
+            OriginU O;
+            if constexpr (TABLE) O = aa_origin(*E, U, u, o32);
+            else O = origin_q(U, o32);
             if (closest_unit_m(U, O, U.grp == -1, d32, &acc))   // rare
                 fused_fallback<false, false, true, 2>(S, U, closest_bits_m(U, O, U.grp == -1, d32),
                                                       nullptr, &acc, sp, cnt, nullptr);
@@ -2411,118 +2467,48 @@ PT_HD int aa_closest(const SceneK& S, const AaEye& E, D3 d0, const Spill& sp, D3
         return closest_finish<false, false, BVH>(S, acc, eye, dn, P, cnt);
     }
 #endif
-    return closest<FORCE64, false, BVH>(S, ld3(S.eye), d0, -1, sp, P, cnt, true);
+    return closest<FORCE64, false, BVH>(S, TABLE ? ld3(S.eye) : eye, d0, -1, sp, P, cnt, true);
 }
 
-// One jittered primary ray: sample `sample` of J.pixel.  Returns the hit as
-// closest() does and leaves the origin (the hit point) and the incoming
-// direction of bounce 0 in the homes kSpP / kSpNd when it is an object's.
+// The jittered primary source.  primary(): one jittered ray, sample `sample`
+// of J.pixel; returns the hit as closest() does and leaves the origin (the hit
+// point) and the incoming direction of bounce 0 in the homes kSpP / kSpNd when
+// it is an object's.  A restart is this closest query over the eye-frame units
+// by the lanes whose path ended in this iteration; the other lanes of the wave
+// wait for it.
 template <bool FORCE64, bool BVH>
-PT_HD int aa_primary(const SceneK& S, const LaneJob& J, const AaPixel& X, const AaEye& E,
-                     uint32_t sample, const Spill& sp, Counters* cnt) {
-    double jx, jy;
-    aa_jitter(J.seed, J.pixel, sample, &jx, &jy);
-    const D3 d0 = aa_dir(S, X.W, X.H, X.ix, X.iy, jx, jy);
-    D3 P;
-    const int t = aa_closest<FORCE64, BVH>(S, E, d0, sp, &P, cnt);
-    if (t >= 0 && t < S.n_obj_tri) {
-        sp.put3(kSpP, P);
-        sp.put3(kSpNd, d0);   // (unnormalised, as the reference holds it: main.py:191)
-    }
-    return t;
-}
-
-// LaneSched's sample order with a primary ray per sample: every sample of
-// the lane, its first included, starts by tracing its own jittered ray
-// (start()).  A sample whose primary ray escapes (0) or hits the light
-// (light_rgb) is complete at once, and start() goes on to the next one until
-// a sample lands on an object or the lane's samples run out.  The restart is
-// a closest query over the eye-frame units by the lanes whose path ended in
-// this iteration; the other lanes of the wave wait for it.
-template <bool FORCE64, bool BVH>
-struct AaSched {
-    const LaneJob& J;
+struct AaRay {
+    static constexpr bool kCached = false;
+    static constexpr int kEye = 0;
     AaPixel X;
     AaEye E;
-    int si;
-    PT_HD uint32_t sample() const { return (uint32_t)(J.sample0 + si * J.sample_stride); }
-    PT_HD uint32_t pixel() const { return J.pixel; }
-    PT_HD bool start(const SceneK& S, const Spill& sp, int* tri, D3* acc, Counters* cnt) {
-        for (; si < J.n_samples; ++si) {
-            const int t = aa_primary<FORCE64, BVH>(S, J, X, E, sample(), sp, cnt);
-            if (t >= 0 && t < S.n_obj_tri) {
-                *tri = t;
-                return true;
-            }
-            if (t >= 0) *acc = *acc + ld3(S.kd + kKdLightRgb);   // main.py:214-215
+    PT_HD int primary(const SceneK& S, const LaneJob& J, uint32_t sample, const Spill& sp, Counters* cnt) const {
+        double jx, jy;
+        aa_jitter(J.seed, J.pixel, sample, &jx, &jy);
+        const D3 d0 = aa_dir(S, X.W, X.H, X.ix, X.iy, jx, jy);
+        D3 P;
+        const int t = eye_closest<FORCE64, BVH, true>(S, &E, ld3(S.kd + kKdEye), d0, sp, &P, cnt);
+        if (t >= 0 && t < S.n_obj_tri) {
+            sp.put3(kSpP, P);
+            sp.put3(kSpNd, d0);   // (unnormalised, as the reference holds it: main.py:191)
         }
-        return false;
-    }
-    template <bool COUNT>
-    PT_HD bool advance(const SceneK& S, bool done, const Spill& sp, int* tri, D3* acc, Counters* cnt) {
-        if (!done) return true;
-        ++si;
-        return start(S, sp, tri, acc, cnt);
+        return t;
     }
 };
 
-// MomentSched's form: each complete sample's colour goes to the home.
-template <bool FORCE64, bool BVH, class Home>
-struct AaMomentSched {
-    const LaneJob& J;
-    AaPixel X;
-    AaEye E;
-    int si;
-    Home& home;
-    PT_HD uint32_t sample() const { return (uint32_t)(J.sample0 + si * J.sample_stride); }
-    PT_HD uint32_t pixel() const { return J.pixel; }
-    PT_HD bool start(const SceneK& S, const Spill& sp, int* tri, Counters* cnt) {
-        for (; si < J.n_samples; ++si) {
-            const int t = aa_primary<FORCE64, BVH>(S, J, X, E, sample(), sp, cnt);
-            if (t >= 0 && t < S.n_obj_tri) {
-                *tri = t;
-                return true;
-            }
-            home.add(t < 0 ? d3(0, 0, 0) : ld3(S.kd + kKdLightRgb));
-        }
-        return false;
-    }
-    template <bool COUNT>
-    PT_HD bool advance(const SceneK& S, bool done, const Spill& sp, int* tri, D3* acc, Counters* cnt) {
-        if (!done) return true;
-        home.add(*acc);
-        *acc = d3(0, 0, 0);
-        ++si;
-        return start(S, sp, tri, cnt);
-    }
-};
-
-// All samples of one lane with jittered primary rays; returns the SUM of the
-// sample colours (render_lane's contract; bounces <= 0: main.py:192 never
-// runs).
+// render_lane / render_lane_moments with jittered primary rays (AaSched: the
+// sum form's scheduler, which the restart statistics of the host checks extend)
 template <bool FORCE64, bool BVH>
-PT_HD D3 render_lane_aa(const SceneK& S, const LaneJob& J, const AaPixel& X, const AaEye& E,
-                        const Spill& sp, Counters* cnt) {
-    D3 acc = d3(0, 0, 0);
-    if (J.n_samples <= 0 || J.bounces <= 0) return acc;
-    AaSched<FORCE64, BVH> q{J, X, E, 0};
-    int tri = -1;
-    if (q.start(S, sp, &tri, &acc, cnt)) render_loop<FORCE64, false, BVH>(S, J, tri, sp, cnt, q, &acc);
-    return acc;
+using AaSched = Sched<AaRay<FORCE64, BVH>, SumSink>;
+template <bool FORCE64, bool BVH>
+PT_HD D3 render_lane_aa(const SceneK& S, const LaneJob& J, const AaPixel& X, const AaEye& E, const Spill& sp,
+                        Counters* cnt) {
+    return render_lane_sampled<FORCE64, BVH>(S, J, AaRay<FORCE64, BVH>{X, E}, sp, cnt, SumSink{});
 }
-// render_lane_moments' form: the lane's J.n_samples colours into `home`.
 template <bool FORCE64, bool BVH, class Home>
-PT_HD void render_lane_moments_aa(const SceneK& S, const LaneJob& J, const AaPixel& X,
-                                  const AaEye& E, const Spill& sp, Counters* cnt, Home& home) {
-    if (J.n_samples <= 0) return;
-    if (J.bounces <= 0) {
-        for (int i = 0; i < J.n_samples; ++i) home.add(d3(0, 0, 0));
-        return;
-    }
-    AaMomentSched<FORCE64, BVH, Home> q{J, X, E, 0, home};
-    int tri = -1;
-    D3 acc = d3(0, 0, 0);
-    if (q.start(S, sp, &tri, cnt)) render_loop<FORCE64, false, BVH>(S, J, tri, sp, cnt, q, &acc);
+PT_HD void render_lane_moments_aa(const SceneK& S, const LaneJob& J, const AaPixel& X, const AaEye& E,
+                                  const Spill& sp, Counters* cnt, Home& home) {
+    render_lane_sampled<FORCE64, BVH>(S, J, AaRay<FORCE64, BVH>{X, E}, sp, cnt, MomentSink<Home>{home});
 }
 
 // ---------------------------------------------------------- thin lens --
@@ -2572,142 +2558,40 @@ PT_HD D3 lens_dir(const SceneK& S, int W, int H, int ix, int iy, double jx, doub
     return d3(x - ex, y - ey, 0.0 - S.kd[kKdEye + 2]);
 }
 
-// aa_closest from a lens point `eye`: the same unit form over unit_eye, whose
-// bounds hold on the whole disc (prepare_scene's "all" box holds it), but no
-// wave-shared table of origin terms — every lane has its own origin and
-// computes origin_q for it.  (A copy rather than a parameter of aa_closest:
-// the antialiasing kernels' code stays as it was.)
-template <bool FORCE64, bool BVH>
-PT_HD int lens_closest(const SceneK& S, D3 eye, D3 d0, const Spill& sp, D3* P, Counters* cnt) {
-#if PT_AA_PRIMARY_M && PT_LIGHT_QUAD && PT_QUAD && PT_MARGIN
-    if (!FORCE64) {
-        const D3 dn = unit(d0);
-        sp.put3(kSpP, eye);
-        sp.put3(kSpNd, d0);
-        const F3 o32 = to_f3(eye - ld3(S.kd + kKdCenter));
-        const F3 d32 = to_f3(dn);
-        ClosestAcc acc = closest_init();
-        for (int u = 0; u < S.n_unit; ++u) {
-            const UnitF U = S.unit_eye[u];
-            const OriginU O = origin_q(U, o32);
-            if (closest_unit_m(U, O, U.grp == -1, d32, &acc))   // rare
-                fused_fallback<false, false, true, 2>(S, U, closest_bits_m(U, O, U.grp == -1, d32),
-                                                      nullptr, &acc, sp, cnt, nullptr);
-        }
-        if (BVH && S.n_bnode) {   // the meshes, as closest()
-            if (S.bvh_depth < kBvhStack) {
-                bvh_closest<false>(S, o32, -1, d32, &acc, sp, cnt);
-            } else {
-                ShadowSet none = {};
-                bvh_pass<false, false>(S, o32, -1, false, true, &none, d32, &acc, sp, cnt);
-            }
-        }
-        return closest_finish<false, false, BVH>(S, acc, eye, dn, P, cnt);
-    }
-#endif
-    return closest<FORCE64, false, BVH>(S, eye, d0, -1, sp, P, cnt, true);
-}
-
-// aa_primary's form: the primary ray of sample `sample` from its lens point,
-// which stays in the home rows kSpLens for the sample's bounces (bounce<true>).
+// AaRay through the lens: the primary ray of sample `sample` from its lens
+// point, which stays in the home rows kSpLens for the sample's bounces
+// (bounce<1>).  AA: PT_FLAG_AA beside the lens.
 template <bool FORCE64, bool BVH, bool AA>
-PT_HD int lens_primary(const SceneK& S, const LaneJob& J, const AaPixel& X, uint32_t sample, const Spill& sp,
-                       Counters* cnt) {
-    double jx, jy, lx, ly;
-    lens_point<AA>(J.seed, J.pixel, sample, S.kd[kKdLensR], &jx, &jy, &lx, &ly);
-    const D3 eye = d3(S.kd[kKdEye] + lx, S.kd[kKdEye + 1] + ly, S.kd[kKdEye + 2]);
-    const D3 d0 = lens_dir(S, X.W, X.H, X.ix, X.iy, jx, jy, lx, ly, eye.x, eye.y);
-    sp.put(kSpLens, eye.x);
-    sp.put(kSpLens + 1, eye.y);
-    D3 P;
-    const int t = lens_closest<FORCE64, BVH>(S, eye, d0, sp, &P, cnt);
-    if (t >= 0 && t < S.n_obj_tri) {
-        sp.put3(kSpP, P);
-        sp.put3(kSpNd, d0);
-    }
-    return t;
-}
-
-// AaSched / AaMomentSched with lens_primary; AA: PT_FLAG_AA beside the lens.
-template <bool FORCE64, bool BVH, bool AA>
-struct LensSched {
-    static constexpr bool kLens = true;
-    const LaneJob& J;
+struct LensRay {
+    static constexpr bool kCached = false;
+    static constexpr int kEye = 1;
     AaPixel X;
-    int si;
-    PT_HD uint32_t sample() const { return (uint32_t)(J.sample0 + si * J.sample_stride); }
-    PT_HD uint32_t pixel() const { return J.pixel; }
-    PT_HD bool start(const SceneK& S, const Spill& sp, int* tri, D3* acc, Counters* cnt) {
-        for (; si < J.n_samples; ++si) {
-            const int t = lens_primary<FORCE64, BVH, AA>(S, J, X, sample(), sp, cnt);
-            if (t >= 0 && t < S.n_obj_tri) {
-                *tri = t;
-                return true;
-            }
-            if (t >= 0) *acc = *acc + ld3(S.kd + kKdLightRgb);
+    PT_HD int primary(const SceneK& S, const LaneJob& J, uint32_t sample, const Spill& sp, Counters* cnt) const {
+        double jx, jy, lx, ly;
+        lens_point<AA>(J.seed, J.pixel, sample, S.kd[kKdLensR], &jx, &jy, &lx, &ly);
+        const D3 eye = d3(S.kd[kKdEye] + lx, S.kd[kKdEye + 1] + ly, S.kd[kKdEye + 2]);
+        const D3 d0 = lens_dir(S, X.W, X.H, X.ix, X.iy, jx, jy, lx, ly, eye.x, eye.y);
+        sp.put(kSpLens, eye.x);
+        sp.put(kSpLens + 1, eye.y);
+        D3 P;
+        const int t = eye_closest<FORCE64, BVH, false>(S, nullptr, eye, d0, sp, &P, cnt);
+        if (t >= 0 && t < S.n_obj_tri) {
+            sp.put3(kSpP, P);
+            sp.put3(kSpNd, d0);
         }
-        return false;
-    }
-    template <bool COUNT>
-    PT_HD bool advance(const SceneK& S, bool done, const Spill& sp, int* tri, D3* acc, Counters* cnt) {
-        if (!done) return true;
-        ++si;
-        return start(S, sp, tri, acc, cnt);
-    }
-};
-template <bool FORCE64, bool BVH, bool AA, class Home>
-struct LensMomentSched {
-    static constexpr bool kLens = true;
-    const LaneJob& J;
-    AaPixel X;
-    int si;
-    Home& home;
-    PT_HD uint32_t sample() const { return (uint32_t)(J.sample0 + si * J.sample_stride); }
-    PT_HD uint32_t pixel() const { return J.pixel; }
-    PT_HD bool start(const SceneK& S, const Spill& sp, int* tri, Counters* cnt) {
-        for (; si < J.n_samples; ++si) {
-            const int t = lens_primary<FORCE64, BVH, AA>(S, J, X, sample(), sp, cnt);
-            if (t >= 0 && t < S.n_obj_tri) {
-                *tri = t;
-                return true;
-            }
-            home.add(t < 0 ? d3(0, 0, 0) : ld3(S.kd + kKdLightRgb));
-        }
-        return false;
-    }
-    template <bool COUNT>
-    PT_HD bool advance(const SceneK& S, bool done, const Spill& sp, int* tri, D3* acc, Counters* cnt) {
-        if (!done) return true;
-        home.add(*acc);
-        *acc = d3(0, 0, 0);
-        ++si;
-        return start(S, sp, tri, cnt);
+        return t;
     }
 };
 
 // render_lane_aa / render_lane_moments_aa through the lens
 template <bool FORCE64, bool BVH, bool AA>
-PT_HD D3 render_lane_lens(const SceneK& S, const LaneJob& J, const AaPixel& X, const Spill& sp,
-                          Counters* cnt) {
-    D3 acc = d3(0, 0, 0);
-    if (J.n_samples <= 0 || J.bounces <= 0) return acc;
-    LensSched<FORCE64, BVH, AA> q{J, X, 0};
-    int tri = -1;
-    if (q.start(S, sp, &tri, &acc, cnt)) render_loop<FORCE64, false, BVH>(S, J, tri, sp, cnt, q, &acc);
-    return acc;
+PT_HD D3 render_lane_lens(const SceneK& S, const LaneJob& J, const AaPixel& X, const Spill& sp, Counters* cnt) {
+    return render_lane_sampled<FORCE64, BVH>(S, J, LensRay<FORCE64, BVH, AA>{X}, sp, cnt, SumSink{});
 }
 template <bool FORCE64, bool BVH, bool AA, class Home>
 PT_HD void render_lane_moments_lens(const SceneK& S, const LaneJob& J, const AaPixel& X, const Spill& sp,
                                     Counters* cnt, Home& home) {
-    if (J.n_samples <= 0) return;
-    if (J.bounces <= 0) {
-        for (int i = 0; i < J.n_samples; ++i) home.add(d3(0, 0, 0));
-        return;
-    }
-    LensMomentSched<FORCE64, BVH, AA, Home> q{J, X, 0, home};
-    int tri = -1;
-    D3 acc = d3(0, 0, 0);
-    if (q.start(S, sp, &tri, cnt)) render_loop<FORCE64, false, BVH>(S, J, tri, sp, cnt, q, &acc);
+    render_lane_sampled<FORCE64, BVH>(S, J, LensRay<FORCE64, BVH, AA>{X}, sp, cnt, MomentSink<Home>{home});
 }
 
 // ------------------------------------------------ caller-supplied rays --
@@ -2717,7 +2601,7 @@ PT_HD void render_lane_moments_lens(const SceneK& S, const LaneJob& J, const AaP
 // the sample reads the eye; the Philox pixel word is the record's key.  The
 // primary ray is the same for every sample of a record, so its hit is traced
 // once per lane and cached in the home rows kSpP0 as a frame's is
-// (LaneSched).  What LaneSched rebuilds from two rows and the scene's eye, the
+// (FrameHit).  What FrameHit rebuilds from two rows and the scene's eye, the
 // direction, comes back from the record instead, and so does the specular
 // term's eye: with the direction read from the record the home has two free
 // rows (kSpD0's) beside the cached hit, and o and d are six values; a record
@@ -2737,7 +2621,7 @@ PT_HD bool rays_in_frame(const SceneK& S, double X, D3 o) {
            fabs(o.z - S.kd[kKdCenter + 2]) <= X;
 }
 
-// The record's primary hit: lens_closest's unit form with per-lane origin
+// The record's primary hit: eye_closest's unit form with per-lane origin
 // terms for an origin inside the frame, FORCE_F64's query for this ray alone
 // outside it (the bounces start on scene surfaces and take the filter again).
 // f32_route (may be null; the host checks): set when the filter's branch ran.
@@ -2746,88 +2630,41 @@ PT_HD int rays_primary(const SceneK& S, double frame_x, D3 o, D3 d0, const Spill
                        bool* f32_route = nullptr) {
     if (!FORCE64 && rays_in_frame(S, frame_x, o)) {
         if (f32_route) *f32_route = true;
-        return lens_closest<false, BVH>(S, o, d0, sp, P, cnt);
+        return eye_closest<false, BVH, false>(S, nullptr, o, d0, sp, P, cnt);
     }
     return closest<true, false, BVH>(S, o, d0, -1, sp, P, cnt, true);
 }
 
-// LaneSched / MomentSched with the record in the place of (kSpD0, the eye)
-struct RaySched {
-    static constexpr bool kRays = true;
-    const LaneJob& J;
+// FrameHit with the record in the place of (kSpD0, the eye)
+struct RayHit {
+    static constexpr bool kCached = true;
+    static constexpr int kEye = 2;
     const RayK* ray;
     int tri0;
-    int si;
-    PT_HD uint32_t sample() const { return (uint32_t)(J.sample0 + si * J.sample_stride); }
-    PT_HD uint32_t pixel() const { return J.pixel; }
     PT_HD const double* eye_o() const { return ray->o; }
-    template <bool COUNT>
-    PT_HD bool advance(const SceneK&, bool done, const Spill& sp, int* tri, D3*, Counters*) {
-        if (!done) return true;
-        if (++si >= J.n_samples) return false;
-        *tri = tri0;
-        sp.put3(kSpP, sp.get3(kSpP0));
+    PT_HD void begin(const Spill& sp, D3 P0) const {
+        sp.put3(kSpP0, P0);
+        sp.put3(kSpP, P0);
         sp.put3(kSpNd, ld3(ray->d));
-        return true;
     }
-};
-template <class Home>
-struct RayMomentSched {
-    static constexpr bool kRays = true;
-    const LaneJob& J;
-    const RayK* ray;
-    int tri0;
-    int si;
-    Home& home;
-    PT_HD uint32_t sample() const { return (uint32_t)(J.sample0 + si * J.sample_stride); }
-    PT_HD uint32_t pixel() const { return J.pixel; }
-    PT_HD const double* eye_o() const { return ray->o; }
     template <bool COUNT>
-    PT_HD bool advance(const SceneK&, bool done, const Spill& sp, int* tri, D3* acc, Counters*) {
-        if (!done) return true;
-        home.add(*acc);
-        *acc = d3(0, 0, 0);
-        if (++si >= J.n_samples) return false;
+    PT_HD void restart(const SceneK&, const Spill& sp, int* tri, Counters*) const {
         *tri = tri0;
         sp.put3(kSpP, sp.get3(kSpP0));
         sp.put3(kSpNd, ld3(ray->d));
-        return true;
     }
 };
 
 // render_lane / render_lane_moments for a record: tri0, P0 its primary hit
 template <bool FORCE64, bool BVH>
-PT_HD D3 render_lane_rays(const SceneK& S, const LaneJob& J, const RayK* ray, int tri0, D3 P0,
-                          const Spill& sp, Counters* cnt) {
-    D3 acc = d3(0, 0, 0);
-    if (J.n_samples <= 0 || J.bounces <= 0) return acc;
-    if (tri0 < 0 || tri0 >= S.n_obj_tri) {   // the ray escapes or hits the light
-        const D3 v = tri0 < 0 ? d3(0, 0, 0) : ld3(S.kd + kKdLightRgb);
-        for (int i = 0; i < J.n_samples; ++i) acc = acc + v;
-        return acc;
-    }
-    sp.put3(kSpP0, P0);
-    sp.put3(kSpP, P0);
-    sp.put3(kSpNd, ld3(ray->d));
-    RaySched q{J, ray, tri0, 0};
-    render_loop<FORCE64, false, BVH>(S, J, tri0, sp, cnt, q, &acc);
-    return acc;
+PT_HD D3 render_lane_rays(const SceneK& S, const LaneJob& J, const RayK* ray, int tri0, D3 P0, const Spill& sp,
+                          Counters* cnt) {
+    return render_lane_cached<FORCE64, false, BVH>(S, J, RayHit{ray, tri0}, P0, sp, cnt, SumSink{});
 }
 template <bool FORCE64, bool BVH, class Home>
 PT_HD void render_lane_moments_rays(const SceneK& S, const LaneJob& J, const RayK* ray, int tri0, D3 P0,
                                     const Spill& sp, Counters* cnt, Home& home) {
-    if (J.n_samples <= 0) return;
-    if (J.bounces <= 0 || tri0 < 0 || tri0 >= S.n_obj_tri) {
-        const D3 v = (J.bounces <= 0 || tri0 < 0) ? d3(0, 0, 0) : ld3(S.kd + kKdLightRgb);
-        for (int i = 0; i < J.n_samples; ++i) home.add(v);
-        return;
-    }
-    sp.put3(kSpP0, P0);
-    sp.put3(kSpP, P0);
-    sp.put3(kSpNd, ld3(ray->d));
-    D3 acc = d3(0, 0, 0);
-    RayMomentSched<Home> q{J, ray, tri0, 0, home};
-    render_loop<FORCE64, false, BVH>(S, J, tri0, sp, cnt, q, &acc);
+    render_lane_cached<FORCE64, false, BVH>(S, J, RayHit{ray, tri0}, P0, sp, cnt, MomentSink<Home>{home});
 }
 
 }  // namespace pt

@@ -2,7 +2,7 @@
 // §4.4): the path loop for caller-supplied primary rays.  A work-item is
 // (record, sample slice) as k_render_list's is (list entry, sample slice); the
 // primary ray, the specular term's eye and the Philox pixel word come from the
-// record (pt_path.h RaySched / RayMomentSched).  Origins differ across a
+// record (pt_path.h RayHit; SumSink / MomentSink).  Origins differ across a
 // wave, so each lane computes its own origin terms as the lens kernels do,
 // but the primary hit is traced once per lane and cached as k_render's is.
 // A translation unit of its own (build.py AA_UNITS), so that no other unit's
@@ -11,8 +11,8 @@
 #include "pt_rays.h"
 
 // k_render_list's block shape, spill home and reduction.  MOM: the moments
-// S, Q as well, summed sample by sample (RayMomentSched), the mean from S;
-// without them the samples are summed as k_render sums them (RaySched).
+// S, Q as well, summed sample by sample (MomentSink), the mean from S;
+// without them the samples are summed as k_render sums them (SumSink).
 template <bool FORCE64, bool BVH, bool MOM>
 __global__ __launch_bounds__(kRenderBlock, PT_RENDER_WAVES) void k_render_rays(
     SceneK S, RaysK R, const RayK* __restrict__ rays, void* __restrict__ out, double* __restrict__ outS,
@@ -42,8 +42,8 @@ __global__ __launch_bounds__(kRenderBlock, PT_RENDER_WAVES) void k_render_rays(
         // the primary hit once per lane: every sample of the record shares it
         if (J.n_samples > 0 && R.bounces > 0)
             tri0 = rays_primary<FORCE64, BVH>(S, R.frame_x, ld3(ray->o), ld3(ray->d), sp, &P0, &cnt);
-        if constexpr (MOM) render_lane_moments_rays<FORCE64, BVH>(S, J, ray, tri0, P0, sp, &cnt, M);
-        else acc = render_lane_rays<FORCE64, BVH>(S, J, ray, tri0, P0, sp, &cnt);
+        if constexpr (MOM) render_lane_cached<FORCE64, false, BVH>(S, J, RayHit{ray, tri0}, P0, sp, &cnt, MomentSink<MomentRegs>{M});
+        else acc = render_lane_cached<FORCE64, false, BVH>(S, J, RayHit{ray, tri0}, P0, sp, &cnt, SumSink{});
     }
     D3 s = MOM ? M.sum() : acc, q = M.sumsq();
     for (uint32_t m = 1; m < R.split; m <<= 1) {

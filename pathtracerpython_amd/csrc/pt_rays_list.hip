@@ -4,7 +4,7 @@
 // record rays[e] in the place of pixel e's primary ray, as k_render_rays is
 // k_render's: a work-item is (list entry, sample slice) (rays_list_job,
 // pt_job.h), the primary hit is traced once per lane and pass with per-lane
-// origin terms (rays_primary), the paths run through render_lane_moments_rays.
+// origin terms (rays_primary), the paths run through render_lane_cached (RayHit, MomentSink).
 // A translation unit of its own (build.py AA_UNITS), so that no other unit's
 // code moves.  pt_hip.hip launches both through the functions at the end.
 #include "pt_render.h"
@@ -37,7 +37,7 @@ __global__ __launch_bounds__(kRenderBlock, PT_LIST_WAVES) void k_render_rays_lis
         // the primary hit once per lane and pass: every sample of the record shares it
         if (j.J.n_samples > 0 && R.bounces > 0)
             tri0 = rays_primary<FORCE64, BVH>(S, R.frame_x, ld3(j.ray->o), ld3(j.ray->d), sp, &P0, &cnt);
-        render_lane_moments_rays<FORCE64, BVH>(S, j.J, j.ray, tri0, P0, sp, &cnt, M);
+        render_lane_cached<FORCE64, false, BVH>(S, j.J, RayHit{j.ray, tri0}, P0, sp, &cnt, MomentSink<MomentRegs>{M});
     }
     D3 s = M.sum(), q = M.sumsq();
     for (uint32_t m = 1; m < R.split; m <<= 1) {

@@ -68,6 +68,24 @@ __device__ __forceinline__ void store_pixel(const RenderK& R, const SlotJob& j, 
     }
 }
 
+// k_render's work-item -> (pixel, lane of its split) mapping, tail rows
+// included (RenderK, pt_job.h), for k_render_aa and k_render_lens: pl the
+// launch-local pixel, c the lane among the pixel's `split`.  Each kernel fills
+// its LaneJob itself: a helper returning the job moved the two units' code
+// (pt_aa.hip -1792 B, pt_lens.hip +1280 B), one filling a reference as well
+// (same sizes, other registers).
+struct PixelMap {
+    uint32_t pl, c, split;
+    bool valid;
+};
+__device__ __forceinline__ PixelMap pixel_map(const RenderK& R, uint32_t tid) {
+    const bool tail = tid >= R.tail_lane;   // wave-uniform
+    const uint32_t slog = tail ? R.tail_log2 : R.split_log2, split = 1u << slog;
+    const uint32_t lt = tail ? tid - R.tail_lane : tid;
+    const uint32_t pl = (tail ? R.tail_pix : 0u) + (lt >> slog);
+    return PixelMap{pl, lt & (split - 1u), split, pl < (tail ? R.npix : R.tail_pix)};
+}
+
 // The primary ray's closest hit (main.py:191, :197-205), shared by the
 // `split` lanes of a pixel (scenes without a BVH): lane c tests the
 // eye-frame units c, c + split, ... (a per-lane unit index: vector loads of
@@ -124,7 +142,8 @@ __global__ __launch_bounds__(kRenderBlock, PT_RENDER_WAVES) void k_render(SceneK
     const Spill sp{&spill[0][threadIdx.x], (int)kRenderBlock};
     PT_STAMP(k0);
     // (slot_job's mapping written out: the register allocation of this kernel
-    // is sensitive to what stays live across the render loop)
+    // is sensitive to what stays live across the render loop; through
+    // pixel_map pt_hip.hip's instantiations differ, same size)
     const uint32_t tid = blockIdx.x * kRenderBlock + threadIdx.x;
     const bool tail = tid >= R.tail_lane;   // wave-uniform
     const uint32_t slog = tail ? R.tail_log2 : R.split_log2, split = 1u << slog;
@@ -167,7 +186,7 @@ __global__ __launch_bounds__(kRenderBlock, PT_RENDER_WAVES) void k_render(SceneK
             PT_PHASE_FLUSH_AT(5, k1 - k0);
         }
 #endif
-        acc = render_lane<FORCE64, COUNT, BVH>(S, J, d0, tri0, P0, sp, &cnt);
+        acc = render_lane_cached<FORCE64, COUNT, BVH>(S, J, FrameHit{tri0, d0}, P0, sp, &cnt, SumSink{});
     }
 #if defined(PT_PHASE_CLOCKS)
     {

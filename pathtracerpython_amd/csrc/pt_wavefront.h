@@ -200,12 +200,12 @@ PT_HD uint32_t wf_start(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, WfC
     return kWfWantClosest;
 }
 
-// Antialiasing (PT_FLAG_AA, pt_path.h AaSched): the slot has no cached primary
+// Antialiasing (PT_FLAG_AA, pt_path.h AaRay): the slot has no cached primary
 // hit.  Sample W->si starts with its own closest query from the eye along the
 // jittered ray: wf_start's body for that d0, the candidates of the eye-frame
 // units into the slot's own query record (walked like a bounce's query, the
 // slot's spill home holding the eye and d0).  The eye units are tested in
-// aa_closest's unit form (PT_WF_AA_PRIMARY_M: origin_q / closest_unit_m, the
+// eye_closest's unit form (PT_WF_AA_PRIMARY_M: origin_q / closest_unit_m, the
 // ambiguous members decided in f64) or in wf_start's per-triangle form; both
 // are conservative filters in front of the same closest_finish.
 #ifndef PT_WF_AA_PRIMARY_M
@@ -241,13 +241,13 @@ PT_HD uint32_t wf_aa_start(const SceneK& S, const LaneJob& J, const AaPixel& X, 
     return kWfWantClosest;
 }
 
-// The thin lens (PT_FLAG_LENS, pt_path.h lens_primary): wf_aa_start with the
+// The thin lens (PT_FLAG_LENS, pt_path.h LensRay): wf_aa_start with the
 // lens rule.  Sample W->si starts at its own lens point eye' along lens_dir's
 // ray; eye' is the query's origin (kSpP, which wf_finish reads back as the
 // origin of closest_finish) and stays in the record's rows kSpLens for the
 // sample's bounces (bounce<true>; these forms cache no primary hit, so the
-// rows are free).  The eye units are tested in lens_closest's form from the
-// slot's own origin.  AA: PT_FLAG_AA beside the lens, a template parameter
+// rows are free).  The eye units are tested in eye_closest's per-lane form
+// from the slot's own origin.  AA: PT_FLAG_AA beside the lens, a template parameter
 // down to the kernels (pt_path.h lens_point).
 template <bool AA>
 PT_HD uint32_t wf_lens_start(const SceneK& S, const LaneJob& J, const AaPixel& X, WfPath* W,
@@ -323,7 +323,7 @@ PT_HD uint32_t wf_begin_bounce_lens(const SceneK& S, const LaneJob& J, WfPath* W
     constexpr const double* eye_o = nullptr;
 #include "pt_wf_bounce.h"
 }
-// caller-supplied rays: the eye is the record's origin (bounce<2>, RaySched::eye_o)
+// caller-supplied rays: the eye is the record's origin (bounce<2>, RayHit::eye_o)
 template <bool KEY = false>
 PT_HD uint32_t wf_begin_bounce_rays(const SceneK& S, const LaneJob& J, const double* eye_o, WfPath* W,
                                     WfShadowQ* shq, WfClosestQ* cq) {
@@ -339,17 +339,17 @@ PT_HD uint32_t wf_begin_bounce_rays(const SceneK& S, const LaneJob& J, const dou
 //
 // Home: where a path's colour goes when the path ends.  WfSum (the uniform
 // render): nowhere, W->acc runs on over the slot's samples.  WfMoments (the
-// list form, an accumulator pass): MomentSched's rule (pt_path.h) — the
+// list form, an accumulator pass): MomentSink's rule (pt_path.h) — the
 // colour is added to the slot's six sums and W->acc restarts at 0, wherever
 // `done` is set below; a primary ray that escapes or hits the light adds its
-// constant n_samples times, as render_lane_moments does.
+// constant n_samples times, as render_lane_cached does for a MomentSink.
 struct WfSum { static constexpr bool kMoments = false; };
 struct WfMoments : MomentMem { static constexpr bool kMoments = true; };
 //
 // AA (antialiasing): a primary query per sample, in the slot's own record cq
 // (wf_aa_start), and nothing cached in kSpD0 / kSpP0 / tri0.  A sample whose
-// primary ray escapes or hits the light is complete at once (AaSched /
-// AaMomentSched's order), and a path's end restarts from the eye.  Returns
+// primary ray escapes or hits the light is complete at once (Sched::start's
+// order), and a path's end restarts from the eye.  Returns
 // kWfNextPrimary when the slot's next sample is to be started in this shade
 // step (wf_aa_start; d0 and pq are unused).
 // LENS (the thin lens, wf_lens_start): AA's per-sample form whether or not the
@@ -357,7 +357,7 @@ struct WfMoments : MomentMem { static constexpr bool kMoments = true; };
 // origin being the sample's lens point, which kSpP still holds.
 // RAYS (caller-supplied rays, wf_rays_primary_step): the centre-ray form — a
 // primary query per record, its hit cached in tri0 / kSpP0 — with the record
-// `ray` in the place of (the job's d0, kSpD0, the scene's eye), as RaySched
+// `ray` in the place of (the job's d0, kSpD0, the scene's eye), as RayHit
 // has it: the home keeps no direction, a sample's restart reads ray->d.  A
 // record whose primary query was decided in f64 (pq->pad = kWfPrimF64) has
 // issued no walk: its hit is in its first slot W0 (tri0, kSpP0).
@@ -369,11 +369,11 @@ PT_HD int wf_finish(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, const W
                     const WfPath* W0 = nullptr) {
     const Spill sp{W->sp, 1};
     if constexpr (AA || LENS) {
-        if (W->state() == kWfPrimary) {   // aa_primary: closest(eye, d0 of this sample)
+        if (W->state() == kWfPrimary) {   // AaRay::primary: closest(eye, d0 of this sample)
             const D3 dj = sp.get3(kSpNd);
             D3 P0 = d3(0, 0, 0);
             D3 eye;
-            if constexpr (LENS) eye = sp.get3(kSpP);   // lens_primary: from the sample's lens point
+            if constexpr (LENS) eye = sp.get3(kSpP);   // LensRay::primary: from the sample's lens point
             else eye = ld3(S.eye);
             const int tri0 = closest_finish<false, false, true>(S, wf_get_acc(*cq), eye, unit(dj),
                                                                 &P0, nullptr);
@@ -478,7 +478,7 @@ PT_HD int wf_finish(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, const W
         }
     }
     if (done) {
-        if constexpr (Home::kMoments) {   // MomentSched::advance
+        if constexpr (Home::kMoments) {   // MomentSink::end
             home.add(acc);
             acc = d3(0, 0, 0);
         }
@@ -495,7 +495,7 @@ PT_HD int wf_finish(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, const W
             tri = W->tri0;
             k = 1.0;
             sp.put3(kSpP, sp.get3(kSpP0));
-            if constexpr (RAYS) sp.put3(kSpNd, ld3(ray->d));   // RaySched::advance
+            if constexpr (RAYS) sp.put3(kSpNd, ld3(ray->d));   // RayHit::restart
             else sp.put3(kSpNd, d3(sp.get(kSpD0), sp.get(kSpD0 + 1), 0.0 - S.eye[2]));
         }
     }
@@ -588,7 +588,7 @@ PT_HD uint32_t wf_primary_step(const SceneK& S, const Src& src, uint32_t entry, 
 }
 
 // The primary query of record `entry` of a ray batch (its `split` slots share
-// it): wf_start's body from the record's origin, in lens_closest's unit form
+// it): wf_start's body from the record's origin, in eye_closest's unit form
 // (per-lane origin_q over unit_eye) — what rays_primary runs for an origin
 // inside the f32 filter's frame; the home rows kSpP / kSpNd of the entry's
 // first slot get o and d.  An origin outside the frame (a NaN included,

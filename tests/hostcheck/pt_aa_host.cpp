@@ -1,5 +1,5 @@
 // pt_aa_host.cpp — TEST INFRASTRUCTURE.  The antialiasing lane code (pt_path.h
-// aa_jitter / aa_dir, AaSched / AaMomentSched through render_loop) compiled
+// aa_jitter / aa_dir, AaRay with either sink through render_loop) compiled
 // for the host on top of pt_hostcheck.cpp, so the CPU suite can check the rule
 // of PT_FLAG_AA (include/pt_capi.h) against its numpy restatement and the
 // oracle without a GPU.  Built by tests/test_aa_host.py into a temporary
@@ -55,8 +55,8 @@ D3 xor_reduce(std::vector<D3> v) {
 // The whole frame of p with PT_FLAG_AA's lane code, `lanes` (a power of two)
 // emulated lanes per pixel: lane c takes samples sample_begin + c, + lanes,
 // ... and the lanes reduce in store_pixel's xor order.  sum: the colour sums
-// of the uniform form (AaSched); S, Q: the moments of the list form
-// (AaMomentSched), all [H*W][3] f64 in image orientation.
+// of the uniform form (SumSink); S, Q: the moments of the list form
+// (MomentSink), all [H*W][3] f64 in image orientation.
 int hc_render_aa(const pt_scene_desc* d, const pt_render_params* p, int force64, int32_t lanes,
                  double* sum, double* S, double* Q) {
     HostScene H;

@@ -1,5 +1,5 @@
 // pt_accum_host.cpp — TEST INFRASTRUCTURE.  The adaptive sampler's lane code
-// (pt_path.h MomentSched / render_lane_moments, moment_err, adapt_active,
+// (pt_path.h MomentSink / render_lane_moments, moment_err, adapt_active,
 // adapt_k) compiled for the host on top of pt_hostcheck.cpp, so the CPU suite
 // can check the per-pixel moments against the oracle's per-sample colours and
 // the stop rule against numpy without a GPU.  Built by tests/test_adaptive.py

@@ -1,5 +1,5 @@
 // pt_lens_host.cpp — TEST INFRASTRUCTURE.  The thin-lens lane code (pt_path.h
-// lens_point / lens_window / lens_dir, LensSched / LensMomentSched through
+// lens_point / lens_window / lens_dir, LensRay with either sink through
 // render_loop) compiled for the host on top of pt_aa_host.cpp, so the CPU
 // suite can check the rule of PT_FLAG_LENS (include/pt_capi.h) against its
 // numpy restatement (tests/lens_ref.py) and the oracle without a GPU.  Built

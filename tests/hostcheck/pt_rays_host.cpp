@@ -1,5 +1,5 @@
 // pt_rays_host.cpp — TEST INFRASTRUCTURE.  The ray lane code (pt_path.h
-// rays_in_frame / rays_primary, RaySched / RayMomentSched through render_loop)
+// rays_in_frame / rays_primary, RayHit with either sink through render_loop)
 // compiled for the host on top of pt_lens_host.cpp, so the CPU suite can check
 // the rule of pt_radiance (include/pt_capi.h) against the oracle without a
 // GPU.  Built by tests/test_rays_host.py into a temporary directory with the
@@ -11,7 +11,7 @@ extern "C" {
 // k_render_rays on the host: for each of the n records, `lanes` (a power of
 // two) emulated lanes, lane c taking samples sample_begin + c, + lanes, ...,
 // reduced in the kernel's xor order.  sum: the colour sums of the form without
-// moments (RaySched); S, Q: the moments' (RayMomentSched), all [n][3] f64 in
+// moments (SumSink); S, Q: the moments' (MomentSink), all [n][3] f64 in
 // the records' order.  route[i]: what rays_primary itself reports — 1 when no
 // lane's primary query ran the f32 filter's branch (forced f64, or an origin
 // outside the frame), 0 when every lane's did, -1 when the lanes disagree.

@@ -1,5 +1,5 @@
 """Antialiasing on the host (PT_FLAG_AA, include/pt_capi.h; pt_path.h aa_jitter,
-aa_dir, AaSched, AaMomentSched): the rule's helpers against their numpy
+aa_dir, AaRay with either sink): the rule's helpers against their numpy
 restatement bit for bit, the sample loop compiled for the host against the
 oracle on shifted screen windows (tests/aa_ref.py), the stop rule on
 antialiased frames, and the checkpoint keys.  The GPU cases are

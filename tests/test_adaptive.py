@@ -1,5 +1,5 @@
 """Adaptive sampling on the host (pathtracerpython_amd/adaptive.py, pt_path.h
-MomentSched): the kernel's moment accumulation compiled for the host against
+MomentSink): the kernel's moment accumulation compiled for the host against
 the oracle's per-sample colours, the stop rule against numpy bit for bit, the
 pass loop against a stand-in accumulator, the CLI refusals and the ABI.  The
 GPU cases are tests/test_gpu_adaptive.py."""

@@ -1,5 +1,5 @@
 """The thin-lens camera on the host (PT_FLAG_LENS, include/pt_capi.h; pt_path.h
-lens_point, lens_window, lens_dir, LensSched, LensMomentSched): the rule's
+lens_point, lens_window, lens_dir, LensRay with either sink): the rule's
 helpers against their numpy restatement, the sample loop compiled for the host
 against the oracle on shifted eyes and screen windows (tests/lens_ref.py), the
 bitwise equalities of the rule, the f32 filter's self-test from the lens disc,

@@ -1,5 +1,5 @@
 """Radiance for caller-supplied rays on the host (pt_radiance, include/pt_capi.h;
-pt_path.h rays_in_frame, rays_primary, RaySched, RayMomentSched): the lane code
+pt_path.h rays_in_frame, rays_primary, RayHit with either sink): the lane code
 compiled for the host (tests/hostcheck/pt_rays_host.cpp) against the oracle on
 descriptors with the ray's origin as the eye (tests/rays_ref.py), the bitwise
 equalities of the rule, the f32 filter's self-test from the box, the records of
