@@ -2201,11 +2201,13 @@ PT_HD void render_loop(const SceneK& S, const LaneJob& J, int tri, const Spill& 
 // sink.  With a SumSink they return the SUM of the lane's sample colours; with
 // a MomentSink they return nothing, the J.n_samples colours went to the home
 // one by one.  No bounces: main.py:192 never runs, the sum is 0 and a home
-// gets samples of 0.  The kernels call these two directly, the policies as
-// temporaries: through a forwarding function per pair every kernel's code
-// moved.  The eight forwards render_lane, render_lane_moments, ..._aa,
-// ..._lens, ..._rays below keep the earlier signatures for the host checks
-// (tests/hostcheck), where an inlining level changes nothing.
+// gets samples of 0.  The kernels and the host checks (tests/hostcheck) call
+// these two directly, the policies as temporaries: through a forwarding
+// function per pair every kernel's code moved.  The eight forwards render_lane,
+// render_lane_moments, ..._aa, ..._lens, ..._rays below keep the earlier
+// signatures and have no caller here any more: they stay so that the host
+// checks as they stood before their lane driver still build against this
+// header.
 //
 // A cached primary hit (prim.tri0, P0): a primary ray that escapes or hits
 // the light gives constant samples, added one by one.  The counters take the
@@ -2497,7 +2499,7 @@ struct AaRay {
 };
 
 // render_lane / render_lane_moments with jittered primary rays (AaSched: the
-// sum form's scheduler, which the restart statistics of the host checks extend)
+// sum form's scheduler, Sched<AaRay<..>, SumSink>, under its earlier name)
 template <bool FORCE64, bool BVH>
 using AaSched = Sched<AaRay<FORCE64, BVH>, SumSink>;
 template <bool FORCE64, bool BVH>

@@ -19,7 +19,7 @@
 //
 // A query work-item takes the next query from its list (one atomic per wave)
 // as soon as its walk ends, so the waves stay full until the list drains.
-// The per-slot arithmetic is that of render_lane (pt_path.h) in the same
+// The per-slot arithmetic is that of render_loop (pt_path.h) in the same
 // order, so the framebuffer is bitwise identical to k_render's (tested).
 // Path state lives in HBM between the kernels: WfPath (256 B per slot, the
 // f64 spill home included) and the query records.
@@ -283,8 +283,8 @@ PT_HD uint32_t wf_lens_start(const SceneK& S, const LaneJob& J, const AaPixel& X
     return kWfWantClosest;
 }
 
-// The body of render_lane's loop up to its walks: RNG, light samples, next
-// ray, the fused pass over the uniform units (pt_path.h render_lane).
+// The body of render_loop up to its walks: RNG, light samples, next
+// ray, the fused pass over the uniform units (pt_path.h render_loop).
 // The sort key of a query origin (the BVH frame; render_wavefront's sort):
 // 4 bits per axis over the root node's grid, in Morton order (neighbouring
 // cells get neighbouring keys)
@@ -400,7 +400,7 @@ PT_HD int wf_finish(const SceneK& S, const LaneJob& J, D3 d0, WfPath* W, const W
             return kWfNextNone;
         }
     } else
-    if (W->state() == kWfPrimary) {   // k_render: closest(eye, d0) then render_lane's prologue
+    if (W->state() == kWfPrimary) {   // k_render: closest(eye, d0) then render_lane_cached's prologue
         D3 P0 = d3(0, 0, 0);
         int tri0;
         if constexpr (RAYS) {

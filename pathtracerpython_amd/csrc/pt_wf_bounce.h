@@ -18,7 +18,7 @@
     const int ogrp = S.tri_grp[tri];
     ShadowSet sh;
     uint32_t w[16];
-#if PT_RNG_PERBLOCK   // as render_lane: one Philox block per light sample, where it is used
+#if PT_RNG_PERBLOCK   // as render_loop: one Philox block per light sample, where it is used
 #pragma unroll
     for (int k = 0; k < kLightSamples; ++k) {
         uint32_t c[4];

@@ -13,12 +13,13 @@ import argparse
 import ctypes as C
 import json
 import os
-import subprocess
 import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import hostlib  # noqa: E402  (tests/hostlib.py: the hostcheck Makefile's rule)
 
 
 def main():
@@ -33,12 +34,7 @@ def main():
     from pathtracerpython_amd._abi import PT_FLAG_AA, make_params
     from pathtracerpython_amd.pack import pack_scene
     scene_reader.VERBOSE = False
-    d = os.path.join(ROOT, "tests", "hostcheck")
-    out = os.path.join(tempfile.mkdtemp(), "libaahost.so")
-    subprocess.run([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-shared",
-                    "-ffp-contract=off", "-Wno-unknown-pragmas", "-o", out, "pt_aa_host.cpp"],
-                   cwd=d, check=True)
-    lib = C.CDLL(out)
+    lib = hostlib.build(tempfile.mkdtemp(), "pt_aa_host")
     pk = pack_scene(scene_reader.Scene(os.path.join(ROOT, "scenes", "cornell", "cornellroom.sdl")))
     p = make_params(a.size, a.size, a.spp, a.bounces, a.seed, PT_FLAG_AA)
     v = (C.c_int64 * 6)()

@@ -3,10 +3,8 @@
 // for the host on top of pt_hostcheck.cpp, so the CPU suite can check the rule
 // of PT_FLAG_AA (include/pt_capi.h) against its numpy restatement and the
 // oracle without a GPU.  Built by tests/test_aa_host.py into a temporary
-// directory with the hostcheck Makefile's g++ flags.
+// directory by the hostcheck Makefile's pattern rule (tests/hostlib.py).
 #include "pt_hostcheck.cpp"
-
-#include <vector>
 
 extern "C" {
 
@@ -18,39 +16,69 @@ void hc_aa_jitter(uint64_t seed, uint32_t pixel, uint32_t sample, double* out) {
 int hc_aa_dir(const pt_scene_desc* d, int32_t W, int32_t H, int32_t ix, int32_t iy, double jx,
               double jy, double* ortho, double* d0) {
     HostScene Hs;
-    if (!prepare_scene(d, &Hs).empty()) return -1;
-    bind_host(&Hs);
+    if (!open_scene(d, &Hs)) return -1;
     aa_window(Hs.k, W, H, jx, jy, ortho);
     const D3 v = aa_dir(Hs.k, W, H, ix, iy, jx, jy);
     d0[0] = v.x; d0[1] = v.y; d0[2] = v.z;
     return 0;
 }
 
+}  // extern "C"
 namespace {
-const AaEye kNoEye{nullptr, 0};   // (the device's per-wave table of the eye's origin terms: none here)
-LaneJob lane_job(const pt_render_params* p, int ix, int iy, int32_t sample0, int32_t stride,
-                 int32_t n_samples) {
-    LaneJob J;
-    J.seed = p->seed;
-    J.pixel = (uint32_t)ix * (uint32_t)p->height + (uint32_t)iy;
-    J.sample0 = sample0;
-    J.sample_stride = stride;
-    J.n_samples = n_samples;
-    J.bounces = p->bounces;
-    J.rr_depth = (p->flags & PT_FLAG_RR) ? p->rr_depth : -1;
-    return J;
+// The whole frame of p, `lanes` (a power of two) emulated lanes per pixel with
+// both sinks.  primary(ix, iy, f): calls f(F64, prim, P0) with the pixel's
+// primary source, as with_primary does.
+template <class Primary>
+void render_frame(Host& h, const pt_render_params* p, int32_t lanes, double* sum, double* S, double* Q,
+                  Primary&& primary) {
+    for (int iy = 0; iy < p->height; ++iy)
+        for (int ix = 0; ix < p->width; ++ix)
+            primary(ix, iy, [&](auto F64, const auto& prim, D3 P0) {
+                store_lanes(p, pixel_key(p, ix, iy), lanes, image_index(p, ix, iy), sum, S, Q,
+                            [&](const LaneJob& J) { return both_sinks<decltype(F64)::value>(h, J, prim, P0); });
+            });
 }
-// the xor butterfly of store_pixel over `lanes` values; lane 0's result
-D3 xor_reduce(std::vector<D3> v) {
-    const size_t n = v.size();
-    for (size_t m = 1; m < n; m <<= 1) {
-        std::vector<D3> w(n);
-        for (size_t i = 0; i < n; ++i) w[i] = v[i] + v[i ^ m];
-        v = w;
+// An adaptive run on the host: the accumulator's pass loop (select by
+// moment_err / adapt_active, adapt_k more samples from sample n[e] on for each
+// listed pixel, one lane per pixel, its primary source as render_frame's) until
+// no pixel is active.  S, Q [H*W][3], n [H*W] in image orientation; returns the
+// passes made, or -3.
+template <class Primary>
+int accum_passes(Host& h, const pt_render_params* p, const AdaptK& A, double* S, double* Q, uint32_t* n,
+                 Primary&& primary) {
+    const size_t np = (size_t)p->width * p->height;
+    for (size_t i = 0; i < 3 * np; ++i) S[i] = Q[i] = 0.0;
+    for (size_t i = 0; i < np; ++i) n[i] = 0;
+    for (int pass = 0; pass <= (int)A.max_spp + 1; ++pass) {
+        bool any = false;
+        for (size_t e = 0; e < np; ++e) {
+            const double err = moment_err(S + 3 * e, Q + 3 * e, n[e], A.floor);
+            if (!adapt_active(n[e], err, A)) continue;
+            const uint32_t k = adapt_k(n[e], A);
+            if (k == 0) continue;
+            any = true;
+            const int row = (int)(e / p->width), ix = (int)(e % p->width), iy = p->height - 1 - row;
+            const LaneJob J = lane_job(p, pixel_key(p, ix, iy), (int32_t)n[e], 1, (int32_t)k);
+            MomentRegs M;
+            M.clear();
+            primary(ix, iy, [&](auto F64, const auto& prim, D3 P0) {
+                run_lane<decltype(F64)::value, false>(h, J, prim, P0, MomentSink<MomentRegs>{M});
+            });
+            add3(S + 3 * e, M.sum());
+            add3(Q + 3 * e, M.sumsq());
+            n[e] += k;
+        }
+        if (!any) return pass;
     }
-    return v[0];
+    return -3;
+}
+// the jittered source of pixel (ix, iy) alone, as f(F64, prim, P0)
+template <bool F64, class F>
+void aa_primary(const pt_render_params* p, int ix, int iy, F&& f) {
+    f(std::bool_constant<F64>{}, AaRay<F64, true>{AaPixel{p->width, p->height, ix, iy}, kNoEye}, d3(0, 0, 0));
 }
 }  // namespace
+extern "C" {
 
 // The whole frame of p with PT_FLAG_AA's lane code, `lanes` (a power of two)
 // emulated lanes per pixel: lane c takes samples sample_begin + c, + lanes,
@@ -59,81 +87,24 @@ D3 xor_reduce(std::vector<D3> v) {
 // (MomentSink), all [H*W][3] f64 in image orientation.
 int hc_render_aa(const pt_scene_desc* d, const pt_render_params* p, int force64, int32_t lanes,
                  double* sum, double* S, double* Q) {
-    HostScene H;
-    if (!prepare_scene(d, &H).empty()) return -1;
-    bind_host(&H);
+    Host h;
+    if (!h.open(d)) return -1;
     if (lanes < 1 || (lanes & (lanes - 1))) return -2;
-    Counters c = {};
-    double spill_mem[kSpillSlots];
-    const Spill sp{spill_mem, 1};
-    for (int iy = 0; iy < p->height; ++iy) {
-        for (int ix = 0; ix < p->width; ++ix) {
-            std::vector<D3> a(lanes), s(lanes), q(lanes);
-            for (int l = 0; l < lanes; ++l) {
-                const int32_t ns = l < p->spp ? (p->spp - l + lanes - 1) / lanes : 0;
-                const LaneJob J = lane_job(p, ix, iy, p->sample_begin + l, lanes, ns);
-                const AaPixel X{p->width, p->height, ix, iy};
-                MomentRegs M;
-                M.clear();
-                if (force64) {
-                    a[l] = render_lane_aa<true, true>(H.k, J, X, kNoEye, sp, &c);
-                    render_lane_moments_aa<true, true>(H.k, J, X, kNoEye, sp, &c, M);
-                } else {
-                    a[l] = render_lane_aa<false, true>(H.k, J, X, kNoEye, sp, &c);
-                    render_lane_moments_aa<false, true>(H.k, J, X, kNoEye, sp, &c, M);
-                }
-                s[l] = M.sum();
-                q[l] = M.sumsq();
-            }
-            const D3 ra = xor_reduce(a), rs = xor_reduce(s), rq = xor_reduce(q);
-            const size_t e = (size_t)(p->height - 1 - iy) * p->width + ix;
-            sum[3 * e] = ra.x; sum[3 * e + 1] = ra.y; sum[3 * e + 2] = ra.z;
-            S[3 * e] = rs.x; S[3 * e + 1] = rs.y; S[3 * e + 2] = rs.z;
-            Q[3 * e] = rq.x; Q[3 * e + 1] = rq.y; Q[3 * e + 2] = rq.z;
-        }
-    }
+    render_frame(h, p, lanes, sum, S, Q, [&](int ix, int iy, auto&& f) {
+        if (force64) aa_primary<true>(p, ix, iy, f);
+        else aa_primary<false>(p, ix, iy, f);
+    });
     return 0;
 }
 
-// An adaptive run on the host with antialiased samples: the accumulator's
-// pass loop (select by moment_err / adapt_active, adapt_k more samples from
-// sample n[e] on for each listed pixel, one lane per pixel) until no pixel is
-// active.  S, Q [H*W][3], n [H*W] in image orientation; returns the passes
-// made, or < 0.
+// accum_passes with antialiased samples
 int hc_accum_aa(const pt_scene_desc* d, const pt_render_params* p, double tol, double floor,
                 uint32_t min_spp, uint32_t max_spp, uint32_t step_spp, double* S, double* Q,
                 uint32_t* n) {
-    HostScene H;
-    if (!prepare_scene(d, &H).empty()) return -1;
-    bind_host(&H);
-    const AdaptK A{tol, floor, min_spp, max_spp, step_spp};
-    Counters c = {};
-    double spill_mem[kSpillSlots];
-    const Spill sp{spill_mem, 1};
-    const size_t np = (size_t)p->width * p->height;
-    for (size_t i = 0; i < 3 * np; ++i) S[i] = Q[i] = 0.0;
-    for (size_t i = 0; i < np; ++i) n[i] = 0;
-    for (int pass = 0; pass <= (int)max_spp + 1; ++pass) {
-        bool any = false;
-        for (size_t e = 0; e < np; ++e) {
-            const double err = moment_err(S + 3 * e, Q + 3 * e, n[e], floor);
-            if (!adapt_active(n[e], err, A)) continue;
-            const uint32_t k = adapt_k(n[e], A);
-            if (k == 0) continue;
-            any = true;
-            const int row = (int)(e / p->width), ix = (int)(e % p->width), iy = p->height - 1 - row;
-            const LaneJob J = lane_job(p, ix, iy, (int32_t)n[e], 1, (int32_t)k);
-            MomentRegs M;
-            M.clear();
-            render_lane_moments_aa<false, true>(H.k, J, AaPixel{p->width, p->height, ix, iy}, kNoEye, sp, &c, M);
-            const D3 s = M.sum(), q = M.sumsq();
-            S[3 * e] += s.x; S[3 * e + 1] += s.y; S[3 * e + 2] += s.z;
-            Q[3 * e] += q.x; Q[3 * e + 1] += q.y; Q[3 * e + 2] += q.z;
-            n[e] += k;
-        }
-        if (!any) return pass;
-    }
-    return -3;
+    Host h;
+    if (!h.open(d)) return -1;
+    return accum_passes(h, p, AdaptK{tol, floor, min_spp, max_spp, step_spp}, S, Q, n,
+                        [&](int ix, int iy, auto&& f) { aa_primary<false>(p, ix, iy, f); });
 }
 
 // Dev tool (scripts/aa_restart_stats.py): how often a wave of k_render_aa runs
@@ -149,12 +120,14 @@ int hc_accum_aa(const pt_scene_desc* d, const pt_render_params* p, double tol, d
 }  // extern "C"
 namespace {
 template <bool FORCE64, bool BVH>
-struct AaTraceSched : AaSched<FORCE64, BVH> {
+using AaSumSched = Sched<AaRay<FORCE64, BVH>, SumSink>;   // the sum form's scheduler of render_lane_sampled
+template <bool FORCE64, bool BVH>
+struct AaTraceSched : AaSumSched<FORCE64, BVH> {
     std::vector<int>* trace;   // queries at iteration i (index 0: before the loop)
     template <bool COUNT>
     bool advance(const SceneK& S, bool done, const Spill& sp, int* tri, D3* acc, Counters* cnt) {
         const int before = this->si;
-        const bool r = AaSched<FORCE64, BVH>::template advance<COUNT>(S, done, sp, tri, acc, cnt);
+        const bool r = AaSumSched<FORCE64, BVH>::template advance<COUNT>(S, done, sp, tri, acc, cnt);
         // start() traced samples before+1 .. si (the one that landed included)
         int q = 0;
         if (done) q = (r ? this->si : this->J.n_samples - 1) - before;
@@ -165,13 +138,12 @@ struct AaTraceSched : AaSched<FORCE64, BVH> {
 }  // namespace
 extern "C" {
 int hc_aa_restart_stats(const pt_scene_desc* d, const pt_render_params* p, int32_t lanes, int64_t* out) {
-    HostScene H;
-    if (!prepare_scene(d, &H).empty()) return -1;
-    bind_host(&H);
+    Host h;
+    if (!h.open(d)) return -1;
     if (lanes < 1 || lanes > 64 || (lanes & (lanes - 1))) return -2;
-    Counters c = {};
-    double spill_mem[kSpillSlots];
-    const Spill sp{spill_mem, 1};
+    const SceneK& K = h.H.k;
+    const Spill& sp = h.sp;
+    Counters& c = h.c;
     for (int i = 0; i < 6; ++i) out[i] = 0;
     std::vector<std::vector<int>> wave;
     auto flush = [&]() {
@@ -193,20 +165,20 @@ int hc_aa_restart_stats(const pt_scene_desc* d, const pt_render_params* p, int32
     for (int iy = 0; iy < p->height; ++iy) {
         for (int ix = 0; ix < p->width; ++ix) {
             for (int l = 0; l < lanes; ++l) {
-                const int32_t ns = l < p->spp ? (p->spp - l + lanes - 1) / lanes : 0;
-                const LaneJob J = lane_job(p, ix, iy, p->sample_begin + l, lanes, ns);
+                const LaneJob J = lane_of(p, pixel_key(p, ix, iy), l, lanes);
+                const int32_t ns = J.n_samples;
                 std::vector<int> t;
                 AaTraceSched<false, true> q{{J, AaPixel{p->width, p->height, ix, iy}, kNoEye, 0}, &t};
                 int tri = -1;
                 D3 acc = d3(0, 0, 0);
                 bool go = false;
                 if (ns > 0 && p->bounces > 0) {
-                    go = q.start(H.k, sp, &tri, &acc, &c);
+                    go = q.start(K, sp, &tri, &acc, &c);
                     t.push_back((go ? q.si : ns - 1) + 1);
                 } else {
                     t.push_back(0);
                 }
-                if (go) render_loop<false, false, true>(H.k, J, tri, sp, &c, q, &acc);
+                if (go) render_loop<false, false, true>(K, J, tri, sp, &c, q, &acc);
                 if (wave.empty()) out[4] += (p->spp + lanes - 1) / lanes;
                 wave.push_back(t);
                 if ((int)wave.size() == 64) flush();

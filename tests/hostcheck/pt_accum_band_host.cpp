@@ -2,8 +2,8 @@
 // accumulator's select (pt_path.h BandK, band_make, band_pixel) compiled for
 // the host on top of pt_hostcheck.cpp, so the CPU suite can compare it with
 // _abi.band_pixels and a direct construction from _abi.band_rows.  Built by
-// tests/test_adaptive_bands.py into a temporary directory with the hostcheck
-// Makefile's g++ flags.
+// tests/test_adaptive_bands.py into a temporary directory by the hostcheck
+// Makefile's pattern rule (tests/hostlib.py).
 #include "pt_hostcheck.cpp"
 
 extern "C" {

@@ -1,9 +1,9 @@
 // pt_accum_host.cpp — TEST INFRASTRUCTURE.  The adaptive sampler's lane code
-// (pt_path.h MomentSink / render_lane_moments, moment_err, adapt_active,
-// adapt_k) compiled for the host on top of pt_hostcheck.cpp, so the CPU suite
+// (pt_path.h render_lane_cached over FrameHit and MomentSink, moment_err,
+// adapt_active, adapt_k) compiled for the host on top of pt_hostcheck.cpp, so the CPU suite
 // can check the per-pixel moments against the oracle's per-sample colours and
 // the stop rule against numpy without a GPU.  Built by tests/test_adaptive.py
-// into a temporary directory with the hostcheck Makefile's g++ flags.
+// into a temporary directory by the hostcheck Makefile's pattern rule (tests/hostlib.py).
 #include "pt_hostcheck.cpp"
 
 extern "C" {
@@ -14,46 +14,26 @@ extern "C" {
 // 1 the memory home (MomentMem, stride 1).
 int hc_render_moments(const pt_scene_desc* d, const pt_render_params* p, int force64, int home,
                       double* S, double* Q, uint32_t* n) {
-    HostScene H;
-    if (!prepare_scene(d, &H).empty()) return -1;
-    bind_host(&H);
-    Counters c = {};
-    double spill_mem[kSpillSlots];
-    const Spill sp{spill_mem, 1};
-    const D3 eye = ld3(H.k.eye);
+    Host h;
+    if (!h.open(d)) return -1;
     for (int iy = 0; iy < p->height; ++iy) {
         for (int ix = 0; ix < p->width; ++ix) {
-            const double x = linspace_at(H.k.ortho[0], H.k.ortho[2], p->width, ix);
-            const double y = linspace_at(H.k.ortho[1], H.k.ortho[3], p->height, iy);
-            const D3 d0 = d3(x - eye.x, y - eye.y, 0.0 - eye.z);
-            LaneJob J;
-            J.seed = p->seed;
-            J.pixel = (uint32_t)ix * (uint32_t)p->height + (uint32_t)iy;
-            J.sample0 = p->sample_begin;
-            J.sample_stride = 1;
-            J.n_samples = p->spp;
-            J.bounces = p->bounces;
-            J.rr_depth = (p->flags & PT_FLAG_RR) ? p->rr_depth : -1;
-            D3 P0 = d3(0, 0, 0);
-            int tri0 = -1;
+            const size_t e = image_index(p, ix, iy);
+            auto lane = [&](auto& M) {   // the pixel's one lane into the home M
+                M.clear();
+                with_bool(force64 != 0, [&](auto F64) {
+                    const CentreHit c = centre_hit<decltype(F64)::value>(h, p, ix, iy);
+                    run_lane<decltype(F64)::value, false>(h, lane_of(p, pixel_key(p, ix, iy), 0, 1), c.hit, c.P0,
+                                                          MomentSink<std::decay_t<decltype(M)>>{M});
+                });
+                st3(S + 3 * e, M.sum());
+                st3(Q + 3 * e, M.sumsq());
+            };
             double mem[6];
             MomentMem Mm{mem, 1};
             MomentRegs Mr;
-            Mm.clear();
-            Mr.clear();
-            if (force64) {
-                if (p->bounces > 0) tri0 = closest<true, false>(H.k, eye, d0, -1, sp, &P0, &c, true);
-                if (home) render_lane_moments<true, false, true>(H.k, J, d0, tri0, P0, sp, &c, Mm);
-                else render_lane_moments<true, false, true>(H.k, J, d0, tri0, P0, sp, &c, Mr);
-            } else {
-                if (p->bounces > 0) tri0 = closest<false, false>(H.k, eye, d0, -1, sp, &P0, &c, true);
-                if (home) render_lane_moments<false, false, true>(H.k, J, d0, tri0, P0, sp, &c, Mm);
-                else render_lane_moments<false, false, true>(H.k, J, d0, tri0, P0, sp, &c, Mr);
-            }
-            const D3 s = home ? Mm.sum() : Mr.sum(), q = home ? Mm.sumsq() : Mr.sumsq();
-            const size_t e = (size_t)(p->height - 1 - iy) * p->width + ix;
-            S[3 * e] = s.x; S[3 * e + 1] = s.y; S[3 * e + 2] = s.z;
-            Q[3 * e] = q.x; Q[3 * e + 1] = q.y; Q[3 * e + 2] = q.z;
+            if (home) lane(Mm);
+            else lane(Mr);
             n[e] = (uint32_t)p->spp;
         }
     }

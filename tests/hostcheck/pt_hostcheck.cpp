@@ -15,6 +15,8 @@
 #include <algorithm>
 #include <memory>
 #include <random>
+#include <type_traits>
+#include <vector>
 
 #include "../../pathtracerpython_amd/csrc/pt_path.h"
 #include "../../pathtracerpython_amd/csrc/pt_wavefront.h"
@@ -39,6 +41,224 @@ static RenderK host_frame(const pt_render_params* p, int32_t first, int32_t row_
     return R;
 }
 
+// ---- the lane driver: what every hc_* entry that runs lane code shares ----
+
+// prepare_scene and bind_host; false: the scene (with its lens, its box) is refused
+static inline bool open_scene(const pt_scene_desc* d, HostScene* H, const pt_lens* L = nullptr,
+                              const double* box = nullptr) {
+    if (!prepare_scene(d, H, L, box).empty()) return false;
+    bind_host(H);
+    return true;
+}
+// An opened scene with one lane's spill home and the counters the lanes bump
+struct Host {
+    HostScene H;
+    Counters c = {};
+    double spill_mem[kSpillSlots];
+    const Spill sp{spill_mem, 1};
+    bool open(const pt_scene_desc* d, const pt_lens* L = nullptr, const double* box = nullptr) {
+        return open_scene(d, &H, L, box);
+    }
+};
+
+// A runtime choice as a template argument: f(std::true_type{}) or f(std::false_type{})
+template <class F>
+auto with_bool(bool b, F&& f) {
+    return b ? f(std::true_type{}) : f(std::false_type{});
+}
+
+static inline uint32_t pixel_key(const pt_render_params* p, int ix, int iy) {
+    return (uint32_t)ix * (uint32_t)p->height + (uint32_t)iy;
+}
+static inline size_t image_index(const pt_render_params* p, int ix, int iy) {
+    return (size_t)(p->height - 1 - iy) * p->width + ix;
+}
+static inline void st3(double* o, D3 v) { o[0] = v.x; o[1] = v.y; o[2] = v.z; }
+static inline void add3(double* o, D3 v) { o[0] += v.x; o[1] += v.y; o[2] += v.z; }
+
+// The job of n_samples samples from sample0 on under p (pt_radiance's launches
+// clamp rr_depth at 0: their callers pass a p that has it)
+static inline LaneJob lane_job(const pt_render_params* p, uint32_t pixel, int32_t sample0, int32_t stride,
+                               int32_t n_samples) {
+    return LaneJob{p->seed, pixel, sample0, stride, n_samples, p->bounces,
+                   (p->flags & PT_FLAG_RR) ? p->rr_depth : -1};
+}
+// lane l of `lanes` emulated lanes: samples sample_begin + l, + lanes, ...
+static inline LaneJob lane_of(const pt_render_params* p, uint32_t pixel, int l, int lanes) {
+    return lane_job(p, pixel, p->sample_begin + l, lanes, l < p->spp ? (p->spp - l + lanes - 1) / lanes : 0);
+}
+// the xor butterfly of store_pixel over a power of two of values; lane 0's result
+static inline D3 xor_reduce(std::vector<D3> v) {
+    const size_t n = v.size();
+    for (size_t m = 1; m < n; m <<= 1) {
+        std::vector<D3> w(n);
+        for (size_t i = 0; i < n; ++i) w[i] = v[i] + v[i ^ m];
+        v = w;
+    }
+    return v[0];
+}
+
+// One lane through the prologue its primary source takes (P0: a cached hit's
+// point; COUNT: FrameHit's counting form)
+template <bool F64, bool COUNT, class Primary, class Sink>
+auto run_lane(Host& h, const LaneJob& J, const Primary& prim, D3 P0, Sink sink) {
+    if constexpr (Primary::kCached) return render_lane_cached<F64, COUNT, true>(h.H.k, J, prim, P0, h.sp, &h.c, sink);
+    else return render_lane_sampled<F64, true>(h.H.k, J, prim, h.sp, &h.c, sink);
+}
+// ... with both sinks: the sum of SumSink, then the moments of MomentSink
+struct LaneSums {
+    D3 a, s, q;
+};
+template <bool F64, class Primary>
+LaneSums both_sinks(Host& h, const LaneJob& J, const Primary& prim, D3 P0) {
+    MomentRegs M;
+    M.clear();
+    const D3 a = run_lane<F64, false>(h, J, prim, P0, SumSink{});
+    run_lane<F64, false>(h, J, prim, P0, MomentSink<MomentRegs>{M});
+    return LaneSums{a, M.sum(), M.sumsq()};
+}
+// One element (a pixel, a ray record): lane(J) of each of its `lanes` (a power
+// of two) emulated lanes, reduced in store_pixel's xor order into row e of
+// sum, S and Q
+template <class Lane>
+void store_lanes(const pt_render_params* p, uint32_t pixel, int lanes, size_t e, double* sum, double* S, double* Q,
+                 Lane&& lane) {
+    std::vector<D3> a(lanes), s(lanes), q(lanes);
+    for (int l = 0; l < lanes; ++l) {
+        const LaneSums r = lane(lane_of(p, pixel, l, lanes));
+        a[l] = r.a; s[l] = r.s; q[l] = r.q;
+    }
+    st3(sum + 3 * e, xor_reduce(a));
+    st3(S + 3 * e, xor_reduce(s));
+    st3(Q + 3 * e, xor_reduce(q));
+}
+
+// Pixel (ix, iy)'s centre ray and its hit, which every sample restarts from (main.py:191)
+struct CentreHit {
+    FrameHit hit;
+    D3 P0;
+};
+template <bool F64>
+CentreHit centre_hit(Host& h, const pt_render_params* p, int ix, int iy) {
+    const SceneK& K = h.H.k;
+    const D3 eye = ld3(K.eye);
+    const double x = linspace_at(K.ortho[0], K.ortho[2], p->width, ix);
+    const double y = linspace_at(K.ortho[1], K.ortho[3], p->height, iy);
+    CentreHit r{{-1, d3(x - eye.x, y - eye.y, 0.0 - eye.z)}, d3(0, 0, 0)};
+    if (p->bounces > 0) r.hit.tri0 = closest<F64, false>(K, eye, r.hit.d0, -1, h.sp, &r.P0, &h.c, true);
+    return r;
+}
+// The ladder over (force64, PT_FLAG_LENS, PT_FLAG_AA), once: f(F64, prim, P0)
+// with the primary source of pixel (ix, iy) they select — a ray per sample from
+// LensRay or AaRay, or with neither flag the centre ray's cached hit
+static const AaEye kNoEye{nullptr, 0};   // (the device's per-wave table of the eye's origin terms: none here)
+template <class F>
+void with_primary(Host& h, const pt_render_params* p, bool force64, bool lens, bool aa, int ix, int iy, F&& f) {
+    const AaPixel X{p->width, p->height, ix, iy};
+    const D3 none = d3(0, 0, 0);
+    with_bool(force64, [&](auto F64) {
+        constexpr bool k64 = decltype(F64)::value;
+        if (lens && aa) return f(F64, LensRay<k64, true, true>{X}, none);
+        if (lens) return f(F64, LensRay<k64, true, false>{X}, none);
+        if (aa) return f(F64, AaRay<k64, true>{X, kNoEye}, none);
+        const CentreHit c = centre_hit<k64>(h, p, ix, iy);
+        return f(F64, c.hit, c.P0);
+    });
+}
+
+// ---- the wavefront walks, to completion (k_wf_shadow's and k_wf_closest's) ----
+
+// A walk's observer: visit(ref, top) before a QNode (ref >= 0) or a leaf
+// (ref < 0) is entered, false gives the walk up; visited(top) after a QNode.
+struct NoWatch {
+    bool visit(int, int) { return true; }
+    void visited(int) {}
+};
+template <class V, class A>
+struct Watcher {
+    V v;
+    A a;
+    bool visit(int ref, int top) { return v(ref, top); }
+    void visited(int top) { a(top); }
+};
+template <class V, class A>
+Watcher<V, A> watcher(V v, A a) {
+    return {v, a};
+}
+// the node visits' peak of a walk on the walk kernels' stacks: pk[0] the
+// largest T.top after a node visit, pk[1] the visits that left T.top above
+// their shared-memory part (16 entries)
+static inline auto peak_watch(int64_t* pk) {
+    return watcher([](int, int) { return true; },
+                   [pk](int top) {
+                       pk[0] = std::max<int64_t>(pk[0], top);
+                       if (top > 16) ++pk[1];
+                   });
+}
+
+// shadow ray k of a query, on the stack view St; false: the observer gave up
+template <class Watch = NoWatch>
+bool walk_shadow(const SceneK& K, WfShadowQ* q, int k, const Spill& sp, const ShadowStack& St, Watch&& w = Watch{}) {
+    Shadow1 r;
+    F3 o32;
+    int ogrp;
+    wf_get_shadow1(*q, k, &o32, &ogrp, &r);
+    ShadowTrav1 T;
+    s1_init(T, K, o32, ogrp, r, K.qroot);
+    while (T.ref != kNoRef) {
+        while (T.ref >= 0) {
+            if (!w.visit(T.ref, T.top)) return false;
+            s1_qnode(T, St, K, r);
+            w.visited(T.top);
+        }
+        if (T.ref != kNoRef) {
+            if (!w.visit(T.ref, T.top)) return false;
+            if (K.bunitc) s1_units<true, PT_WF_LRNG != 0>(T, K, &r, sp, T.ref);
+            else s1_units<false, PT_WF_LRNG != 0>(T, K, &r, sp, T.ref);
+            T.ref = s1_pop(T, St, K, r);
+        }
+    }
+    wf_put_shadow1(q, r);
+    return true;
+}
+// a closest query likewise
+template <class Watch = NoWatch>
+bool walk_closest(const SceneK& K, WfClosestQ* q, const Spill& sp, const ClosestStack& St, Watch&& w = Watch{}) {
+    ClosestAcc ca = wf_get_acc(*q);
+    ClosestTrav T;
+    ctrav_init(T, K, F3{q->o[0], q->o[1], q->o[2]}, q->ogrp, F3{q->d[0], q->d[1], q->d[2]}, ca.b1, K.qroot);
+    while (T.ref != kNoRef) {
+        while (T.ref >= 0) {
+            if (!w.visit(T.ref, T.top)) return false;
+            ctrav_qnode(T, St, K, &ca);
+            w.visited(T.top);
+        }
+        if (T.ref != kNoRef) {
+            if (!w.visit(T.ref, T.top)) return false;
+            if (K.bunitc) ctrav_leaf<false, true>(T, St, K, &ca, sp, nullptr);   // as k_wf_closest
+            else ctrav_leaf<false>(T, St, K, &ca, sp, nullptr);
+        }
+    }
+    q->a1 = ca.a1; q->a2 = ca.a2; q->b1 = ca.b1; q->i1 = ca.i1;
+    return true;
+}
+// Every walk the slots' shade steps asked for (want[t]), on per-lane local stacks
+static inline void run_walks(const SceneK& K, const std::vector<uint32_t>& want, WfPath* W, WfShadowQ* SQ,
+                             WfClosestQ* CQ) {
+    for (size_t t = 0; t < want.size(); ++t) {
+        const Spill sp{W[t].sp, 1};
+        int buf[kBvhStackLocal];
+        ClosestStackLocal L;
+        for (int k = 0; k < kLightSamples; ++k)
+            if ((want[t] >> k) & 1u) walk_shadow(K, &SQ[t], k, sp, ShadowStack{buf, 1});
+        if (want[t] & kWfWantClosest) walk_closest(K, &CQ[t], sp, L.view());
+    }
+}
+// a prepared scene the wavefront kernels take: a BVH whose walks fit their stacks
+static inline bool wf_walkable(const SceneK& K) { return K.n_bnode != 0 && K.n_qnode != 0 && K.qstack <= kBvhStack; }
+// a slot count per pixel, entry or record: a power of two up to 64
+static inline bool split_ok(uint32_t split) { return split != 0 && split <= 64 && (split & (split - 1)) == 0; }
+
 extern "C" {
 
 // sizes and field offsets of the C-ABI structs as the C++ compiler lays
@@ -59,48 +279,28 @@ int hc_abi_layout(int64_t* out) {
 // out: rows*W*3 float64 in image orientation.  counters[8] (optional).
 int hc_render(const pt_scene_desc* d, const pt_render_params* p, int force64,
               double* out, uint64_t* counters) {
-    HostScene H;
-    if (!prepare_scene(d, &H).empty()) return -1;
-    bind_host(&H);
+    Host h;
+    if (!h.open(d)) return -1;
     int32_t first, rows;
     if (!band_layout(p, &first, &rows)) return -2;
-    Counters c = {};
-    double spill_mem[kSpillSlots];
-    const Spill sp{spill_mem, 1};
     for (int r = 0; r < rows; ++r) {
         const int iy = first + r * p->row_step;
         for (int ix = 0; ix < p->width; ++ix) {
-            const D3 eye = ld3(H.k.eye);
-            const double x = linspace_at(H.k.ortho[0], H.k.ortho[2], p->width, ix);
-            const double y = linspace_at(H.k.ortho[1], H.k.ortho[3], p->height, iy);
-            const D3 d0 = d3(x - eye.x, y - eye.y, 0.0 - eye.z);
-            LaneJob J;
-            J.seed = p->seed;
-            J.pixel = (uint32_t)ix * (uint32_t)p->height + (uint32_t)iy;
-            J.sample0 = p->sample_begin;
-            J.sample_stride = 1;
-            J.n_samples = p->spp;
-            J.bounces = p->bounces;
-            J.rr_depth = (p->flags & PT_FLAG_RR) ? p->rr_depth : -1;
-            D3 P0 = d3(0, 0, 0);
-            int tri0 = -1;
-            D3 acc;
             // counters requested: the count-mode lane code (exact first
             // occluders); else the render kernel's own (object-level) one
-            if (force64) {
-                if (p->bounces > 0) tri0 = closest<true, false>(H.k, eye, d0, -1, sp, &P0, &c, true);
-                acc = counters ? render_lane<true, true>(H.k, J, d0, tri0, P0, sp, &c)
-                               : render_lane<true, false>(H.k, J, d0, tri0, P0, sp, &c);
-            } else {
-                if (p->bounces > 0) tri0 = closest<false, false>(H.k, eye, d0, -1, sp, &P0, &c, true);
-                acc = counters ? render_lane<false, true>(H.k, J, d0, tri0, P0, sp, &c)
-                               : render_lane<false, false>(H.k, J, d0, tri0, P0, sp, &c);
-            }
+            const D3 acc = with_bool(force64 != 0, [&](auto F64) {
+                return with_bool(counters != nullptr, [&](auto COUNT) {
+                    const CentreHit c = centre_hit<decltype(F64)::value>(h, p, ix, iy);
+                    return run_lane<decltype(F64)::value, decltype(COUNT)::value>(
+                        h, lane_of(p, pixel_key(p, ix, iy), 0, 1), c.hit, c.P0, SumSink{});
+                });
+            });
             double* o = out + ((size_t)(rows - 1 - r) * p->width + ix) * 3;
             o[0] = acc.x / p->spp; o[1] = acc.y / p->spp; o[2] = acc.z / p->spp;
         }
     }
     if (counters) {
+        const Counters& c = h.c;
         uint32_t v[8] = {c.closest_tests, c.shadow_tests, c.ray_bounces, c.shading_points,
                          c.light_hits, c.escapes, c.fallbacks, c.rescans};
         for (int i = 0; i < 8; ++i) counters[i] = v[i];
@@ -168,8 +368,7 @@ int hc_render_wavefront3(const pt_scene_desc* d, const pt_render_params* p, doub
     // entries: anything else is a corrupted stack (-5 instead of a walk that
     // never ends or leaves the tree)
     HostScene H;
-    if (!prepare_scene(d, &H).empty()) return -1;
-    bind_host(&H);
+    if (!open_scene(d, &H)) return -1;
     auto sane = [&](int ref, int top, int64_t work) {
         return ref < (int)H.qnode.size() && top >= 0 && top <= kBvhStack &&
                work <= 5 * (int64_t)H.qnode.size() + 1;
@@ -193,7 +392,24 @@ int hc_render_wavefront3(const pt_scene_desc* d, const pt_render_params* p, doub
     auto hist = [&](int kind, int ref) {
         if (depth_hist && ref >= 0) ++depth_hist[kind * 32 + std::min(qdepth[ref], 31)];
     };
-    if (H.k.n_bnode == 0 || H.k.n_qnode == 0 || H.k.qstack > kBvhStack) return -3;
+    // a walk's observer: the sanity check, the depth histogram, the counts and the peak
+    auto watch = [&](int kind, int64_t& work) {
+        return watcher(
+            [&, kind](int ref, int top) {
+                if (!sane(ref, top, ++work)) return false;
+                hist(kind, ref);
+                if (ref < 0) {
+                    ++ws[4 * kind + 2];
+                    ws[4 * kind + 3] += (~ref) & 7;
+                }
+                return true;
+            },
+            [&, kind](int top) {
+                ++ws[4 * kind + 1];
+                seen(kind, top);
+            });
+    };
+    if (!wf_walkable(H.k)) return -3;
     int32_t first, rows;
     if (!band_layout(p, &first, &rows)) return -2;
     const size_t n = (size_t)rows * p->width;
@@ -219,65 +435,21 @@ int hc_render_wavefront3(const pt_scene_desc* d, const pt_render_params* p, doub
             const Spill sp{W[i].sp, 1};
             for (int k = 0; k < kLightSamples; ++k) {   // one walk per open shadow ray, as k_wf_shadow
                 if (!((want[i] >> k) & 1u)) continue;
-                Shadow1 r;
-                F3 o32;
-                int ogrp;
-                wf_get_shadow1(SQ[i], k, &o32, &ogrp, &r);
                 ++ws[0];
-                ShadowTrav1 T;
                 int buf[kBvhStackLocal];
                 const ShadowStack K = nl > 0 ? ShadowStack{s_lds.get(), 1, s_glob.get(), 1, nl}
                                              : ShadowStack{buf, 1};
-                s1_init(T, H.k, o32, ogrp, r, H.k.qroot);
                 int64_t work = 0;
-                while (T.ref != kNoRef) {   // the walk, counted
-                    while (T.ref >= 0) {
-                        if (!sane(T.ref, T.top, ++work)) return -5;
-                        hist(0, T.ref);
-                        s1_qnode(T, K, H.k, r);
-                        ++ws[1];
-                        seen(0, T.top);
-                    }
-                    if (T.ref != kNoRef) {
-                        if (!sane(-1, T.top, ++work)) return -5;
-                        ++ws[2];
-                        ws[3] += (~T.ref) & 7;
-                        if (H.k.bunitc) s1_units<true, PT_WF_LRNG != 0>(T, H.k, &r, sp, T.ref);
-                        else s1_units<false, PT_WF_LRNG != 0>(T, H.k, &r, sp, T.ref);
-                        T.ref = s1_pop(T, K, H.k, r);
-                    }
-                }
-                wf_put_shadow1(&SQ[i], r);
+                if (!walk_shadow(H.k, &SQ[i], k, sp, K, watch(0, work))) return -5;
             }
             if (want[i] & kWfWantClosest) {
-                ClosestAcc ca = wf_get_acc(CQ[i]);
-                ClosestTrav T;
                 ClosestStackLocal L;
                 const ClosestStack K =
                     nl > 0 ? ClosestStack{c_ref.get(), c_dist.get(), 1, c_gref.get(), c_gdist.get(), 1, nl}
                            : L.view();
-                const WfClosestQ& q = CQ[i];
-                ctrav_init(T, H.k, F3{q.o[0], q.o[1], q.o[2]}, q.ogrp, F3{q.d[0], q.d[1], q.d[2]}, ca.b1,
-                           H.k.qroot);
                 ++ws[4];
                 int64_t work = 0;
-                while (T.ref != kNoRef) {   // ctrav_step, counted
-                    while (T.ref >= 0) {
-                        if (!sane(T.ref, T.top, ++work)) return -5;
-                        hist(1, T.ref);
-                        ctrav_qnode(T, K, H.k, &ca);
-                        ++ws[5];
-                        seen(1, T.top);
-                    }
-                    if (T.ref != kNoRef) {
-                        if (!sane(-1, T.top, ++work)) return -5;
-                        ++ws[6];
-                        ws[7] += (~T.ref) & 7;
-                        if (H.k.bunitc) ctrav_leaf<false, true>(T, K, H.k, &ca, sp, nullptr);   // as k_wf_closest
-                        else ctrav_leaf<false>(T, K, H.k, &ca, sp, nullptr);
-                    }
-                }
-                CQ[i].a1 = ca.a1; CQ[i].a2 = ca.a2; CQ[i].b1 = ca.b1; CQ[i].i1 = ca.i1;
+                if (!walk_closest(H.k, &CQ[i], sp, K, watch(1, work))) return -5;
             }
         }
     }
@@ -701,35 +873,18 @@ void hc_rng4(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t bounce, ui
 // tool: the lane-utilisation bound of a wave is sum / (64 max) over its 64).
 int hc_lane_iters(const pt_scene_desc* d, const pt_render_params* p, int32_t split,
                   int32_t* out) {
-    HostScene H;
-    if (!prepare_scene(d, &H).empty()) return -1;
-    bind_host(&H);
+    Host h;
+    if (!h.open(d)) return -1;
     int32_t first, rows;
     if (!band_layout(p, &first, &rows)) return -2;
-    double spill_mem[kSpillSlots];
-    const Spill sp{spill_mem, 1};
-    const D3 eye = ld3(H.k.eye);
     for (int r = 0; r < rows; ++r) {
         const int iy = first + r * p->row_step;
         for (int ix = 0; ix < p->width; ++ix) {
-            const double x = linspace_at(H.k.ortho[0], H.k.ortho[2], p->width, ix);
-            const double y = linspace_at(H.k.ortho[1], H.k.ortho[3], p->height, iy);
-            const D3 d0 = d3(x - eye.x, y - eye.y, 0.0 - eye.z);
-            Counters c0 = {};
-            D3 P0 = d3(0, 0, 0);
-            const int tri0 = p->bounces > 0 ? closest<false, false>(H.k, eye, d0, -1, sp, &P0, &c0, true) : -1;
+            const CentreHit c0 = centre_hit<false>(h, p, ix, iy);
             for (int c = 0; c < split; ++c) {
-                LaneJob J;
-                J.seed = p->seed;
-                J.pixel = (uint32_t)ix * (uint32_t)p->height + (uint32_t)iy;
-                J.sample0 = p->sample_begin + c;
-                J.sample_stride = split;
-                J.n_samples = c < p->spp ? (p->spp - c + split - 1) / split : 0;
-                J.bounces = p->bounces;
-                J.rr_depth = (p->flags & PT_FLAG_RR) ? p->rr_depth : -1;
-                Counters cnt = {};
-                render_lane<false, true>(H.k, J, d0, tri0, P0, sp, &cnt);
-                out[((size_t)r * p->width + ix) * split + c] = (int32_t)cnt.shading_points;
+                h.c = {};
+                run_lane<false, true>(h, lane_of(p, pixel_key(p, ix, iy), c, split), c0.hit, c0.P0, SumSink{});
+                out[((size_t)r * p->width + ix) * split + c] = (int32_t)h.c.shading_points;
             }
         }
     }

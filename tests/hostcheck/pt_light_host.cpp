@@ -1,7 +1,7 @@
 // pt_light_host.cpp — TEST INFRASTRUCTURE.  The light pick of the lane code
 // (pt_core.h pick_light and its forms, light_tri_of) on the host, on top of
 // pt_hostcheck.cpp.  Two uses, both from tests/test_light_pick_host.py, built
-// with the hostcheck Makefile's g++ flags into a temporary directory:
+// by the hostcheck Makefile's pattern rule (tests/hostlib.py) into a temporary directory:
 //   * a stand-alone program (main below): the counting forms against the
 //     loop form for every u = k / 2^24 and for u outside [0, 1) on synthetic
 //     tables, and the light point against the path through light_tri;

@@ -3,7 +3,7 @@
 // loop (Mat::nint, pt_prepare.h) and what pow_ref (pt_core.h) returns, on top
 // of pt_accum_host.cpp (and so pt_hostcheck.cpp), so that one library serves
 // tests/test_materials_host.py.  Built by that test into a temporary
-// directory with the hostcheck Makefile's g++ flags.
+// directory by the hostcheck Makefile's pattern rule (tests/hostlib.py).
 #include "pt_accum_host.cpp"
 
 extern "C" {

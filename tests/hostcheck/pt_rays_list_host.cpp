@@ -1,10 +1,10 @@
 // pt_rays_list_host.cpp — TEST INFRASTRUCTURE.  A ray accumulator's list pass
 // (pt_job.h rays_list_job, the mapping k_render_rays_list runs; pt_path.h
-// rays_primary, render_lane_moments_rays) compiled for the host on top of
-// pt_rays_host.cpp, so the CPU suite can check the mapping for every work-item
-// and a whole adaptive run over ray records against the oracle without a GPU.
-// Built by tests/test_rays_adaptive_host.py into a temporary directory with
-// the hostcheck Makefile's g++ flags (rays_list.mk).
+// rays_primary, RayHit with MomentSink through render_lane_cached) compiled for
+// the host on top of pt_rays_host.cpp, so the CPU suite can check the mapping
+// for every work-item and a whole adaptive run over ray records against the
+// oracle without a GPU.  Built by tests/test_rays_adaptive_host.py into a
+// temporary directory by the hostcheck Makefile's pattern rule (tests/hostlib.py).
 #include "pt_rays_host.cpp"
 
 namespace {
@@ -48,21 +48,17 @@ int hc_rays_list_job(const RayK* rays, uint32_t n_rays, const pt_render_params* 
 
 // One pass of k_render_rays_list on the host: the work-items of the launch
 // (whole blocks of 64, as the kernel's grid) mapped by rays_list_job, each
-// lane's primary hit by rays_primary and its paths by
-// render_lane_moments_rays, an entry's `split` lanes reduced in the kernel's
+// lane's primary hit by rays_primary and its paths by render_lane_cached
+// (RayHit, MomentSink), an entry's `split` lanes reduced in the kernel's
 // xor order and added to S, Q ([n_rays][3]) and n by lane 0.
 int hc_rays_list_pass(const pt_scene_desc* d, const double* box, const RayK* rays, uint32_t n_rays,
                       const pt_render_params* p, const pt_adapt_params* ap, int force64, uint32_t split,
                       const uint32_t* list, uint32_t n_list, double* S, double* Q, uint32_t* n) {
-    HostScene H;
-    if (!prepare_scene(d, &H, nullptr, box).empty()) return -1;
-    bind_host(&H);
+    Host h;
+    if (!h.open(d, nullptr, box)) return -1;
     if (split < 1 || split > 64 || (split & (split - 1))) return -2;
-    const RaysListK R = list_record(p, ap, split, n_list, n_rays, H.frame_x);
+    const RaysListK R = list_record(p, ap, split, n_list, n_rays, h.H.frame_x);
     const uint64_t threads = ((((uint64_t)n_list << R.split_log2) + 63u) / 64u) * 64u;
-    Counters c = {};
-    double spill_mem[kSpillSlots];
-    const Spill sp{spill_mem, 1};
     std::vector<uint32_t> n0(n, n + n_rays);   // every lane of the launch reads n before any lane 0 writes it
     for (uint64_t base = 0; base < threads; base += split) {
         std::vector<D3> s(split), q(split);
@@ -72,23 +68,19 @@ int hc_rays_list_pass(const pt_scene_desc* d, const double* box, const RayK* ray
             if (l == 0) j0 = j;
             MomentRegs M;
             M.clear();
-            if (j.valid) {
-                D3 P0 = d3(0, 0, 0);
-                int tri0 = -1;
-                if (j.J.n_samples > 0 && R.bounces > 0)
-                    tri0 = force64 ? rays_primary<true, true>(H.k, R.frame_x, ld3(j.ray->o), ld3(j.ray->d), sp, &P0, &c)
-                                   : rays_primary<false, true>(H.k, R.frame_x, ld3(j.ray->o), ld3(j.ray->d), sp, &P0, &c);
-                if (force64) render_lane_moments_rays<true, true>(H.k, j.J, j.ray, tri0, P0, sp, &c, M);
-                else render_lane_moments_rays<false, true>(H.k, j.J, j.ray, tri0, P0, sp, &c, M);
-            }
+            if (j.valid)
+                with_bool(force64 != 0, [&](auto F64) {
+                    D3 P0;
+                    const RayHit hit = ray_hit<decltype(F64)::value>(h, R.frame_x, j.ray,
+                                                                     j.J.n_samples > 0 && R.bounces > 0, &P0);
+                    run_lane<decltype(F64)::value, false>(h, j.J, hit, P0, MomentSink<MomentRegs>{M});
+                });
             s[l] = M.sum();
             q[l] = M.sumsq();
         }
         if (j0.valid && j0.k > 0) {
-            const D3 rs = xor_reduce(s), rq = xor_reduce(q);
-            const size_t e = (size_t)j0.e * 3;
-            S[e] += rs.x; S[e + 1] += rs.y; S[e + 2] += rs.z;
-            Q[e] += rq.x; Q[e + 1] += rq.y; Q[e + 2] += rq.z;
+            add3(S + (size_t)j0.e * 3, xor_reduce(s));
+            add3(Q + (size_t)j0.e * 3, xor_reduce(q));
             n[j0.e] += j0.k;
         }
     }

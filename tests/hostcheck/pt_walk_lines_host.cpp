@@ -3,8 +3,8 @@
 // a zero or an f32-subnormal component and rcp_dir's +-1e30 branch is never
 // taken.  hc_walk_lines runs the same two checks on the caller's lines
 // (tests/rays_any_ref.py: axis directions, d.z = 0, components of 1e-39).
-// Built by tests/test_rays_any_host.py into a temporary directory with the
-// hostcheck Makefile's g++ flags.
+// Built by tests/test_rays_any_host.py into a temporary directory by the
+// hostcheck Makefile's pattern rule (tests/hostlib.py).
 #include "pt_hostcheck.cpp"
 
 extern "C" {

@@ -4,7 +4,7 @@
 // against every uniform unit, the shipped unit-level closest form against the
 // per-member reference (verdict_m on the members' weight minimums with the
 // lean range) and against eval64.  Built by tests/test_unit_forms_host.py
-// with the Makefile's plain g++ flags.
+// by the hostcheck Makefile's pattern rule (tests/hostlib.py).
 #include "pt_hostcheck.cpp"
 
 namespace {

@@ -6,11 +6,11 @@ antialiased frames, and the checkpoint keys.  The GPU cases are
 tests/test_gpu_aa.py."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostlib
 import aa_ref
 from adaptive_sim import histogram, simulate
 from conftest import ROOT, quad_scene
@@ -25,14 +25,9 @@ _up = C.POINTER(C.c_uint32)
 
 @pytest.fixture(scope="module")
 def aa_host(tmp_path_factory):
-    """tests/hostcheck/pt_aa_host.cpp built with the hostcheck Makefile's g++
-    flags into a temporary directory."""
-    d = os.path.join(ROOT, "tests", "hostcheck")
-    out = str(tmp_path_factory.mktemp("aa_host") / "libaahost.so")
-    subprocess.run([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-shared",
-                    "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-o", out,
-                    "pt_aa_host.cpp"], cwd=d, check=True)
-    lib = C.CDLL(out)
+    """tests/hostcheck/pt_aa_host.cpp built by the hostcheck Makefile into a
+    temporary directory."""
+    lib = hostlib.build(tmp_path_factory.mktemp("aa_host"), "pt_aa_host")
     lib.hc_aa_jitter.restype = None
     lib.hc_aa_jitter.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, _dp]
     lib.hc_aa_dir.restype = C.c_int

@@ -1,19 +1,17 @@
 """The antialiased wavefront state machine on the host (pt_wavefront.h
 wf_aa_start / wf_shade_aa: a primary query per sample in the slot's own record;
 tests/hostcheck/pt_aa_wf_host.cpp), in its uniform and its list form, against
-the single kernel's lane code (pt_aa_host.cpp hc_render_aa: render_lane_aa /
-render_lane_moments_aa) bit for bit and against the oracle's antialiased
+the single kernel's lane code (pt_aa_host.cpp hc_render_aa: render_lane_sampled
+over AaRay, both sinks) bit for bit and against the oracle's antialiased
 per-sample colours (tests/aa_ref.py).  The GPU cases are
 tests/test_gpu_aa_wavefront.py."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostlib
 import aa_ref
-from conftest import ROOT
 
 from pathtracerpython_amd._abi import PT_FLAG_AA, PT_FLAG_RR, make_params
 from pathtracerpython_amd.pack import pack_scene
@@ -27,21 +25,12 @@ BOUNCES, SEED = 3, 5
 ALL = np.arange(W * H, dtype=np.uint32)
 
 
-def _build(tmp, name):
-    d = os.path.join(ROOT, "tests", "hostcheck")
-    out = str(tmp / ("lib" + name + ".so"))
-    subprocess.run([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-shared",
-                    "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-o", out, name + ".cpp"],
-                   cwd=d, check=True)
-    return C.CDLL(out)
-
-
 @pytest.fixture(scope="module")
 def libs(tmp_path_factory):
     """pt_aa_wf_host.cpp (the state machine) and pt_aa_host.cpp (the single
     kernel's lane code)."""
     tmp = tmp_path_factory.mktemp("aa_wf_host")
-    wf, lane = _build(tmp, "pt_aa_wf_host"), _build(tmp, "pt_aa_host")
+    wf, lane = hostlib.build(tmp, "pt_aa_wf_host"), hostlib.build(tmp, "pt_aa_host")
     wf.hc_aa_wf_render.restype = C.c_int
     wf.hc_aa_wf_render.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, _dp, _ip, _ip, C.c_int32]
     wf.hc_aa_wf_pass.restype = C.c_int
@@ -98,7 +87,7 @@ def wf_pass(lib, pk, p, lst, rule, split, S, Q, n, fresh=1):
 
 
 def lane_code(lib, pk, p, lanes):
-    """(sum, S, Q) of render_lane_aa / render_lane_moments_aa, `lanes` per pixel."""
+    """(sum, S, Q) of render_lane_sampled over AaRay (SumSink, MomentSink), `lanes` per pixel."""
     a, S, Q = (np.zeros((p.height, p.width, 3)) for _ in range(3))
     rc = lib.hc_render_aa(C.addressof(pk.desc), C.addressof(p), 0, int(lanes), a.ctypes.data_as(_dp),
                           S.ctypes.data_as(_dp), Q.ctypes.data_as(_dp))

@@ -5,11 +5,11 @@ pass loop against a stand-in accumulator, the CLI refusals and the ABI.  The
 GPU cases are tests/test_gpu_adaptive.py."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostlib
 from adaptive_sim import (active_numpy, err_numpy, histogram, k_numpy, oracle_samples, simulate)
 from conftest import CORNELL, ROOT
 
@@ -22,14 +22,9 @@ _up = C.POINTER(C.c_uint32)
 
 @pytest.fixture(scope="module")
 def accum_host(tmp_path_factory):
-    """tests/hostcheck/pt_accum_host.cpp built with the hostcheck Makefile's
-    g++ flags into a temporary directory."""
-    d = os.path.join(ROOT, "tests", "hostcheck")
-    out = str(tmp_path_factory.mktemp("accum_host") / "libaccumhost.so")
-    subprocess.run([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-shared",
-                    "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-o", out,
-                    "pt_accum_host.cpp"], cwd=d, check=True)
-    lib = C.CDLL(out)
+    """tests/hostcheck/pt_accum_host.cpp built by the hostcheck Makefile
+    into a temporary directory."""
+    lib = hostlib.build(tmp_path_factory.mktemp("accum_host"), "pt_accum_host")
     lib.hc_render_moments.restype = C.c_int
     lib.hc_adapt_rule.restype = C.c_int
     lib.hc_adapt_rule.argtypes = [_dp, _dp, _up, C.c_int64, C.c_double, C.c_double, C.c_uint32,

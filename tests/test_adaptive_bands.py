@@ -6,11 +6,11 @@ accumulators, the CLI refusals and the ABI.  The GPU cases are
 tests/test_gpu_adaptive_bands.py."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostlib
 from adaptive_sim import simulate
 from conftest import CORNELL, ROOT
 from test_adaptive import FakeAccum, fake_frames
@@ -24,14 +24,9 @@ from pathtracerpython_amd.render import MultiRenderer
 # --------------------------------------------------------- band mapping --
 @pytest.fixture(scope="module")
 def band_host(tmp_path_factory):
-    """tests/hostcheck/pt_accum_band_host.cpp built with the hostcheck
-    Makefile's g++ flags into a temporary directory."""
-    d = os.path.join(ROOT, "tests", "hostcheck")
-    out = str(tmp_path_factory.mktemp("band_host") / "libbandhost.so")
-    subprocess.run([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-shared",
-                    "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-o", out,
-                    "pt_accum_band_host.cpp"], cwd=d, check=True)
-    lib = C.CDLL(out)
+    """tests/hostcheck/pt_accum_band_host.cpp built by the hostcheck
+    Makefile into a temporary directory."""
+    lib = hostlib.build(tmp_path_factory.mktemp("band_host"), "pt_accum_band_host")
     lib.hc_band_pixels.restype = C.c_int64
     lib.hc_band_pixels.argtypes = [C.c_int32] * 6 + [C.POINTER(C.c_uint32), C.c_int64]
     return lib

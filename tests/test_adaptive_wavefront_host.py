@@ -5,14 +5,12 @@ the single kernel's lane code (hc_render_moments) bit for bit at split 1 and
 against the oracle's per-sample colours at wider splits.  The GPU cases are
 tests/test_gpu_adaptive_wavefront.py."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostlib
 from adaptive_sim import moments_upto, oracle_samples
-from conftest import ROOT
 
 from pathtracerpython_amd._abi import PT_FLAG_RR, make_params
 from pathtracerpython_amd.pack import pack_scene
@@ -24,21 +22,12 @@ W = H = 12
 BOUNCES, SEED = 3, 5
 
 
-def _build(tmp, name):
-    d = os.path.join(ROOT, "tests", "hostcheck")
-    out = str(tmp / ("lib" + name + ".so"))
-    subprocess.run([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-shared",
-                    "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-o", out, name + ".cpp"],
-                   cwd=d, check=True)
-    return C.CDLL(out)
-
-
 @pytest.fixture(scope="module")
 def libs(tmp_path_factory):
     """pt_accum_wf_host.cpp (the list pass) and pt_accum_host.cpp (the single
     kernel's lane code), built as tests/test_adaptive.py builds the latter."""
     tmp = tmp_path_factory.mktemp("accum_wf_host")
-    wf, mk = _build(tmp, "pt_accum_wf_host"), _build(tmp, "pt_accum_host")
+    wf, mk = hostlib.build(tmp, "pt_accum_wf_host"), hostlib.build(tmp, "pt_accum_host")
     wf.hc_accum_wf_pass.restype = C.c_int
     wf.hc_accum_wf_pass.argtypes = [C.c_void_p, C.c_void_p, _up, C.c_uint32, C.c_uint32, C.c_uint32,
                                     C.c_uint32, C.c_uint32, _dp, _dp, _up, C.POINTER(C.c_int32)]

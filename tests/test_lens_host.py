@@ -7,11 +7,11 @@ the stop rule on lens frames, the checkpoint keys and the argument checks.
 The GPU cases are tests/test_gpu_lens.py."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostlib
 import aa_ref
 import lens_ref
 from adaptive_sim import histogram, simulate
@@ -38,14 +38,9 @@ def lens_of(case):
 
 @pytest.fixture(scope="module")
 def lens_host(tmp_path_factory):
-    """tests/hostcheck/pt_lens_host.cpp built with the hostcheck Makefile's g++
-    flags into a temporary directory."""
-    d = os.path.join(ROOT, "tests", "hostcheck")
-    out = str(tmp_path_factory.mktemp("lens_host") / "liblenshost.so")
-    subprocess.run([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-shared",
-                    "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-o", out,
-                    "pt_lens_host.cpp"], cwd=d, check=True)
-    lib = C.CDLL(out)
+    """tests/hostcheck/pt_lens_host.cpp built by the hostcheck Makefile into a
+    temporary directory."""
+    lib = hostlib.build(tmp_path_factory.mktemp("lens_host"), "pt_lens_host")
     lib.hc_lens_point.restype = None
     lib.hc_lens_point.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int32, C.c_double, _dp]
     lib.hc_lens_dir.restype = C.c_int

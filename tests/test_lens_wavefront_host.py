@@ -2,17 +2,17 @@
 wf_lens_start / wf_shade_lens: a primary query per sample from the sample's own
 lens point, in the slot's own record; tests/hostcheck/pt_lens_wf_host.cpp), in
 its uniform and its list form, against the single kernel's lane code
-(pt_lens_host.cpp hc_render_lens: render_lane_lens / render_lane_moments_lens)
+(pt_lens_host.cpp hc_render_lens: render_lane_sampled over LensRay, both sinks)
 bit for bit and against the oracle's per-sample colours through the lens
 (tests/lens_ref.py on the mesh scene, cases A and B).  The GPU cases are
 tests/test_gpu_lens_wavefront.py."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostlib
 import lens_wf_ref as ref
 from conftest import ROOT
 
@@ -39,21 +39,12 @@ def lens_of(case):
     return make_lens((ref.CASES[case]["R"], ref.CASES[case]["zf"]))
 
 
-def _build(tmp, name):
-    d = os.path.join(ROOT, "tests", "hostcheck")
-    out = str(tmp / ("lib" + name + ".so"))
-    subprocess.run([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-shared",
-                    "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-o", out, name + ".cpp"],
-                   cwd=d, check=True)
-    return C.CDLL(out)
-
-
 @pytest.fixture(scope="module")
 def libs(tmp_path_factory):
     """pt_lens_wf_host.cpp (the state machine, and the antialiased one it is
     built on) and pt_lens_host.cpp (the single kernel's lane code)."""
     tmp = tmp_path_factory.mktemp("lens_wf_host")
-    wf, lane = _build(tmp, "pt_lens_wf_host"), _build(tmp, "pt_lens_host")
+    wf, lane = hostlib.build(tmp, "pt_lens_wf_host"), hostlib.build(tmp, "pt_lens_host")
     wf.hc_lens_wf_render.restype = C.c_int
     wf.hc_lens_wf_render.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, _dp, _ip, _ip,
                                      C.c_int32]

@@ -10,26 +10,18 @@ triangle, seven random areas, tables that are not monotone or not finite and
 must keep the loop), and as a library on the table prepare_scene builds for
 the Cornell room.  The GPU cases are tests/test_gpu_light_pick.py."""
 import ctypes as C
-import os
 import subprocess
 
 import pytest
 
-from conftest import ROOT
-
-HC = os.path.join(ROOT, "tests", "hostcheck")
-FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas"]
+import hostlib
 
 
 @pytest.fixture(scope="module")
 def built(tmp_path_factory):
-    """(program, library) of pt_light_host.cpp, the hostcheck Makefile's g++ flags."""
+    """(program, library) of pt_light_host.cpp, by the hostcheck Makefile."""
     d = tmp_path_factory.mktemp("light_host")
-    exe, so = str(d / "light_host"), str(d / "liblighthost.so")
-    cxx = os.environ.get("CXX", "g++")
-    subprocess.run([cxx] + FLAGS + ["-o", exe, "pt_light_host.cpp"], cwd=HC, check=True)
-    subprocess.run([cxx] + FLAGS + ["-fPIC", "-shared", "-o", so, "pt_light_host.cpp"], cwd=HC,
-                   check=True)
+    exe, so = hostlib.make(d, "pt_light_host"), hostlib.make(d, "libpt_light_host.so")
     return exe, so
 
 

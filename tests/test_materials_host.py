@@ -11,14 +11,14 @@ import ctypes as C
 import glob
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostlib
 import material_scenes as ms
 from adaptive_sim import active_numpy, err_numpy, histogram, k_numpy, simulate
-from conftest import GOLDEN, ROOT, hc_render
+from conftest import GOLDEN, hc_render
 from material_scenes import compare
 from oracle import oracle
 from pathtracerpython_amd._abi import PT_FLAG_RR, make_params
@@ -53,14 +53,9 @@ def frames(scenes):
 @pytest.fixture(scope="module")
 def mat_host(tmp_path_factory):
     """tests/hostcheck/pt_material_host.cpp (the lane code, the accumulator's
-    and the material helpers) built with the hostcheck Makefile's g++ flags
-    into a temporary directory."""
-    d = os.path.join(ROOT, "tests", "hostcheck")
-    out = str(tmp_path_factory.mktemp("mat_host") / "libmathost.so")
-    subprocess.run([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-shared",
-                    "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-o", out,
-                    "pt_material_host.cpp"], cwd=d, check=True)
-    lib = C.CDLL(out)
+    and the material helpers) built by the hostcheck Makefile into a temporary
+    directory."""
+    lib = hostlib.build(tmp_path_factory.mktemp("mat_host"), "pt_material_host")
     lib.hc_render.restype = C.c_int
     lib.hc_render_wavefront.restype = C.c_int
     lib.hc_render_moments.restype = C.c_int

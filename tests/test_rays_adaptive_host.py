@@ -8,11 +8,11 @@ checkpoint keys, the command line's argument checks and the image-order helper.
 The GPU cases are tests/test_gpu_rays_adaptive.py."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostlib
 import adaptive_sim
 import rays_adaptive_ref as ref
 from conftest import ROOT
@@ -29,12 +29,9 @@ NONE = 0xFFFFFFFF
 
 @pytest.fixture(scope="module")
 def list_host(tmp_path_factory):
-    """tests/hostcheck/pt_rays_list_host.cpp built by its make rule
-    (tests/hostcheck/rays_list.mk) into a temporary directory."""
-    out = str(tmp_path_factory.mktemp("rays_list_host"))
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "hostcheck"), "-f", "rays_list.mk", "rays_list",
-                    "BUILD=" + out], check=True)
-    lib = C.CDLL(os.path.join(out, "librayslist.so"))
+    """tests/hostcheck/pt_rays_list_host.cpp built by the hostcheck Makefile
+    into a temporary directory."""
+    lib = hostlib.build(tmp_path_factory.mktemp("rays_list_host"), "pt_rays_list_host")
     lib.hc_rays_list_job.restype = C.c_int
     lib.hc_rays_list_job.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, _up, C.c_uint32,
                                      _up, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]

@@ -9,16 +9,16 @@ twins on the classes of tests/rays_any_ref.py: the lane code
 cases are tests/test_gpu_rays_any.py."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostlib
 import adaptive_sim
 import rays_adaptive_ref as adaptive_ref
 import rays_any_ref as ra
 import rays_ref
-from conftest import GOLDEN, ROOT, random_scene
+from conftest import GOLDEN, random_scene
 from oracle import oracle
 
 from pathtracerpython_amd._abi import PT_FLAG_RR, make_adapt, make_params, make_rays
@@ -31,35 +31,23 @@ SCENES = ("cornell", "mesh", "rand")
 ALL = ra.CLASS_NAMES + ("overflow",)
 
 
-def _build(tmp, name):
-    d = os.path.join(ROOT, "tests", "hostcheck")
-    out = str(tmp / ("lib" + name + ".so"))
-    subprocess.run([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-shared",
-                    "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-o", out, name + ".cpp"],
-                   cwd=d, check=True)
-    return C.CDLL(out)
-
-
 @pytest.fixture(scope="module")
 def libs(tmp_path_factory):
     """(lane code, wavefront state machine, list pass, walk check) built as
     their own tests build them."""
     tmp = tmp_path_factory.mktemp("rays_any_host")
-    lane, wf = _build(tmp, "pt_rays_host"), _build(tmp, "pt_rays_wf_host")
+    lane, wf = hostlib.build(tmp, "pt_rays_host"), hostlib.build(tmp, "pt_rays_wf_host")
     lane.hc_radiance.restype = C.c_int
     lane.hc_radiance.argtypes = [C.c_void_p, _dp, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int32,
                                  _dp, _dp, _dp, _ip]
     wf.hc_rays_wf.restype = C.c_int
     wf.hc_rays_wf.argtypes = [C.c_void_p, _dp, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32, C.c_int, _dp, _dp,
                               _dp, _ip, _ip, _lp]
-    out = str(tmp_path_factory.mktemp("rays_any_list"))
-    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "hostcheck"), "-f", "rays_list.mk", "rays_list",
-                    "BUILD=" + out], check=True)
-    lst = C.CDLL(os.path.join(out, "librayslist.so"))
+    lst = hostlib.build(tmp, "pt_rays_list_host")
     lst.hc_rays_list_pass.restype = C.c_int
     lst.hc_rays_list_pass.argtypes = [C.c_void_p, _dp, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int,
                                       C.c_uint32, _up, C.c_uint32, _dp, _dp, _up]
-    walk = _build(tmp, "pt_walk_lines_host")
+    walk = hostlib.build(tmp, "pt_walk_lines_host")
     walk.hc_walk_lines.restype = C.c_int
     walk.hc_walk_lines.argtypes = [C.c_void_p, _dp, _dp, C.c_int64, _lp]
     return lane, wf, lst, walk

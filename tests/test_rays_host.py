@@ -7,11 +7,11 @@ scenes made by the older entries, the camera generators and the command line's
 argument checks.  The GPU cases are tests/test_gpu_rays.py."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostlib
 import rays_ref
 from conftest import ROOT, hc_render
 
@@ -26,14 +26,9 @@ TOL = 1e-12   # the project's f64 bar
 
 @pytest.fixture(scope="module")
 def rays_host(tmp_path_factory):
-    """tests/hostcheck/pt_rays_host.cpp built with the hostcheck Makefile's g++
-    flags into a temporary directory."""
-    d = os.path.join(ROOT, "tests", "hostcheck")
-    out = str(tmp_path_factory.mktemp("rays_host") / "librayshost.so")
-    subprocess.run([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-shared",
-                    "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-o", out,
-                    "pt_rays_host.cpp"], cwd=d, check=True)
-    lib = C.CDLL(out)
+    """tests/hostcheck/pt_rays_host.cpp built by the hostcheck Makefile into a
+    temporary directory."""
+    lib = hostlib.build(tmp_path_factory.mktemp("rays_host"), "pt_rays_host")
     lib.hc_radiance.restype = C.c_int
     lib.hc_radiance.argtypes = [C.c_void_p, _dp, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int32,
                                 _dp, _dp, _dp, _ip]

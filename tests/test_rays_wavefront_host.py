@@ -2,17 +2,17 @@
 WfRays, wf_rays_primary_step, wf_finish's ray mode, wf_begin_bounce_rays:
 a primary query per record, its hit cached, the record in the place of the
 pixel; tests/hostcheck/pt_rays_wf_host.cpp) against the single kernel's lane
-code (pt_rays_host.cpp hc_radiance: render_lane_rays /
-render_lane_moments_rays) bit for bit and against the oracle's per-sample
+code (pt_rays_host.cpp hc_radiance: render_lane_cached over RayHit, both
+sinks) bit for bit and against the oracle's per-sample
 colours (tests/rays_ref.py).  The GPU cases are
 tests/test_gpu_rays_wavefront.py."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostlib
 import deep_scenes
 import rays_ref
 from conftest import ROOT
@@ -36,21 +36,12 @@ ORACLE = tuple(c for c in rays_ref.PARITY_CASES if c[0] in ("mesh", "multi")) + 
     ("mesh", 16, 5, 3, 1, 0), ("mesh", 16, 5, 3, None, 5))
 
 
-def _build(tmp, name):
-    d = os.path.join(ROOT, "tests", "hostcheck")
-    out = str(tmp / ("lib" + name + ".so"))
-    subprocess.run([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-shared",
-                    "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-o", out, name + ".cpp"],
-                   cwd=d, check=True)
-    return C.CDLL(out)
-
-
 @pytest.fixture(scope="module")
 def libs(tmp_path_factory):
     """pt_rays_wf_host.cpp (the state machine, on the buffers of the
     antialiased and the lens one) and pt_rays_host.cpp (the lane code)."""
     tmp = tmp_path_factory.mktemp("rays_wf_host")
-    wf, lane = _build(tmp, "pt_rays_wf_host"), _build(tmp, "pt_rays_host")
+    wf, lane = hostlib.build(tmp, "pt_rays_wf_host"), hostlib.build(tmp, "pt_rays_host")
     wf.hc_rays_wf.restype = C.c_int
     wf.hc_rays_wf.argtypes = [C.c_void_p, _dp, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32, C.c_int, _dp, _dp,
                               _dp, _ip, _ip, _lp]

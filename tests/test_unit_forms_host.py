@@ -7,12 +7,12 @@ interval, no ambiguity lost, no certain verdict the f64 evaluation
 contradicts, and closest_bits_m rebuilding exactly the members' bits."""
 import ctypes as C
 import os
-import subprocess
 
 import pytest
 
+import hostlib
 import grazing
-from conftest import ROOT, quad_scene
+from conftest import quad_scene
 from pathtracerpython_amd.pack import pack_scene
 
 NAMES = ("candidate/triangle/interval differs", "ambiguity lost", "certain verdict wrong (eval64)",
@@ -21,14 +21,8 @@ NAMES = ("candidate/triangle/interval differs", "ambiguity lost", "certain verdi
 
 @pytest.fixture(scope="module")
 def forms():
-    """unit_forms_selftest.cpp with the Makefile's plain g++ flags."""
-    d = os.path.join(ROOT, "tests", "hostcheck")
-    out = os.path.join(d, "build", "libunitforms.so")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    subprocess.run([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-shared",
-                    "-ffp-contract=off", "-Wall", "-Wno-unknown-pragmas", "-o", out,
-                    "unit_forms_selftest.cpp"], cwd=d, check=True)
-    lib = C.CDLL(out)
+    """unit_forms_selftest.cpp built by the hostcheck Makefile."""
+    lib = hostlib.build(os.path.join(hostlib.HOSTCHECK, "build"), "unit_forms_selftest")
     lib.hc_unit_forms_selftest.restype = C.c_int
     return lib
 
