@@ -2203,11 +2203,7 @@ PT_HD void render_loop(const SceneK& S, const LaneJob& J, int tri, const Spill& 
 // one by one.  No bounces: main.py:192 never runs, the sum is 0 and a home
 // gets samples of 0.  The kernels and the host checks (tests/hostcheck) call
 // these two directly, the policies as temporaries: through a forwarding
-// function per pair every kernel's code moved.  The eight forwards render_lane,
-// render_lane_moments, ..._aa, ..._lens, ..._rays below keep the earlier
-// signatures and have no caller here any more: they stay so that the host
-// checks as they stood before their lane driver still build against this
-// header.
+// function per pair every kernel's code moved.
 //
 // A cached primary hit (prim.tri0, P0): a primary ray that escapes or hits
 // the light gives constant samples, added one by one.  The counters take the
@@ -2259,13 +2255,6 @@ PT_HD auto render_lane_sampled(const SceneK& S, const LaneJob& J, Primary prim, 
     if constexpr (!Sink::kMoments) return acc;
 }
 
-// All samples of one lane for one pixel (FrameHit); returns the SUM of sample
-// colours.
-template <bool FORCE64, bool COUNT, bool BVH = true>
-PT_HD D3 render_lane(const SceneK& S, const LaneJob& J, D3 d0, int tri0, D3 P0, const Spill& sp, Counters* cnt) {
-    return render_lane_cached<FORCE64, COUNT, BVH>(S, J, FrameHit{tri0, d0}, P0, sp, cnt, SumSink{});
-}
-
 // ------------------------------------------------- per-pixel moments --
 // Adaptive sampling (build extension): besides the sum S of a
 // pixel's sample colours the accumulator keeps the per-channel sum of their
@@ -2299,13 +2288,6 @@ struct MomentMem {
     PT_HD D3 sum() const { return d3(base[0], base[stride], base[2 * stride]); }
     PT_HD D3 sumsq() const { return d3(base[3 * stride], base[4 * stride], base[5 * stride]); }
 };
-
-// render_lane with the moments: the lane's sample colours into `home`.
-template <bool FORCE64, bool COUNT, bool BVH, class Home>
-PT_HD void render_lane_moments(const SceneK& S, const LaneJob& J, D3 d0, int tri0, D3 P0, const Spill& sp,
-                               Counters* cnt, Home& home) {
-    render_lane_cached<FORCE64, COUNT, BVH>(S, J, FrameHit{tri0, d0}, P0, sp, cnt, MomentSink<Home>{home});
-}
 
 // The stop rule of an adaptive run.  Every operation is f64, in this order
 // (the tests evaluate the same expressions in numpy and compare bits).
@@ -2498,21 +2480,6 @@ struct AaRay {
     }
 };
 
-// render_lane / render_lane_moments with jittered primary rays (AaSched: the
-// sum form's scheduler, Sched<AaRay<..>, SumSink>, under its earlier name)
-template <bool FORCE64, bool BVH>
-using AaSched = Sched<AaRay<FORCE64, BVH>, SumSink>;
-template <bool FORCE64, bool BVH>
-PT_HD D3 render_lane_aa(const SceneK& S, const LaneJob& J, const AaPixel& X, const AaEye& E, const Spill& sp,
-                        Counters* cnt) {
-    return render_lane_sampled<FORCE64, BVH>(S, J, AaRay<FORCE64, BVH>{X, E}, sp, cnt, SumSink{});
-}
-template <bool FORCE64, bool BVH, class Home>
-PT_HD void render_lane_moments_aa(const SceneK& S, const LaneJob& J, const AaPixel& X, const AaEye& E,
-                                  const Spill& sp, Counters* cnt, Home& home) {
-    render_lane_sampled<FORCE64, BVH>(S, J, AaRay<FORCE64, BVH>{X, E}, sp, cnt, MomentSink<Home>{home});
-}
-
 // ---------------------------------------------------------- thin lens --
 // PT_FLAG_LENS (build extension, include/pt_capi.h): sample s
 // of pixel k starts at its own point eye' of the lens disc and aims through
@@ -2585,17 +2552,6 @@ struct LensRay {
     }
 };
 
-// render_lane_aa / render_lane_moments_aa through the lens
-template <bool FORCE64, bool BVH, bool AA>
-PT_HD D3 render_lane_lens(const SceneK& S, const LaneJob& J, const AaPixel& X, const Spill& sp, Counters* cnt) {
-    return render_lane_sampled<FORCE64, BVH>(S, J, LensRay<FORCE64, BVH, AA>{X}, sp, cnt, SumSink{});
-}
-template <bool FORCE64, bool BVH, bool AA, class Home>
-PT_HD void render_lane_moments_lens(const SceneK& S, const LaneJob& J, const AaPixel& X, const Spill& sp,
-                                    Counters* cnt, Home& home) {
-    render_lane_sampled<FORCE64, BVH>(S, J, LensRay<FORCE64, BVH, AA>{X}, sp, cnt, MomentSink<Home>{home});
-}
-
 // ------------------------------------------------ caller-supplied rays --
 // pt_radiance (build extension, include/pt_capi.h): sample s
 // of a ray record is the reference's sample (main.py:186-271) with the primary
@@ -2656,17 +2612,5 @@ struct RayHit {
         sp.put3(kSpNd, ld3(ray->d));
     }
 };
-
-// render_lane / render_lane_moments for a record: tri0, P0 its primary hit
-template <bool FORCE64, bool BVH>
-PT_HD D3 render_lane_rays(const SceneK& S, const LaneJob& J, const RayK* ray, int tri0, D3 P0, const Spill& sp,
-                          Counters* cnt) {
-    return render_lane_cached<FORCE64, false, BVH>(S, J, RayHit{ray, tri0}, P0, sp, cnt, SumSink{});
-}
-template <bool FORCE64, bool BVH, class Home>
-PT_HD void render_lane_moments_rays(const SceneK& S, const LaneJob& J, const RayK* ray, int tri0, D3 P0,
-                                    const Spill& sp, Counters* cnt, Home& home) {
-    render_lane_cached<FORCE64, false, BVH>(S, J, RayHit{ray, tri0}, P0, sp, cnt, MomentSink<Home>{home});
-}
 
 }  // namespace pt
